@@ -20,8 +20,17 @@ stream's PCM.  Streams continue from step to step: frame numbers move on by F
 MD5 runs on its own HIP stream beside the next step's encode.  PCM is resident
 in HBM before the timed region (the same bytes each step); outputs stay in HBM.
 
-After the timed region the output is PROVED, not assumed: the device error word
-is checked (flacgpu_sync_check), a sample of streams' last-step frames is
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does what the headline
+needs and no more: it builds the input, warms up, times the N steps, reads the
+device error word (flacgpu_sync_check) and prints the line (metric, value, unit,
+ms_per_step, the timed steps' per-kernel event times and the roofline priced from
+them).  `--dump-outputs DIR` adds DIR/<name>.npy of what the last timed step left
+in the caller's buffers (dump_outputs: every frame's size and offset, the carried
+MD5 states, a seeded sample of the bitstream); the input is seeded, so two builds
+can be compared output for output.  Every other leg below runs under `--full`.
+
+With `--full` the output is PROVED after the timed region, not assumed: the device
+error word is checked (flacgpu_sync_check), a sample of streams' last-step frames is
 compared byte for byte with the CPU restatement (oracle/, with the same frame
 numbers), and their carried MD5 states are finalised on the device and compared
 with hashlib over the bytes they absorbed.  `output_ok` is that comparison.
@@ -34,11 +43,11 @@ prints nothing: rank 0's JSON line is the only stdout line); under torchrun
 ranks shard streams with no data-path collective (weak scaling); a barrier and
 a max-over-ranks reduction bracket the timed region.
 
-After the headline (config 2) the default run times BASELINE configs 3, 4 and
+After the headline (config 2) the `--full` run times BASELINE configs 3, 4 and
 5 as their own lines (`configs`: 65536-block steps, the same barrier + max over
 ranks, output compared with the oracle, CPU port per config at N = 1).
 
-The JSON line also carries:
+The JSON line also carries (stream_curve, end_to_end and cpu_baseline under `--full`):
   roofline      -- the dominant kernel (analysis, pack or MD5: the longest mean
                    launch), its algorithmic bytes per launch / its mean launch time
                    from HIP events on its stream, against 8 TB/s; `traffic` from the
@@ -135,9 +144,19 @@ def parse():
                    help="other BASELINE configs timed as their own lines after the headline ('' = none)")
     p.add_argument("--cfg-frames", type=int, default=65536, help="blocks per GPU per step of each --configs line")
     p.add_argument("--cfg-steps", type=int, default=20)
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also run every other leg: oracle comparison of the output (output_ok), "
+                        "CPU baselines, the other configs, stream curve, sharded stream, end-to-end")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last step's outputs as DIR/<name>.npy (rank 0)")
     a = p.parse_args()
     if a.config:
         a.channels, a.bits, a.rate, a.lpc = PRESETS[a.config]
+    if not a.full:
+        # the plain run: set up, warm up, time the steps, (dump,) print the line
+        a.no_cpu = a.no_curve = a.no_e2e = a.no_sharded = True
+        if not a.cpu_only:  # --cpu-only is a run of its own: its legs are what it was asked for
+            a.configs = ""
     return a
 
 
@@ -255,6 +274,50 @@ def run_timed(w, steps, warmup, dist=None):
         dist.barrier()
     w.enc.set_timing(False)
     return t1 - t0
+
+
+DUMP_SEED = 20260821
+DUMP_FRAMES = 512  # frames of the bitstream sample
+DUMP_BYTES = 8 << 20  # bitstream bytes of the sample at most (float32: 32 MiB of the 64 MB the dump may take)
+
+
+def dump_outputs(w, path):
+    """What the last timed step left in the caller's buffers, as <path>/<name>.npy (float64 unless noted):
+    frame_bytes    every frame's size;
+    frame_offsets  every frame's offset in the output buffer;
+    total_bytes    the step's bitstream bytes;
+    md5_h, md5_bytes  every stream's carried MD5 chaining value (n_streams x 4) and absorbed byte count;
+    sample_frames  the frames of the bitstream sample: DUMP_FRAMES frame indices drawn once with
+                   DUMP_SEED, in ascending order, cut where their bytes would pass DUMP_BYTES;
+    bitstream_sample  those frames' bytes, one after another (float32).
+    The whole bitstream is gigabytes, hence the sample; sizes and offsets cover every frame."""
+    import numpy as np
+    import torch
+
+    w.enc.sync_check(w.stream.cuda_stream)
+    w.enc.sync_check(w.md5_stream.cuda_stream)
+    os.makedirs(path, exist_ok=True)
+    sizes = w.d_fb.cpu().numpy().astype(np.int64)
+    offs = w.d_off.cpu().numpy().astype(np.int64)
+    n = len(sizes)
+    out = {"frame_bytes": sizes.astype(np.float64), "frame_offsets": offs.astype(np.float64),
+           "total_bytes": np.array([int(w.d_tot[0].item())], dtype=np.float64)}
+    if w.md5 == "device":
+        st = w.d_state.cpu().numpy().view(np.uint32).reshape(w.S, 8)  # flacgpu_md5_state: h[4], u64 bytes, ...
+        out["md5_h"] = st[:, :4].astype(np.float64)
+        out["md5_bytes"] = (st[:, 4].astype(np.float64) + st[:, 5].astype(np.float64) * 4294967296.0)
+    rng = np.random.Generator(np.random.PCG64(DUMP_SEED))
+    picks = np.sort(rng.choice(n, size=min(DUMP_FRAMES, n), replace=False))
+    keep = int(np.searchsorted(np.cumsum(sizes[picks]), DUMP_BYTES, side="right"))
+    picks = picks[:keep]
+    # bounds before the device reads: a frame inside the buffer, whatever the size arrays hold
+    assert all(0 <= offs[f] and 0 <= sizes[f] and offs[f] + sizes[f] <= w.out_cap for f in picks)
+    parts = [w.d_out[int(offs[f]):int(offs[f] + sizes[f])] for f in picks]
+    body = torch.cat(parts).cpu().numpy() if parts else np.zeros(0, dtype=np.uint8)
+    out["sample_frames"] = picks.astype(np.float64)
+    out["bitstream_sample"] = body.astype(np.float32)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def verify(args, w, buf, fb, n_verify, dev, frames=True):
@@ -1200,7 +1263,7 @@ def rate_units(value, channels, rate):
 
 
 def config_line(args, cfg, dist, rank, world, dev, cpu=None):
-    """One BASELINE config (c3 / c4 / c5) as its own timed line inside the default run: its preset,
+    """One BASELINE config (c3 / c4 / c5) as its own timed line inside the --full run: its preset,
     65536-block steps, barrier + max over ranks, output compared with the oracle after timing, the
     CPU port timed on rank 0 at N = 1 (one core, P cores, and fixed-only for the LPC configs)."""
     import numpy as np
@@ -1525,6 +1588,8 @@ def main():
     samples_per_rank = args.frames * 4096
     value = samples_per_rank * world * args.steps / elapsed / 1e6
     ms_per_step = elapsed / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(w, args.dump_outputs)  # before verify(), which finalises the carried MD5 states
 
     kt = kernel_times(enc)
     fbytes = w.d_fb.cpu().numpy().astype(np.int64)
@@ -1533,7 +1598,13 @@ def main():
     key = workload_key(args)
     roof = roofline_of(args, kt, args.steps, pcm_bytes, int(fbytes.sum()), ms_per_step, key)
 
-    ok, vinfo = verify(args, w, buf, fb, args.verify_streams, dev) if rank == 0 else (True, {})
+    if args.full:
+        ok, vinfo = verify(args, w, buf, fb, args.verify_streams, dev) if rank == 0 else (True, {})
+    else:
+        # the plain run reads the device error word only; output_ok (the oracle comparison) is --full's
+        enc.sync_check(w.stream.cuda_stream)
+        enc.sync_check(w.md5_stream.cuda_stream)
+        ok, vinfo = None, None
     w.close()
 
     sharded = None

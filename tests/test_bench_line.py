@@ -121,6 +121,62 @@ def test_compact_line_bounded_even_when_blocks_grow():
     assert len(json.dumps(bench.compact_line(full, "x"))) <= bench.LINE_MAX
 
 
+def _parse(monkeypatch, *argv):
+    monkeypatch.setattr("sys.argv", ["bench.py", *argv])
+    return bench.parse()
+
+
+def test_plain_run_has_no_side_legs_and_full_keeps_them(monkeypatch):
+    """`bench.py --gpus 1 --steps N --warmup W` is the headline alone; --full is the run with every leg."""
+    a = _parse(monkeypatch, "--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_cpu and a.no_curve and a.no_e2e and a.no_sharded and a.configs == ""
+    f = _parse(monkeypatch, "--full", "--dump-outputs", "d")
+    assert f.full and f.dump_outputs == "d" and f.configs == "c3,c4,c5"
+    assert not (f.no_cpu or f.no_curve or f.no_e2e or f.no_sharded)
+    assert _parse(monkeypatch, "--full", "--no-e2e", "--configs=").no_e2e
+    # the CPU legs alone are a run of their own and keep the configs they were given
+    assert _parse(monkeypatch, "--cpu-only", "--configs=c5").configs == "c5"
+
+
+def test_dump_outputs_arrays(tmp_path):
+    """dump_outputs on host tensors laid out as the workload's: float32/float64 .npy, sizes and
+    offsets of every frame, the MD5 states' words, and whole frames of the bitstream at seeded picks."""
+    import types
+
+    import numpy as np
+    import torch
+
+    n, S = 1000, 10
+    rng = np.random.Generator(np.random.PCG64(1))
+    sizes = rng.integers(20000, 30000, n)
+    offs = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+    body = rng.integers(0, 256, int(sizes.sum()), dtype=np.uint8)
+    st = np.zeros((S, 8), dtype=np.uint32)
+    st[:, :4] = rng.integers(0, 1 << 32, (S, 4), dtype=np.uint64)
+    st[:, 4], st[:, 5] = 0x80000000, 3  # 3 * 2^32 + 2^31 bytes absorbed
+    stream = types.SimpleNamespace(cuda_stream=0)
+    w = types.SimpleNamespace(enc=types.SimpleNamespace(sync_check=lambda s: None), stream=stream, md5_stream=stream,
+                              S=S, md5="device", out_cap=len(body), d_out=torch.from_numpy(body),
+                              d_fb=torch.from_numpy(sizes.astype(np.int32)), d_off=torch.from_numpy(offs),
+                              d_tot=torch.tensor([len(body), 0]), d_state=torch.from_numpy(st.view(np.uint8).reshape(-1)))
+    bench.dump_outputs(w, str(tmp_path / "o"))
+    d = {f[:-4]: np.load(tmp_path / "o" / f) for f in os.listdir(tmp_path / "o")}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert sum(a.nbytes for a in d.values()) <= 64 << 20
+    assert np.array_equal(d["frame_bytes"], sizes) and np.array_equal(d["frame_offsets"], offs)
+    assert d["total_bytes"].tolist() == [len(body)]
+    assert np.array_equal(d["md5_h"], st[:, :4]) and d["md5_bytes"].tolist() == [3 * 2.0 ** 32 + 2.0 ** 31] * S
+    picks = d["sample_frames"].astype(np.int64)
+    assert np.all(np.diff(picks) > 0) and 0 < len(picks) <= bench.DUMP_FRAMES
+    assert sizes[picks].sum() <= bench.DUMP_BYTES < sizes[picks].sum() + 30000  # cut where the next frame would pass
+    want = np.concatenate([body[offs[f]:offs[f] + sizes[f]] for f in picks])
+    assert np.array_equal(d["bitstream_sample"], want)
+    # the picks are drawn once from a fixed seed: a second dump takes the same frames
+    bench.dump_outputs(w, str(tmp_path / "p"))
+    assert np.array_equal(np.load(tmp_path / "p" / "sample_frames.npy"), d["sample_frames"])
+
+
 def test_detail_sidecar_written(tmp_path, monkeypatch):
     p = tmp_path / "d.json"
     monkeypatch.setenv("FLACGPU_BENCH_DETAIL", str(p))

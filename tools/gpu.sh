@@ -27,7 +27,7 @@
 #   tools/gpu.sh cpuplace <tag>                            CPU-baseline legs alone (no GPU) under each thread
 #                                                          placement -> gpurun_out/<tag>_cpu_<place>.json
 #   tools/gpu.sh final  <tag>                              tests + smoke + profiles of every config at
-#                                                          its bench workload + the default bench line
+#                                                          its bench workload + the bench.py --full line
 set -o pipefail
 CMD=$1; TAG=${2:-run}; shift 2 || shift $#
 REPO=$(pwd)
@@ -105,7 +105,7 @@ do_ab() {  # "<configs>" <variant>...
           done
         fi
         local out=gpurun_out/ab_${TAG}_${cfg}_${name}_$rep.json
-        env "${envs[@]}" timeout -k 10 300 python bench.py $CA --steps $ST --warmup 3 --no-cpu --no-curve \
+        env "${envs[@]}" timeout -k 10 300 python bench.py --full $CA --steps $ST --warmup 3 --no-cpu --no-curve \
           --no-e2e --no-sharded --verify-streams 8 $AB_ARGS > $out 2> $out.err || { echo "FAIL $cfg $name"; tail -5 $out.err; return 1; }
         python3 -c "
 import json, sys
@@ -185,6 +185,6 @@ case $CMD in
     do_profile ${TAG}_c3 c3 65536 16384 > gpurun_out/${TAG}_prof_c3.log 2>&1 &&
     do_profile ${TAG}_c4 c4 65536 16384 > gpurun_out/${TAG}_prof_c4.log 2>&1 &&
     do_profile ${TAG}_c5 c5 65536 16384 > gpurun_out/${TAG}_prof_c5.log 2>&1 &&
-    do_bench ;;
+    do_bench --full ;;
   *) sed -n 2,25p "$0"; exit 2 ;;
 esac
