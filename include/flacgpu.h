@@ -412,11 +412,71 @@ int flacgpu_encode_files(flacgpu_ctx *ctx, uint32_t n_files, const void *const *
  * (Config.default for the WAV's channels and bit depth). */
 int flacgpu_wav_to_flac(int device, const void *wav, size_t wav_len, uint8_t *out, size_t out_cap, size_t *out_len);
 
+/* ---- Decode and verify (no reference counterpart: the reference's readme lists a decoder as
+ *      queued).  Frames are decoded where the encode entry points leave them; DESIGN.md
+ *      "Decode and verify". ------------------------------------------------------------------ */
+/* Per-frame status.  1..7 are minus the codes of the CPU verifier decoder (oracle/flac_decode.c),
+ * checked in its order; the first failure wins. */
+enum { FLACGPU_DEC_OK = 0, FLACGPU_DEC_SYNC = 1, FLACGPU_DEC_HEADER = 2, FLACGPU_DEC_CRC8 = 3,
+       FLACGPU_DEC_SUBFRAME = 4, FLACGPU_DEC_CRC16 = 5, FLACGPU_DEC_TRUNCATED = 6, FLACGPU_DEC_RANGE = 7,
+       FLACGPU_DEC_MISMATCH = 8 };
+typedef struct {                             /* 32 bytes */
+    uint32_t status, block_size;
+    uint64_t number;                         /* coded frame number */
+    uint32_t sample_rate;
+    uint32_t first_bad;                      /* MISMATCH: first differing interleaved sample of the frame;
+                                                0xFFFFFFFF: frame number / block size not the expected one */
+    uint8_t channel_assign, bits, pad[6];
+} flacgpu_decode_result;
+
+/* Decode n_frames (<= max_frames_per_call) device-resident frames of the context's channel count
+ * and bit depth: frame f is the d_frame_bytes[f] bytes at d_frames + d_frame_offsets[f] (the
+ * layout of flacgpu_encode_plan_device).  Its PCM region starts d_pcm_offsets[f] bytes into
+ * d_pcm_out / d_pcm_expect; d_pcm_offsets NULL: the frames are consecutive blocks of one stream
+ * (offsets from a scan of the parsed block sizes).  d_pcm_out (NULL: none, capacity pcm_cap
+ * bytes) receives interleaved little-endian PCM of bits/8 bytes per sample; a frame whose region
+ * would pass pcm_cap gets RANGE.  d_pcm_expect (NULL: none) is compared with the decoded samples:
+ * a difference gives MISMATCH.  A frame with a non-zero status writes no PCM.  d_results[f] and
+ * *d_bad_count (frames with a non-zero status) are device memory.  Asynchronous on hip_stream.
+ * The decode scratch of a context is allocated by its first decode call.  Blocks larger than
+ * the context's block_size are RANGE. */
+int flacgpu_decode_frames_device(flacgpu_ctx *ctx, const uint8_t *d_frames, const uint64_t *d_frame_offsets,
+                                 const uint32_t *d_frame_bytes, uint64_t n_frames, const uint64_t *d_pcm_offsets,
+                                 uint8_t *d_pcm_out, uint64_t pcm_cap, const uint8_t *d_pcm_expect,
+                                 flacgpu_decode_result *d_results, uint32_t *d_bad_count, void *hip_stream);
+/* The --verify of flacgpu_encode_plan_device: decode every frame of the plan from d_out and compare
+ * it with the PCM it was encoded from (d_pcm).  The expected PCM offset, frame number and sample
+ * count of every frame come from the plan's frame table; another number or size gives MISMATCH
+ * with first_bad = 0xFFFFFFFF.  The plan must hold at most max_frames_per_call frames. */
+int flacgpu_verify_plan_device(flacgpu_ctx *ctx, const flacgpu_plan *plan, const void *d_pcm, const uint8_t *d_out,
+                               const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                               flacgpu_decode_result *d_results, uint32_t *d_bad_count, void *hip_stream);
+/* Host buffers, synchronous, in chunks of max_frames_per_call: the concatenated frames of one
+ * stream to pcm_out (the PCM of the frames with status 0, each at the place its predecessors'
+ * block sizes give it); *n_samples = interchannel samples.  Returns FLACGPU_OK with the
+ * per-frame statuses in results[]; the call's own errors use the codes above. */
+int flacgpu_decode_frames(flacgpu_ctx *ctx, const uint8_t *frames, const uint32_t *frame_bytes, uint64_t n_frames,
+                          uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, flacgpu_decode_result *results);
+/* Frame index of a FLAC file in memory (host only, no GPU): "fLaC", the metadata blocks
+ * (STREAMINFO to *streaminfo, the others skipped by length), then the frame boundaries: a frame
+ * ends where a CRC-16 over it is good and the next frame header (sync code, good CRC-8) or the
+ * end of the data follows.  streaminfo NULL: flac points at a bare run of frames.  frame_bytes[]
+ * (capacity cap) gets the sizes, *n_frames their count (also when cap is too small:
+ * FLACGPU_ERR_OUTPUT_TOO_SMALL), *first_frame_offset (may be NULL) the first frame's offset. */
+int flacgpu_flac_index(const void *flac, size_t len, flacgpu_streaminfo *streaminfo, size_t *first_frame_offset,
+                       uint32_t *frame_bytes, size_t cap, size_t *n_frames);
+/* Index, decode (flacgpu_decode_frames) and MD5 (the host engine) of a whole file whose channel
+ * count and bit depth are the context's; *md5_ok (may be NULL) = the PCM's MD5 and sample count
+ * are STREAMINFO's.  A damaged frame makes the call fail with FLACGPU_ERR_INVALID_INPUT. */
+int flacgpu_decode_file(flacgpu_ctx *ctx, const void *flac, size_t len, uint8_t *pcm_out, size_t pcm_cap,
+                        uint64_t *n_samples, int *md5_ok);
+
 /* ---- Instrumentation ---------------------------------------------------- */
 /* Kernel ids for flacgpu_kernel_time: frame analysis (4096-sample frames /
  * short frames), frame-size scan, frame packing (all frames), stream MD5. */
 enum { FLACGPU_K_ANALYZE = 0, FLACGPU_K_ANALYZE_TAIL = 1, FLACGPU_K_SCAN = 2, FLACGPU_K_PACK = 3, FLACGPU_K_MD5 = 4,
-       FLACGPU_K_COUNT = 5 };
+       FLACGPU_K_DEC_PARSE = 5, FLACGPU_K_DEC_RECON = 6, /* the decoder's parse and reconstruct kernels */
+       FLACGPU_K_COUNT = 7 };
 /* When enabled, every launch of kernel k is bracketed by HIP events on the
  * stream it runs on; flacgpu_kernel_time returns the number of timed launches
  * and their summed device milliseconds since the last reset. */

@@ -19,6 +19,7 @@
 
 #include "../../include/flacgpu.h"
 #include "fg_common.hpp"
+#include "fg_dec.hpp"
 #include "fg_internal.hpp"
 #include "fg_layout.hpp"
 #include "fg_md5_host.hpp"
@@ -36,6 +37,11 @@ hipError_t launch_advance_jobs(FrameJob *jobs, uint64_t n, uint64_t delta, hipSt
 hipError_t launch_md5_blocks(uint32_t *state, const uint32_t *blocks, uint64_t n_blocks, hipStream_t st);
 uint32_t md5_workgroups(uint32_t n, int kernel);
 hipError_t launch_streaminfo_replay(const uint32_t *sizes, uint64_t n, uint32_t *minmax, hipStream_t st);
+// fg_dec.hip
+hipError_t launch_dec_parse(const dec::Args &a, hipStream_t st);
+hipError_t launch_dec_recon(const dec::Args &a, hipStream_t st);
+hipError_t launch_dec_expect(const FrameJob *jobs, uint64_t n, uint64_t *pcm_off, uint64_t *number, uint32_t *ns,
+                             hipStream_t st);
 }  // namespace fg
 
 using namespace fg;
@@ -43,6 +49,22 @@ using namespace fg;
 static_assert(sizeof(SubRec) == sizeof(flacgpu_subframe_record), "record layout");
 static_assert(sizeof(FrameRec) == sizeof(flacgpu_frame_record), "record layout");
 static_assert(sizeof(Md5State) == sizeof(flacgpu_md5_state), "md5 state layout");
+static_assert(sizeof(dec::Result) == sizeof(flacgpu_decode_result), "decode result layout");
+
+// Decode scratch of a context (allocated by its first decode call, max_frames frames): the
+// subframe descriptors k_dec_parse leaves for k_dec_recon, the parsed block sizes and their scan,
+// and the expected frame table of a verify.
+struct DecScratch {
+    dec::DecSub *subs = nullptr;
+    uint32_t *blocks = nullptr, *body = nullptr, *exp_n = nullptr, *ctl = nullptr;  // ctl: [0] ticket
+    uint64_t *samp_off = nullptr, *total = nullptr, *exp_off = nullptr, *exp_number = nullptr;
+    // staging of the host-buffer decode (flacgpu_decode_frames), grow-only
+    uint8_t *d_frames = nullptr, *d_pcm = nullptr;
+    uint64_t frames_cap = 0, pcm_cap = 0;
+    uint64_t *d_foff = nullptr;
+    uint32_t *d_fbytes = nullptr, *d_bad = nullptr;
+    dec::Result *d_results = nullptr;
+};
 
 namespace {
 
@@ -178,6 +200,7 @@ struct flacgpu_ctx {
     uint8_t md5_buf[64] = {};
     uint32_t md5_fill = 0;
     uint64_t md5_len = 0;
+    DecScratch *dec = nullptr;  // frame decoder / verifier: allocated by the first decode call
 };
 
 // device MD5 engine: whole blocks move through one bounded device buffer
@@ -873,6 +896,13 @@ void flacgpu_close(flacgpu_ctx *c) {
     hipFree(c->d_status);
     hipFree(c->d_crc_join);
     hipFree(c->d_scan_part);
+    if (c->dec) {
+        DecScratch *d = c->dec;
+        void *bufs[] = {d->subs, d->blocks, d->body, d->exp_n, d->ctl, d->samp_off, d->total, d->exp_off, d->exp_number,
+                        d->d_frames, d->d_pcm, d->d_foff, d->d_fbytes, d->d_bad, d->d_results};
+        for (void *b : bufs) hipFree(b);
+        delete d;
+    }
     hipFree(c->d_err);
     hipFree(c->d_ctr);
     hipFree(c->d_cum);
@@ -1706,6 +1736,180 @@ int flacgpu_debug_stamps(flacgpu_ctx *c, uint64_t *out32, int reset) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpy(out32, c->d_stamps, 32 * 8, hipMemcpyDeviceToHost));
     if (reset) HIPCHK(hipMemset(c->d_stamps, 0, 32 * 8));
+    return FLACGPU_OK;
+}
+
+// ---- frame decoder / verifier (fg_dec.hpp, fg_dec.hip) -------------------------------------
+static int dec_scratch(flacgpu_ctx *c) {
+    if (c->dec) return FLACGPU_OK;
+    DecScratch *d = new (std::nothrow) DecScratch();
+    if (!d) return FLACGPU_ERR_OUT_OF_MEMORY;
+    c->dec = d;  // freed by flacgpu_close, whole or partial
+    const uint64_t n = c->max_frames;
+    HIPCHK(hipMalloc(&d->subs, n * c->C * sizeof(dec::DecSub)));
+    HIPCHK(hipMalloc(&d->blocks, n * 4u));
+    HIPCHK(hipMalloc(&d->body, n * 4u));
+    HIPCHK(hipMalloc(&d->exp_n, n * 4u));
+    HIPCHK(hipMalloc(&d->ctl, 64));
+    HIPCHK(hipMalloc(&d->samp_off, n * 8u));
+    HIPCHK(hipMalloc(&d->total, 8));
+    HIPCHK(hipMalloc(&d->exp_off, n * 8u));
+    HIPCHK(hipMalloc(&d->exp_number, n * 8u));
+    HIPCHK(hipMalloc(&d->d_bad, 4));
+    return FLACGPU_OK;
+}
+
+// parse, (scan,) reconstruct of n frames, queued on st
+static int dec_core(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff, const uint32_t *d_fbytes, uint32_t n,
+                    const uint64_t *d_pcm_off, uint8_t *d_out, uint64_t cap, const uint8_t *d_expect, bool verify,
+                    flacgpu_decode_result *d_results, uint32_t *d_bad, hipStream_t st) {
+    DecScratch *d = c->dec;
+    dec::Args a{};
+    a.frames = d_frames;
+    a.frame_off = d_foff;
+    a.frame_bytes = d_fbytes;
+    a.n_frames = n;
+    a.channels = c->C;
+    a.bits = c->bits;
+    a.bps = c->bits / 8u;
+    a.rate = c->cfg.sample_rate;
+    a.block = c->cfg.block_size;
+    a.subs = d->subs;
+    a.blocks = d->blocks;
+    a.body = d->body;
+    a.pcm_off = d_pcm_off;
+    a.samp_off = d->samp_off;
+    a.out = d_out;
+    a.cap = cap;
+    a.expect = d_expect;
+    a.exp_number = verify ? d->exp_number : nullptr;
+    a.exp_n = verify ? d->exp_n : nullptr;
+    a.results = (dec::Result *)d_results;
+    a.bad = d_bad ? d_bad : d->d_bad;
+    a.ticket = d->ctl;
+    {
+        Timed t(c, FLACGPU_K_DEC_PARSE, st);
+        HIPCHK(launch_dec_parse(a, st));
+    }
+    if (!d_pcm_off) {
+        // consecutive blocks of one stream: sample offsets from the scan of the parsed block sizes
+        const uint32_t nb = (n + 4095u) / 4096u;
+        if (nb > c->scan_part_cap) {
+            HIPCHK(hipStreamSynchronize(st));
+            hipFree(c->d_scan_part);
+            c->d_scan_part = nullptr;
+            c->scan_part_cap = 0;
+            HIPCHK(hipMalloc(&c->d_scan_part, (size_t)nb * 8u));
+            c->scan_part_cap = nb;
+        }
+        Timed t(c, FLACGPU_K_SCAN, st);
+        HIPCHK(launch_scan(d->blocks, d->samp_off, d->total, n, c->d_scan_part, st));
+    }
+    Timed t(c, FLACGPU_K_DEC_RECON, st);
+    HIPCHK(launch_dec_recon(a, st));
+    return FLACGPU_OK;
+}
+
+int flacgpu_decode_frames_device(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_frame_offsets,
+                                 const uint32_t *d_frame_bytes, uint64_t n_frames, const uint64_t *d_pcm_offsets,
+                                 uint8_t *d_pcm_out, uint64_t pcm_cap, const uint8_t *d_pcm_expect,
+                                 flacgpu_decode_result *d_results, uint32_t *d_bad_count, void *hip_stream) {
+    if (!c || !d_frames || !d_frame_offsets || !d_frame_bytes || !d_results || !d_bad_count || n_frames > c->max_frames)
+        return FLACGPU_ERR_INVALID_INPUT;
+    HIPCHK(hipSetDevice(c->device));
+    const int rc = dec_scratch(c);
+    if (rc) return rc;
+    hipStream_t st = pick_stream(c, hip_stream);
+    if (n_frames == 0) {
+        HIPCHK(hipMemsetAsync(d_bad_count, 0, 4, st));
+        return FLACGPU_OK;
+    }
+    return dec_core(c, d_frames, d_frame_offsets, d_frame_bytes, (uint32_t)n_frames, d_pcm_offsets, d_pcm_out, pcm_cap,
+                    d_pcm_expect, false, d_results, d_bad_count, st);
+}
+
+int flacgpu_verify_plan_device(flacgpu_ctx *c, const flacgpu_plan *p, const void *d_pcm, const uint8_t *d_out,
+                               const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                               flacgpu_decode_result *d_results, uint32_t *d_bad_count, void *hip_stream) {
+    if (!c || !p || p->ctx != c || !d_pcm || !d_out || !d_frame_offsets || !d_frame_bytes || !d_results || !d_bad_count ||
+        p->n_frames > c->max_frames)
+        return FLACGPU_ERR_INVALID_INPUT;
+    HIPCHK(hipSetDevice(c->device));
+    const int rc = dec_scratch(c);
+    if (rc) return rc;
+    hipStream_t st = pick_stream(c, hip_stream);
+    if (p->n_frames == 0) {
+        HIPCHK(hipMemsetAsync(d_bad_count, 0, 4, st));
+        return FLACGPU_OK;
+    }
+    DecScratch *d = c->dec;
+    // the plan's frame table (full jobs, then tail jobs) by output slot
+    HIPCHK(launch_dec_expect(p->d_jobs, p->n_frames, d->exp_off, d->exp_number, d->exp_n, st));
+    return dec_core(c, d_out, d_frame_offsets, d_frame_bytes, (uint32_t)p->n_frames, d->exp_off, nullptr, 0,
+                    (const uint8_t *)d_pcm, true, d_results, d_bad_count, st);
+}
+
+int flacgpu_decode_frames(flacgpu_ctx *c, const uint8_t *frames, const uint32_t *frame_bytes, uint64_t n_frames,
+                          uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, flacgpu_decode_result *results) {
+    if (!c || !n_samples || !results || (n_frames && (!frames || !frame_bytes)) || (pcm_cap && !pcm_out))
+        return FLACGPU_ERR_INVALID_INPUT;
+    *n_samples = 0;
+    if (n_frames == 0) return FLACGPU_OK;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = dec_scratch(c);
+    if (rc) return rc;
+    DecScratch *d = c->dec;
+    hipStream_t st = c->stream;
+    const uint64_t frame_pcm = (uint64_t)c->cfg.block_size * c->C * (c->bits / 8u);
+    if (!d->d_foff) {
+        HIPCHK(hipMalloc(&d->d_foff, (uint64_t)c->max_frames * 8u));
+        HIPCHK(hipMalloc(&d->d_fbytes, (uint64_t)c->max_frames * 4u));
+        HIPCHK(hipMalloc(&d->d_results, (uint64_t)c->max_frames * sizeof(dec::Result)));
+    }
+    std::vector<uint64_t> foff;
+    uint64_t src = 0, written = 0;
+    for (uint64_t f0 = 0; f0 < n_frames; f0 += c->max_frames) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(c->max_frames, n_frames - f0);
+        foff.assign(n, 0);
+        uint64_t bytes = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            foff[i] = bytes;
+            bytes += frame_bytes[f0 + i];
+        }
+        if (bytes + 16u > d->frames_cap) {
+            hipFree(d->d_frames);
+            d->d_frames = nullptr;
+            d->frames_cap = 0;
+            HIPCHK(hipMalloc(&d->d_frames, bytes + 16u));
+            d->frames_cap = bytes + 16u;
+        }
+        const uint64_t need = (uint64_t)n * frame_pcm;
+        if (need > d->pcm_cap) {
+            hipFree(d->d_pcm);
+            d->d_pcm = nullptr;
+            d->pcm_cap = 0;
+            HIPCHK(hipMalloc(&d->d_pcm, need));
+            d->pcm_cap = need;
+        }
+        HIPCHK(hipMemcpyAsync(d->d_frames, frames + src, bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d->d_foff, foff.data(), (uint64_t)n * 8u, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d->d_fbytes, frame_bytes + f0, (uint64_t)n * 4u, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemsetAsync(d->d_pcm, 0, need, st));
+        rc = dec_core(c, d->d_frames, d->d_foff, d->d_fbytes, n, nullptr, d->d_pcm, need, nullptr, false,
+                      (flacgpu_decode_result *)d->d_results, nullptr, st);
+        if (rc) return rc;
+        uint64_t total = 0;
+        HIPCHK(hipMemcpyAsync(results + f0, d->d_results, (uint64_t)n * sizeof(dec::Result), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&total, d->total, 8, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        const uint64_t out_bytes = total * c->C * (c->bits / 8u);
+        if (out_bytes > need) return FLACGPU_ERR_INTERNAL;
+        if (written + out_bytes > pcm_cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
+        if (out_bytes) HIPCHK(hipMemcpy(pcm_out + written, d->d_pcm, out_bytes, hipMemcpyDeviceToHost));
+        written += out_bytes;
+        *n_samples += total;
+        src += bytes;
+    }
     return FLACGPU_OK;
 }
 

@@ -1,0 +1,153 @@
+// fg_dec_api.cpp -- the host-only side of the decoder's C ABI: the frame index of a FLAC file or
+// of a bare run of frames (no GPU), and the whole-file decode built on it and on
+// flacgpu_decode_frames.  Plain C++ over include/flacgpu.h and the shared decode core.
+#include <cstring>
+#include <vector>
+
+#include "../../include/flacgpu.h"
+#include "fg_dec.hpp"
+#include "fg_md5_host.hpp"
+
+using namespace fg;
+
+namespace {
+
+uint64_t rd_be(const uint8_t *p, int n) {
+    uint64_t v = 0;
+    for (int i = 0; i < n; i++) v = (v << 8) | p[i];
+    return v;
+}
+
+// a frame header with a good CRC-8 starts at p (RFC 9639 9.1); its length in *hdr_bytes
+bool header_at(const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate, uint32_t *hdr_bytes) {
+    if (len < 6 || p[0] != 0xFF || (p[1] & 0xFE) != 0xF8) return false;
+    dec::BitReader b = dec::br_make(p, (uint32_t)(len > 32 ? 32 : len));
+    dec::FrameHdr h;
+    const uint32_t st = dec::parse_header(b, stream_bits, stream_rate, 0, 0, 65535u, h);
+    *hdr_bytes = h.hdr_bytes;
+    return st == dec::ST_OK;
+}
+
+// Frame sizes of the frames in [p, p + len): a frame ends where the next position with a sync
+// code and a CRC-8-clean header follows a good CRC-16 over everything since the frame's start.
+int index_frames(const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate, std::vector<uint32_t> &sizes) {
+    size_t s = 0;
+    while (s < len) {
+        uint32_t hdr = 0;
+        if (!header_at(p + s, len - s, stream_bits, stream_rate, &hdr)) return FLACGPU_ERR_INVALID_INPUT;
+        // crc = CRC-16 of [s, upto); a candidate end e needs it over [s, e - 2)
+        uint32_t crc = 0;
+        size_t upto = s, e = s + hdr + 3u;  // at least one subframe byte and the CRC-16
+        bool found = false;
+        for (; e <= len; e++) {
+            while (upto < e - 2u) crc = crc_byte_v(crc, p[upto++]);
+            if (crc != (((uint32_t)p[e - 2] << 8) | p[e - 1])) continue;
+            uint32_t nh = 0;
+            if (e == len || header_at(p + e, len - e, stream_bits, stream_rate, &nh)) {
+                found = true;
+                break;
+            }
+        }
+        if (!found || e - s > 0xFFFFFFFFull) return FLACGPU_ERR_INVALID_INPUT;
+        sizes.push_back((uint32_t)(e - s));
+        s = e;
+    }
+    return FLACGPU_OK;
+}
+
+// "fLaC" and the metadata blocks (RFC 9639 8): STREAMINFO (8.2) to *si, the others skipped by length
+int parse_metadata(const uint8_t *p, size_t len, flacgpu_streaminfo *si, size_t *first) {
+    if (len < 4 || std::memcmp(p, "fLaC", 4) != 0) return FLACGPU_ERR_INVALID_INPUT;
+    size_t pos = 4;
+    bool have_si = false;
+    for (;;) {
+        if (pos + 4 > len) return FLACGPU_ERR_INVALID_INPUT;
+        const bool last = (p[pos] & 0x80) != 0;
+        const uint32_t type = p[pos] & 0x7F;
+        const size_t n = (size_t)rd_be(p + pos + 1, 3);
+        pos += 4;
+        if (n > len - pos) return FLACGPU_ERR_INVALID_INPUT;
+        if (type == 0) {
+            if (n != 34) return FLACGPU_ERR_INVALID_INPUT;
+            const uint8_t *q = p + pos;
+            std::memset(si, 0, sizeof(*si));
+            si->min_block_size = (uint16_t)rd_be(q, 2);
+            si->max_block_size = (uint16_t)rd_be(q + 2, 2);
+            si->min_frame_size = (uint32_t)rd_be(q + 4, 3);
+            si->max_frame_size = (uint32_t)rd_be(q + 7, 3);
+            const uint64_t v = rd_be(q + 10, 8);  // rate 20, channels-1 3, bits-1 5, samples 36
+            si->sample_rate = (uint32_t)(v >> 44);
+            si->channels = (uint8_t)(((v >> 41) & 7u) + 1u);
+            si->bit_depth = (uint8_t)(((v >> 36) & 31u) + 1u);
+            si->interchannel_samples = v & ((1ull << 36) - 1u);
+            std::memcpy(si->md5, q + 18, 16);
+            have_si = true;
+        }
+        pos += n;
+        if (last) break;
+    }
+    if (!have_si) return FLACGPU_ERR_INVALID_INPUT;
+    *first = pos;
+    return FLACGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flacgpu_flac_index(const void *flac, size_t len, flacgpu_streaminfo *streaminfo, size_t *first_frame_offset,
+                       uint32_t *frame_bytes, size_t cap, size_t *n_frames) {
+    if (!flac || !n_frames || (cap && !frame_bytes)) return FLACGPU_ERR_INVALID_INPUT;
+    const uint8_t *p = (const uint8_t *)flac;
+    *n_frames = 0;
+    size_t first = 0;
+    uint32_t bits = 16, rate = 0;
+    if (streaminfo) {  // a file; NULL: a bare run of frames
+        const int rc = parse_metadata(p, len, streaminfo, &first);
+        if (rc) return rc;
+        bits = streaminfo->bit_depth;
+        rate = streaminfo->sample_rate;
+    }
+    if (first_frame_offset) *first_frame_offset = first;
+    std::vector<uint32_t> sizes;
+    const int rc = index_frames(p + first, len - first, bits, rate, sizes);
+    if (rc) return rc;
+    *n_frames = sizes.size();
+    if (sizes.size() > cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
+    if (!sizes.empty()) std::memcpy(frame_bytes, sizes.data(), sizes.size() * sizeof(uint32_t));
+    return FLACGPU_OK;
+}
+
+int flacgpu_decode_file(flacgpu_ctx *ctx, const void *flac, size_t len, uint8_t *pcm_out, size_t pcm_cap,
+                        uint64_t *n_samples, int *md5_ok) {
+    if (!ctx || !flac || !n_samples || (pcm_cap && !pcm_out)) return FLACGPU_ERR_INVALID_INPUT;
+    *n_samples = 0;
+    if (md5_ok) *md5_ok = 0;
+    const uint8_t *p = (const uint8_t *)flac;
+    flacgpu_streaminfo si;
+    size_t first = 0;
+    int rc = parse_metadata(p, len, &si, &first);
+    if (rc) return rc;
+    flacgpu_config cfg;
+    rc = flacgpu_get_config(ctx, &cfg);
+    if (rc) return rc;
+    if (si.channels != cfg.channels || si.bit_depth != cfg.bits_per_sample) return FLACGPU_ERR_INVALID_INPUT;
+    std::vector<uint32_t> sizes;
+    rc = index_frames(p + first, len - first, si.bit_depth, si.sample_rate, sizes);
+    if (rc) return rc;
+    std::vector<flacgpu_decode_result> res(sizes.size() ? sizes.size() : 1);
+    rc = flacgpu_decode_frames(ctx, p + first, sizes.data(), sizes.size(), pcm_out, pcm_cap, n_samples, res.data());
+    if (rc) return rc;
+    for (size_t i = 0; i < sizes.size(); i++)
+        if (res[i].status) return FLACGPU_ERR_INVALID_INPUT;  // a damaged frame: not a decodable file
+    HostMd5 h;
+    h.update(pcm_out, (size_t)(*n_samples * cfg.channels * (cfg.bits_per_sample / 8u)));
+    uint8_t digest[16];
+    h.final(digest);
+    if (md5_ok)
+        *md5_ok = std::memcmp(digest, si.md5, 16) == 0 &&
+                  (si.interchannel_samples == 0 || si.interchannel_samples == *n_samples);
+    return FLACGPU_OK;
+}
+
+}  // extern "C"

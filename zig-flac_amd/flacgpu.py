@@ -350,6 +350,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_gather_frames_device": (I32, [P, P, U64, P, P, U64, P, U64, P, U64, ctypes.POINTER(U64),
                                                ctypes.POINTER(U64), P]),
         "flacgpu_encode_frames_sharded": (I32, [P, P, P, U32, U64, U64, P, SZ, ctypes.POINTER(SZ), P]),
+        "flacgpu_decode_frames_device": (I32, [P, P, P, P, U64, P, P, U64, P, P, P, P]),
+        "flacgpu_verify_plan_device": (I32, [P, P, P, P, P, P, P, P, P]),
+        "flacgpu_decode_frames": (I32, [P, P, P, U64, P, SZ, ctypes.POINTER(U64), P]),
+        "flacgpu_flac_index": (I32, [P, SZ, P, ctypes.POINTER(SZ), P, SZ, ctypes.POINTER(SZ)]),
+        "flacgpu_decode_file": (I32, [P, P, SZ, P, SZ, ctypes.POINTER(U64), ctypes.POINTER(I32)]),
     }
     # an older build named by FLACGPU_LIB (same-box A/B runs, tools/ab.sh) may predate later entry
     # points: those stay unbound there; the in-tree library must export every one
@@ -383,6 +388,8 @@ def exported_symbols() -> list:
         "flacgpu_wav_to_flac", "flacgpu_open_multi", "flacgpu_close_multi", "flacgpu_multi_encode_frames",
         "flacgpu_comm_unique_id", "flacgpu_comm_init", "flacgpu_comm_destroy", "flacgpu_comm_rank",
         "flacgpu_comm_size", "flacgpu_gather_frames_device", "flacgpu_encode_frames_sharded",
+        "flacgpu_decode_frames_device", "flacgpu_verify_plan_device", "flacgpu_decode_frames", "flacgpu_flac_index",
+        "flacgpu_decode_file",
     ]
 
 
@@ -462,7 +469,76 @@ class Plan:
             pass
 
 
-class Encoder:
+# per-frame decode status (FLACGPU_DEC_*): 1..7 are minus the CPU verifier decoder's codes
+DEC_OK, DEC_SYNC, DEC_HEADER, DEC_CRC8, DEC_SUBFRAME, DEC_CRC16, DEC_TRUNCATED, DEC_RANGE, DEC_MISMATCH = range(9)
+K_DEC_PARSE, K_DEC_RECON = 5, 6  # FLACGPU_K_DEC_PARSE / FLACGPU_K_DEC_RECON (kernel_time ids)
+
+
+class DecodeResult(ctypes.Structure):
+    """flacgpu_decode_result: one frame's status and header fields (32 bytes)."""
+    _fields_ = [("status", ctypes.c_uint32), ("block_size", ctypes.c_uint32), ("number", ctypes.c_uint64),
+                ("sample_rate", ctypes.c_uint32), ("first_bad", ctypes.c_uint32), ("channel_assign", ctypes.c_uint8),
+                ("bits", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 6)]
+
+
+def flac_index(buf: bytes, raw_frames: bool = False):
+    """flacgpu_flac_index (host only): (StreamInfo or None, first frame offset, [frame sizes]) of a
+    FLAC file in memory; raw_frames: `buf` is a bare run of frames (no "fLaC", no metadata)."""
+    L = load_library()
+    si = None if raw_frames else StreamInfo()
+    first, n = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    cap = len(buf) // 8 + 1  # a frame is at least 9 bytes
+    sizes = (ctypes.c_uint32 * cap)()
+    _check(L.flacgpu_flac_index(bytes(buf), len(buf), ctypes.byref(si) if si is not None else None, ctypes.byref(first),
+                                sizes, cap, ctypes.byref(n)), "flac_index")
+    return si, first.value, list(sizes)[: n.value]
+
+
+class _DecodeOps:
+    """The decode / verify entry points of a context (Encoder and Decoder share them)."""
+
+    def decode_frames_device(self, d_frames: int, d_frame_offsets: int, d_frame_bytes: int, n_frames: int,
+                             d_results: int, d_bad_count: int, d_pcm_offsets: Optional[int] = None,
+                             d_pcm_out: Optional[int] = None, pcm_cap: int = 0, d_pcm_expect: Optional[int] = None,
+                             stream: Optional[int] = None) -> None:
+        """flacgpu_decode_frames_device: device addresses in, nothing synchronised."""
+        _check(self.lib.flacgpu_decode_frames_device(self.ctx, d_frames, d_frame_offsets, d_frame_bytes, n_frames,
+                                                     d_pcm_offsets or None, d_pcm_out or None, pcm_cap,
+                                                     d_pcm_expect or None, d_results, d_bad_count, _stream(stream)),
+               "decode_frames_device")
+
+    def decode_frames(self, frames: bytes, sizes: Sequence[int]):
+        """flacgpu_decode_frames: concatenated frames of one stream -> (PCM bytes, [DecodeResult])."""
+        n = len(sizes)
+        per = self.channels * self.bytes_per_sample
+        cap = max(n * self.block_size * per, 1)
+        out = ctypes.create_string_buffer(cap)
+        fb = (ctypes.c_uint32 * max(n, 1))(*sizes)
+        res = (DecodeResult * max(n, 1))()
+        ns = ctypes.c_uint64(0)
+        src = ctypes.create_string_buffer(bytes(frames), len(frames)) if frames else None
+        _check(self.lib.flacgpu_decode_frames(self.ctx, src, fb, n, out, cap, ctypes.byref(ns), res), "decode_frames")
+        return out.raw[: ns.value * per], list(res)[:n]
+
+    def decode_file(self, flac: bytes):
+        """flacgpu_decode_file: a whole FLAC file -> (PCM bytes, md5_ok)."""
+        si, _, sizes = flac_index(flac)
+        per = self.channels * self.bytes_per_sample
+        cap = max(len(sizes) * self.block_size * per, 1)
+        out = ctypes.create_string_buffer(cap)
+        ns, ok = ctypes.c_uint64(0), ctypes.c_int(0)
+        _check(self.lib.flacgpu_decode_file(self.ctx, bytes(flac), len(flac), out, cap, ctypes.byref(ns),
+                                            ctypes.byref(ok)), "decode_file")
+        return out.raw[: ns.value * per], bool(ok.value)
+
+    def verify_plan_device(self, plan: "Plan", d_pcm: int, d_out: int, d_frame_offsets: int, d_frame_bytes: int,
+                           d_results: int, d_bad_count: int, stream: Optional[int] = None) -> None:
+        """flacgpu_verify_plan_device: decode the plan's encoded frames and compare them with d_pcm."""
+        _check(self.lib.flacgpu_verify_plan_device(self.ctx, plan.handle, d_pcm, d_out, d_frame_offsets, d_frame_bytes,
+                                                   d_results, d_bad_count, _stream(stream)), "verify_plan_device")
+
+
+class Encoder(_DecodeOps):
     """GPU block encoder context == Encoder.init / deinit (encoder.zig:44-164)."""
 
     def __init__(self, channels: int, bits: int, sample_rate: int, device: int = 0, max_frames: int = 32768,
@@ -685,6 +761,15 @@ class Encoder:
         arr = (FrameRecord * max(n.value, 1))()
         _check(self.lib.flacgpu_get_records(self.ctx, arr, n.value, ctypes.byref(n)), "get_records")
         return list(arr)[: n.value]
+
+
+class Decoder(Encoder):
+    """A context used to decode: frames of `channels` x `bits` with blocks of at most block_size
+    samples.  There is no CPU fallback: without a device the constructor raises FlacGpuError(-5)."""
+
+    def __init__(self, channels: int, bits: int, sample_rate: int, device: int = 0, max_frames: int = 4096,
+                 block_size: int = 4096):
+        super().__init__(channels, bits, sample_rate, device=device, max_frames=max_frames, block_size=block_size)
 
 
 class MultiEncoder:
