@@ -465,9 +465,28 @@ int flacgpu_decode_frames(flacgpu_ctx *ctx, const uint8_t *frames, const uint32_
  * FLACGPU_ERR_OUTPUT_TOO_SMALL), *first_frame_offset (may be NULL) the first frame's offset. */
 int flacgpu_flac_index(const void *flac, size_t len, flacgpu_streaminfo *streaminfo, size_t *first_frame_offset,
                        uint32_t *frame_bytes, size_t cap, size_t *n_frames);
-/* Index, decode (flacgpu_decode_frames) and MD5 (the host engine) of a whole file whose channel
- * count and bit depth are the context's; *md5_ok (may be NULL) = the PCM's MD5 and sample count
- * are STREAMINFO's.  A damaged frame makes the call fail with FLACGPU_ERR_INVALID_INPUT. */
+/* The same index of a bare run of frames resident in device memory (any alignment, len <= 2^32 - 1),
+ * found on the device: d_frame_offsets[] (relative to d_data) and d_frame_bytes[] (capacity cap
+ * each) are what flacgpu_decode_frames_device takes.  *d_result (device memory): INDEX_OK with the
+ * frame count and the same sizes flacgpu_flac_index(..., streaminfo = NULL) finds on these bytes;
+ * INDEX_INVALID (0 frames) where that call returns FLACGPU_ERR_INVALID_INPUT; INDEX_TOO_SMALL
+ * with the true count where it exceeds cap.  Only an OK result writes the two arrays, and only
+ * their first n_frames entries.  stream_bits / stream_rate stand for the "from STREAMINFO"
+ * header codes (16 and 0 in flacgpu_flac_index without a streaminfo).  Asynchronous on
+ * hip_stream, no host synchronisation (but when the context's index scratch, sized from len and
+ * cap, has to grow); independent of max_frames_per_call. */
+enum { FLACGPU_INDEX_OK = 0, FLACGPU_INDEX_INVALID = 1, FLACGPU_INDEX_TOO_SMALL = 2 };
+typedef struct { uint64_t n_frames; uint32_t status; uint32_t reserved; } flacgpu_index_result; /* device memory */
+int flacgpu_flac_index_device(flacgpu_ctx *ctx, const uint8_t *d_data, uint64_t len,
+                              uint32_t stream_bits, uint32_t stream_rate,
+                              uint64_t *d_frame_offsets, uint32_t *d_frame_bytes, uint64_t cap,
+                              flacgpu_index_result *d_result, void *hip_stream);
+/* Decode and MD5 (the host engine) of a whole file whose channel count and bit depth are the
+ * context's: the frames are uploaded once, indexed on the device (flacgpu_flac_index_device) and
+ * decoded from there in chunks of max_frames_per_call, each chunk's PCM hashed on the host while
+ * the next decodes; a stream the device index refuses goes through flacgpu_flac_index and
+ * flacgpu_decode_frames.  *md5_ok (may be NULL) = the PCM's MD5 and sample count are
+ * STREAMINFO's.  A damaged frame makes the call fail with FLACGPU_ERR_INVALID_INPUT. */
 int flacgpu_decode_file(flacgpu_ctx *ctx, const void *flac, size_t len, uint8_t *pcm_out, size_t pcm_cap,
                         uint64_t *n_samples, int *md5_ok);
 
@@ -476,7 +495,8 @@ int flacgpu_decode_file(flacgpu_ctx *ctx, const void *flac, size_t len, uint8_t 
  * short frames), frame-size scan, frame packing (all frames), stream MD5. */
 enum { FLACGPU_K_ANALYZE = 0, FLACGPU_K_ANALYZE_TAIL = 1, FLACGPU_K_SCAN = 2, FLACGPU_K_PACK = 3, FLACGPU_K_MD5 = 4,
        FLACGPU_K_DEC_PARSE = 5, FLACGPU_K_DEC_RECON = 6, /* the decoder's parse and reconstruct kernels */
-       FLACGPU_K_COUNT = 7 };
+       FLACGPU_K_INDEX = 7,                              /* the device frame index: all its stages as one launch */
+       FLACGPU_K_COUNT = 8 };
 /* When enabled, every launch of kernel k is bracketed by HIP events on the
  * stream it runs on; flacgpu_kernel_time returns the number of timed launches
  * and their summed device milliseconds since the last reset. */

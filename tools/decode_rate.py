@@ -8,7 +8,13 @@ flacgpu_decode_frames_device in verify mode (compare with the PCM) and in output
 PCM): HIP events around the call, warm-up, repeats, the median; the parse and reconstruct kernel
 times from flacgpu_kernel_time in a pass of their own.  Writes one JSON document.
 
-    python tools/decode_rate.py --out profiles/dec_rate.json
+The index leg (--index-out) takes the C2 batch as a FLAC file: the host frame index
+flacgpu_flac_index over its frames (wall clock, best of 3), the device index
+flacgpu_flac_index_device over the same bytes in HBM (HIP events, warm-up, the median), the device
+decode of the frames it found (the same way), and flacgpu_decode_file end to end (wall clock).
+
+    python tools/decode_rate.py --out profiles/dec_rate.json --index-out profiles/index_rate.json
+    python tools/decode_rate.py --legs index --index-out profiles/index_rate.json
 """
 import argparse
 import ctypes
@@ -114,6 +120,102 @@ def gpu_rate(name: str, frames: int, warmup: int, repeats: int) -> dict:
     return res
 
 
+def index_rate(frames: int, warmup: int, repeats: int) -> dict:
+    import numpy as np
+    import torch
+
+    import flacgpu
+    import synth
+
+    ch, bits, rate, _ = PRESETS["c2"]
+    dev = torch.device("cuda", 0)
+    n = frames * 4096
+    unit = synth.synth_pcm(64 * 4096, ch, bits, rate)
+    pcm = (unit * ((frames + 63) // 64))[: n * ch * (bits // 8)]
+    L = flacgpu.load_library()
+    with flacgpu.Encoder(ch, bits, rate, device=0, max_frames=frames) as enc:
+        flac = enc.encode_file(pcm)
+        # host index of the frames alone (the bytes the device index gets), best of 3
+        si = flacgpu.StreamInfo()
+        first, nf = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        cap = len(flac) // 8 + 1
+        sizes = (ctypes.c_uint32 * cap)()
+        assert L.flacgpu_flac_index(flac, len(flac), ctypes.byref(si), ctypes.byref(first), sizes, cap, ctypes.byref(nf)) == 0
+        assert nf.value == frames
+        body = flac[first.value:]
+        host_s = None
+        for _ in range(3):
+            t = time.perf_counter()
+            rc = L.flacgpu_flac_index(body, len(body), None, None, sizes, cap, ctypes.byref(nf))
+            dt = time.perf_counter() - t
+            assert rc == 0 and nf.value == frames
+            host_s = dt if host_s is None else min(host_s, dt)
+        want = np.frombuffer(sizes, dtype=np.uint32)[:frames].copy()
+        # the same bytes in HBM, as they sit in the file (the first frame's offset is odd)
+        d_file = torch.from_numpy(np.frombuffer(flac, dtype=np.uint8).copy()).to(dev)
+        d_off = torch.zeros(cap, dtype=torch.int64, device=dev)
+        d_fb = torch.zeros(cap, dtype=torch.int32, device=dev)
+        d_ir = torch.zeros(16, dtype=torch.uint8, device=dev)
+        d_res = torch.zeros(32 * frames, dtype=torch.uint8, device=dev)
+        d_bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        d_dec = torch.zeros(len(pcm), dtype=torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        d_frames = d_file.data_ptr() + first.value
+
+        def index():
+            enc.flac_index_device(d_frames, len(body), d_off.data_ptr(), d_fb.data_ptr(), cap, d_ir.data_ptr(),
+                                  stream_bits=bits, stream_rate=rate, stream=st)
+
+        def decode():
+            enc.decode_frames_device(d_frames, d_off.data_ptr(), d_fb.data_ptr(), frames, d_res.data_ptr(),
+                                     d_bad.data_ptr(), d_pcm_out=d_dec.data_ptr(), pcm_cap=len(pcm), stream=st)
+
+        def timed(fn):
+            for _ in range(warmup):
+                fn()
+            enc.sync_check(st)
+            ms = []
+            for _ in range(repeats):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                ms.append(a.elapsed_time(b))
+            return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
+
+        res = {"frames": frames, "channels": ch, "bits": bits, "file_bytes": len(flac), "frame_bytes": len(body),
+               "first_frame_offset": first.value,
+               "host_index": {"seconds_best_of_3": host_s, "mb_per_s": len(body) / host_s / 1e6}}
+        res["device_index"] = timed(index)
+        ir = flacgpu.IndexResult.from_buffer_copy(d_ir.cpu().numpy().tobytes())
+        assert ir.status == 0 and ir.n_frames == frames
+        assert (d_fb[:frames].cpu().numpy().view(np.uint32) == want).all(), "device index differs from the host index"
+        res["device_index"]["gb_per_s"] = len(body) / res["device_index"]["ms_median"] / 1e6
+        res["device_index"]["x_host_index"] = host_s * 1e3 / res["device_index"]["ms_median"]
+        res["device_decode"] = timed(decode)
+        assert int(d_bad.item()) == 0 and d_dec.cpu().numpy().tobytes() == pcm
+        res["device_index"]["of_device_decode"] = res["device_index"]["ms_median"] / res["device_decode"]["ms_median"]
+        # the whole file, host buffers in and out (the first call allocates: not timed)
+        out = ctypes.create_string_buffer(len(pcm))
+        ns, ok = ctypes.c_uint64(0), ctypes.c_int(0)
+        wall = []
+        for i in range(4):
+            t = time.perf_counter()
+            rc = L.flacgpu_decode_file(enc.ctx, flac, len(flac), out, len(pcm), ctypes.byref(ns), ctypes.byref(ok))
+            wall.append(time.perf_counter() - t)
+            assert rc == 0 and ok.value == 1 and ns.value == n
+        assert out.raw == pcm
+        res["decode_file"] = {"seconds_first_call": wall[0], "seconds_best_of_3": min(wall[1:]),
+                              "msamples_per_s": n / min(wall[1:]) / 1e6}
+        # what of it is the MD5 chain of the PCM on one host core
+        import hashlib
+        t = time.perf_counter()
+        hashlib.md5(pcm).digest()
+        res["decode_file"]["hashlib_md5_seconds"] = time.perf_counter() - t
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dec_rate.json"))
@@ -121,7 +223,17 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--legs", choices=("all", "decode", "index"), default="all")
+    ap.add_argument("--index-out", default=os.path.join(ROOT, "profiles", "index_rate.json"))
     a = ap.parse_args()
+    if a.legs != "decode":
+        idx = {"c2": index_rate(a.frames, a.warmup, a.repeats)}
+        print(json.dumps({"index": idx}), flush=True)
+        with open(a.index_out, "w") as f:
+            json.dump(idx, f, indent=1)
+            f.write("\n")
+        if a.legs == "index":
+            return
     doc = {"cpu_oracle_fast_c2": cpu_rate(a.cpu_frames)}
     print(json.dumps({"cpu": doc["cpu_oracle_fast_c2"]}), flush=True)
     for name in ("c2", "c5"):

@@ -20,6 +20,7 @@
 #include "../../include/flacgpu.h"
 #include "fg_common.hpp"
 #include "fg_dec.hpp"
+#include "fg_index.hpp"
 #include "fg_internal.hpp"
 #include "fg_layout.hpp"
 #include "fg_md5_host.hpp"
@@ -42,6 +43,10 @@ hipError_t launch_dec_parse(const dec::Args &a, hipStream_t st);
 hipError_t launch_dec_recon(const dec::Args &a, hipStream_t st);
 hipError_t launch_dec_expect(const FrameJob *jobs, uint64_t n, uint64_t *pcm_off, uint64_t *number, uint32_t *ns,
                              hipStream_t st);
+// fg_index.hip
+hipError_t launch_index(const idx::IdxArgs &g, hipStream_t st);
+int decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate,
+                           uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, uint8_t digest[16]);
 }  // namespace fg
 
 using namespace fg;
@@ -50,6 +55,9 @@ static_assert(sizeof(SubRec) == sizeof(flacgpu_subframe_record), "record layout"
 static_assert(sizeof(FrameRec) == sizeof(flacgpu_frame_record), "record layout");
 static_assert(sizeof(Md5State) == sizeof(flacgpu_md5_state), "md5 state layout");
 static_assert(sizeof(dec::Result) == sizeof(flacgpu_decode_result), "decode result layout");
+static_assert(sizeof(idx::IndexResult) == sizeof(flacgpu_index_result), "index result layout");
+static_assert(FLACGPU_INDEX_INVALID == (int)idx::IDX_INVALID && FLACGPU_INDEX_TOO_SMALL == (int)idx::IDX_TOO_SMALL,
+              "index status codes");
 
 // Decode scratch of a context (allocated by its first decode call, max_frames frames): the
 // subframe descriptors k_dec_parse leaves for k_dec_recon, the parsed block sizes and their scan,
@@ -64,6 +72,18 @@ struct DecScratch {
     uint64_t *d_foff = nullptr;
     uint32_t *d_fbytes = nullptr, *d_bad = nullptr;
     dec::Result *d_results = nullptr;
+};
+
+// Index scratch of a context (flacgpu_flac_index_device), grow-only, sized from the call's len and
+// cap: one allocation carved into the arrays of idx::IdxArgs; and the frame table and result of
+// the whole-file decode, which indexes the file it uploaded.
+struct IdxScratch {
+    uint8_t *buf = nullptr;
+    uint64_t cap = 0;
+    uint64_t *f_off = nullptr;
+    uint32_t *f_bytes = nullptr;
+    uint64_t f_cap = 0;
+    idx::IndexResult *d_res = nullptr;
 };
 
 namespace {
@@ -201,6 +221,7 @@ struct flacgpu_ctx {
     uint32_t md5_fill = 0;
     uint64_t md5_len = 0;
     DecScratch *dec = nullptr;  // frame decoder / verifier: allocated by the first decode call
+    IdxScratch *idx = nullptr;  // device frame index: allocated by the first index call
 };
 
 // device MD5 engine: whole blocks move through one bounded device buffer
@@ -902,6 +923,13 @@ void flacgpu_close(flacgpu_ctx *c) {
                         d->d_frames, d->d_pcm, d->d_foff, d->d_fbytes, d->d_bad, d->d_results};
         for (void *b : bufs) hipFree(b);
         delete d;
+    }
+    if (c->idx) {
+        hipFree(c->idx->buf);
+        hipFree(c->idx->f_off);
+        hipFree(c->idx->f_bytes);
+        hipFree(c->idx->d_res);
+        delete c->idx;
     }
     hipFree(c->d_err);
     hipFree(c->d_ctr);
@@ -1849,6 +1877,70 @@ int flacgpu_verify_plan_device(flacgpu_ctx *c, const flacgpu_plan *p, const void
                     (const uint8_t *)d_pcm, true, d_results, d_bad_count, st);
 }
 
+// ---- device frame index (fg_index.hpp, fg_index.hip) ----------------------------------------
+static IdxScratch *idx_scratch(flacgpu_ctx *c) {
+    if (!c->idx) c->idx = new (std::nothrow) IdxScratch();  // freed by flacgpu_close
+    return c->idx;
+}
+
+// the eight stages over [d_data, d_data + len), len > 0, queued on st
+static int index_core(flacgpu_ctx *c, const uint8_t *d_data, uint64_t len, uint32_t stream_bits, uint32_t stream_rate,
+                      uint64_t *d_off, uint32_t *d_bytes, uint64_t cap, idx::IndexResult *d_res, hipStream_t st) {
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
+    idx::IdxArgs g{};
+    g.data = d_data;
+    g.len = len;
+    g.lead = (uint32_t)((uintptr_t)d_data & 15u);
+    g.bits = stream_bits;
+    g.rate = stream_rate;
+    g.n_chunks = (g.lead + len + idx::kIdxChunk - 1u) / idx::kIdxChunk;
+    g.n_groups = (uint32_t)((g.n_chunks + idx::kIdxGroup - 1u) / idx::kIdxGroup);
+    g.spos_cap = std::min<uint64_t>(cap, len / 8u + 1u);  // a frame is at least 9 bytes
+    g.offs = d_off;
+    g.bytes = d_bytes;
+    g.cap = cap;
+    g.res = d_res;
+    // the carve: 8-byte arrays first
+    const uint64_t nc = g.n_chunks, ng = g.n_groups;
+    const uint64_t o_cmask = 0, o_smask = o_cmask + nc * 8u, o_grp = o_smask + nc * 8u, o_gcnt = o_grp + ng * 4u,
+                   o_ctl = o_gcnt + ng * 4u, o_spos = o_ctl + 16u, o_terms = o_spos + g.spos_cap * 4u,
+                   need = o_terms + nc * 2u;
+    if (need > x->cap) {
+        HIPCHK(hipStreamSynchronize(st));  // an earlier index on this stream may still use the old one
+        hipFree(x->buf);
+        x->buf = nullptr;
+        x->cap = 0;
+        HIPCHK(hipMalloc(&x->buf, need));
+        x->cap = need;
+    }
+    g.cmask = (uint64_t *)(x->buf + o_cmask);
+    g.smask = (uint64_t *)(x->buf + o_smask);
+    g.grp = (uint32_t *)(x->buf + o_grp);
+    g.gcnt = (uint32_t *)(x->buf + o_gcnt);
+    g.ctl = (uint32_t *)(x->buf + o_ctl);
+    g.spos = (uint32_t *)(x->buf + o_spos);
+    g.terms = (uint16_t *)(x->buf + o_terms);
+    Timed t(c, FLACGPU_K_INDEX, st);
+    HIPCHK(launch_index(g, st));
+    return FLACGPU_OK;
+}
+
+int flacgpu_flac_index_device(flacgpu_ctx *c, const uint8_t *d_data, uint64_t len, uint32_t stream_bits,
+                              uint32_t stream_rate, uint64_t *d_frame_offsets, uint32_t *d_frame_bytes, uint64_t cap,
+                              flacgpu_index_result *d_result, void *hip_stream) {
+    if (!c || !d_data || !d_frame_offsets || !d_frame_bytes || !d_result || len > 0xFFFFFFFFull)
+        return FLACGPU_ERR_INVALID_INPUT;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = pick_stream(c, hip_stream);
+    if (len == 0) {  // no frames: OK, 0
+        HIPCHK(hipMemsetAsync(d_result, 0, sizeof(flacgpu_index_result), st));
+        return FLACGPU_OK;
+    }
+    return index_core(c, d_data, len, stream_bits, stream_rate, d_frame_offsets, d_frame_bytes, cap,
+                      (idx::IndexResult *)d_result, st);
+}
+
 int flacgpu_decode_frames(flacgpu_ctx *c, const uint8_t *frames, const uint32_t *frame_bytes, uint64_t n_frames,
                           uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, flacgpu_decode_result *results) {
     if (!c || !n_samples || !results || (n_frames && (!frames || !frame_bytes)) || (pcm_cap && !pcm_out))
@@ -1914,3 +2006,94 @@ int flacgpu_decode_frames(flacgpu_ctx *c, const uint8_t *frames, const uint32_t 
 }
 
 }  // extern "C"
+
+// The device side of flacgpu_decode_file (fg_dec_api.cpp): the frames [p, p + len) of a stream of
+// the context's layout uploaded once, indexed on the device, decoded from there in chunks of
+// max_frames; every chunk's PCM is downloaded to pcm_out and hashed while the next chunk decodes.
+// Returns 1 where the device index does not give a frame table (it refuses the stream, or its
+// scratch cannot be had): the caller then takes the host path, which names the error.
+int fg::decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate,
+                               uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, uint8_t digest[16]) {
+    if (len == 0 || len > 0xFFFFFFFFull) return 1;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = dec_scratch(c);
+    if (rc) return rc;
+    DecScratch *d = c->dec;
+    hipStream_t st = c->stream;
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return 1;
+    const uint64_t fcap = len / 8u + 1u;
+    if (fcap > x->f_cap) {
+        HIPCHK(hipStreamSynchronize(st));
+        hipFree(x->f_off);
+        hipFree(x->f_bytes);
+        x->f_off = nullptr;
+        x->f_bytes = nullptr;
+        x->f_cap = 0;
+        if (hipMalloc(&x->f_off, fcap * 8u) != hipSuccess || hipMalloc(&x->f_bytes, fcap * 4u) != hipSuccess) return 1;
+        x->f_cap = fcap;
+    }
+    if (!x->d_res && hipMalloc(&x->d_res, sizeof(idx::IndexResult)) != hipSuccess) return 1;
+    if (!d->d_foff) {
+        HIPCHK(hipMalloc(&d->d_foff, (uint64_t)c->max_frames * 8u));
+        HIPCHK(hipMalloc(&d->d_fbytes, (uint64_t)c->max_frames * 4u));
+        HIPCHK(hipMalloc(&d->d_results, (uint64_t)c->max_frames * sizeof(dec::Result)));
+    }
+    if (len + 16u > d->frames_cap) {
+        HIPCHK(hipStreamSynchronize(st));
+        hipFree(d->d_frames);
+        d->d_frames = nullptr;
+        d->frames_cap = 0;
+        if (hipMalloc(&d->d_frames, len + 16u) != hipSuccess) return 1;
+        d->frames_cap = len + 16u;
+    }
+    HIPCHK(hipMemcpyAsync(d->d_frames, p, len, hipMemcpyHostToDevice, st));
+    rc = index_core(c, d->d_frames, len, stream_bits, stream_rate, x->f_off, x->f_bytes, fcap, x->d_res, st);
+    if (rc == FLACGPU_ERR_OUT_OF_MEMORY) return 1;
+    if (rc) return rc;
+    idx::IndexResult ir{};
+    HIPCHK(hipMemcpyAsync(&ir, x->d_res, sizeof(ir), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ir.status != idx::IDX_OK || ir.n_frames > fcap) return 1;
+    const uint64_t n_frames = ir.n_frames;
+    const uint64_t per = (uint64_t)c->C * (c->bits / 8u), frame_pcm = (uint64_t)c->cfg.block_size * per;
+    std::vector<dec::Result> res(c->max_frames);
+    HostMd5 md5;
+    uint64_t written = 0, hashed = 0;
+    bool damaged = false;
+    for (uint64_t f0 = 0; f0 < n_frames; f0 += c->max_frames) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(c->max_frames, n_frames - f0);
+        const uint64_t need = (uint64_t)n * frame_pcm;
+        if (need > d->pcm_cap) {
+            hipFree(d->d_pcm);
+            d->d_pcm = nullptr;
+            d->pcm_cap = 0;
+            HIPCHK(hipMalloc(&d->d_pcm, need));
+            d->pcm_cap = need;
+        }
+        HIPCHK(hipMemsetAsync(d->d_pcm, 0, need, st));
+        rc = dec_core(c, d->d_frames, x->f_off + f0, x->f_bytes + f0, n, nullptr, d->d_pcm, need, nullptr, false,
+                      (flacgpu_decode_result *)d->d_results, nullptr, st);
+        if (rc) return rc;
+        uint64_t total = 0;
+        HIPCHK(hipMemcpyAsync(res.data(), d->d_results, (uint64_t)n * sizeof(dec::Result), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(&total, d->total, 8, hipMemcpyDeviceToHost, st));
+        // the chunk before this one, already in pcm_out, is hashed while this one decodes
+        md5.update(pcm_out + hashed, (size_t)(written - hashed));
+        hashed = written;
+        HIPCHK(hipStreamSynchronize(st));
+        const uint64_t out_bytes = total * per;
+        if (out_bytes > need) return FLACGPU_ERR_INTERNAL;
+        if (written + out_bytes > pcm_cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
+        if (out_bytes) HIPCHK(hipMemcpy(pcm_out + written, d->d_pcm, out_bytes, hipMemcpyDeviceToHost));
+        written += out_bytes;
+        *n_samples += total;
+        for (uint32_t i = 0; i < n; i++)
+            if (res[i].status) damaged = true;
+    }
+    if (damaged) return FLACGPU_ERR_INVALID_INPUT;  // a damaged frame: not a decodable file
+    md5.update(pcm_out + hashed, (size_t)(written - hashed));
+    md5.final(digest);
+    return FLACGPU_OK;
+}
+

@@ -1,14 +1,23 @@
 // fg_dec_api.cpp -- the host-only side of the decoder's C ABI: the frame index of a FLAC file or
-// of a bare run of frames (no GPU), and the whole-file decode built on it and on
-// flacgpu_decode_frames.  Plain C++ over include/flacgpu.h and the shared decode core.
+// of a bare run of frames (no GPU), and the whole-file decode: metadata here, the frames through
+// the device index and decode (fg_api.cpp decode_stream_resident), or, where the device index
+// refuses them, through the host index and flacgpu_decode_frames.  Plain C++ over
+// include/flacgpu.h and the shared decode core.
 #include <cstring>
 #include <vector>
 
 #include "../../include/flacgpu.h"
 #include "fg_dec.hpp"
+#include "fg_index.hpp"
 #include "fg_md5_host.hpp"
 
 using namespace fg;
+
+namespace fg {
+// fg_api.cpp: upload once, index and decode on the device; 1 = no frame table from the device index
+int decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate,
+                           uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, uint8_t digest[16]);
+}  // namespace fg
 
 namespace {
 
@@ -18,15 +27,7 @@ uint64_t rd_be(const uint8_t *p, int n) {
     return v;
 }
 
-// a frame header with a good CRC-8 starts at p (RFC 9639 9.1); its length in *hdr_bytes
-bool header_at(const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate, uint32_t *hdr_bytes) {
-    if (len < 6 || p[0] != 0xFF || (p[1] & 0xFE) != 0xF8) return false;
-    dec::BitReader b = dec::br_make(p, (uint32_t)(len > 32 ? 32 : len));
-    dec::FrameHdr h;
-    const uint32_t st = dec::parse_header(b, stream_bits, stream_rate, 0, 0, 65535u, h);
-    *hdr_bytes = h.hdr_bytes;
-    return st == dec::ST_OK;
-}
+using idx::header_at;  // the device index (fg_index.hip) tests its candidates with the same function
 
 // Frame sizes of the frames in [p, p + len): a frame ends where the next position with a sync
 // code and a CRC-8-clean header follows a good CRC-16 over everything since the frame's start.
@@ -132,18 +133,26 @@ int flacgpu_decode_file(flacgpu_ctx *ctx, const void *flac, size_t len, uint8_t 
     rc = flacgpu_get_config(ctx, &cfg);
     if (rc) return rc;
     if (si.channels != cfg.channels || si.bit_depth != cfg.bits_per_sample) return FLACGPU_ERR_INVALID_INPUT;
-    std::vector<uint32_t> sizes;
-    rc = index_frames(p + first, len - first, si.bit_depth, si.sample_rate, sizes);
-    if (rc) return rc;
-    std::vector<flacgpu_decode_result> res(sizes.size() ? sizes.size() : 1);
-    rc = flacgpu_decode_frames(ctx, p + first, sizes.data(), sizes.size(), pcm_out, pcm_cap, n_samples, res.data());
-    if (rc) return rc;
-    for (size_t i = 0; i < sizes.size(); i++)
-        if (res[i].status) return FLACGPU_ERR_INVALID_INPUT;  // a damaged frame: not a decodable file
-    HostMd5 h;
-    h.update(pcm_out, (size_t)(*n_samples * cfg.channels * (cfg.bits_per_sample / 8u)));
     uint8_t digest[16];
-    h.final(digest);
+    rc = decode_stream_resident(ctx, p + first, len - first, si.bit_depth, si.sample_rate, pcm_out, pcm_cap, n_samples, digest);
+    if (rc == 1) {
+        // the device index gave no frame table: the host index and the host-buffer decode, which
+        // refuse what they always refused
+        *n_samples = 0;
+        std::vector<uint32_t> sizes;
+        rc = index_frames(p + first, len - first, si.bit_depth, si.sample_rate, sizes);
+        if (rc) return rc;
+        std::vector<flacgpu_decode_result> res(sizes.size() ? sizes.size() : 1);
+        rc = flacgpu_decode_frames(ctx, p + first, sizes.data(), sizes.size(), pcm_out, pcm_cap, n_samples, res.data());
+        if (rc) return rc;
+        for (size_t i = 0; i < sizes.size(); i++)
+            if (res[i].status) return FLACGPU_ERR_INVALID_INPUT;  // a damaged frame: not a decodable file
+        HostMd5 h;
+        h.update(pcm_out, (size_t)(*n_samples * cfg.channels * (cfg.bits_per_sample / 8u)));
+        h.final(digest);
+    } else if (rc) {
+        return rc;
+    }
     if (md5_ok)
         *md5_ok = std::memcmp(digest, si.md5, 16) == 0 &&
                   (si.interchannel_samples == 0 || si.interchannel_samples == *n_samples);

@@ -355,6 +355,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_decode_frames": (I32, [P, P, P, U64, P, SZ, ctypes.POINTER(U64), P]),
         "flacgpu_flac_index": (I32, [P, SZ, P, ctypes.POINTER(SZ), P, SZ, ctypes.POINTER(SZ)]),
         "flacgpu_decode_file": (I32, [P, P, SZ, P, SZ, ctypes.POINTER(U64), ctypes.POINTER(I32)]),
+        "flacgpu_flac_index_device": (I32, [P, P, U64, U32, U32, P, P, U64, P, P]),
     }
     # an older build named by FLACGPU_LIB (same-box A/B runs, tools/ab.sh) may predate later entry
     # points: those stay unbound there; the in-tree library must export every one
@@ -389,7 +390,7 @@ def exported_symbols() -> list:
         "flacgpu_comm_unique_id", "flacgpu_comm_init", "flacgpu_comm_destroy", "flacgpu_comm_rank",
         "flacgpu_comm_size", "flacgpu_gather_frames_device", "flacgpu_encode_frames_sharded",
         "flacgpu_decode_frames_device", "flacgpu_verify_plan_device", "flacgpu_decode_frames", "flacgpu_flac_index",
-        "flacgpu_decode_file",
+        "flacgpu_decode_file", "flacgpu_flac_index_device",
     ]
 
 
@@ -472,6 +473,13 @@ class Plan:
 # per-frame decode status (FLACGPU_DEC_*): 1..7 are minus the CPU verifier decoder's codes
 DEC_OK, DEC_SYNC, DEC_HEADER, DEC_CRC8, DEC_SUBFRAME, DEC_CRC16, DEC_TRUNCATED, DEC_RANGE, DEC_MISMATCH = range(9)
 K_DEC_PARSE, K_DEC_RECON = 5, 6  # FLACGPU_K_DEC_PARSE / FLACGPU_K_DEC_RECON (kernel_time ids)
+K_INDEX = 7  # FLACGPU_K_INDEX: the device frame index, all its stages as one timed launch
+INDEX_OK, INDEX_INVALID, INDEX_TOO_SMALL = range(3)  # flacgpu_index_result.status
+
+
+class IndexResult(ctypes.Structure):
+    """flacgpu_index_result (device memory, 16 bytes)."""
+    _fields_ = [("n_frames", ctypes.c_uint64), ("status", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 class DecodeResult(ctypes.Structure):
@@ -506,6 +514,14 @@ class _DecodeOps:
                                                      d_pcm_offsets or None, d_pcm_out or None, pcm_cap,
                                                      d_pcm_expect or None, d_results, d_bad_count, _stream(stream)),
                "decode_frames_device")
+
+    def flac_index_device(self, d_data: int, length: int, d_frame_offsets: int, d_frame_bytes: int, cap: int,
+                          d_result: int, stream_bits: int = 16, stream_rate: int = 0,
+                          stream: Optional[int] = None) -> None:
+        """flacgpu_flac_index_device: the frame table of a device-resident bare run of frames; device
+        addresses in, *d_result (an IndexResult) in device memory, nothing synchronised."""
+        _check(self.lib.flacgpu_flac_index_device(self.ctx, d_data, length, stream_bits, stream_rate, d_frame_offsets,
+                                                  d_frame_bytes, cap, d_result, _stream(stream)), "flac_index_device")
 
     def decode_frames(self, frames: bytes, sizes: Sequence[int]):
         """flacgpu_decode_frames: concatenated frames of one stream -> (PCM bytes, [DecodeResult])."""
