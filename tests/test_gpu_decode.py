@@ -3,8 +3,8 @@
 Round trips of CPU-encoded streams (the expected PCM is the input, cross-checked with the CPU
 verifier decoder), hand-built frames no encoder here writes, per-frame statuses of corrupted
 frames inside batches of good ones (only input the sanitizer run of test_decode_host.py's host
-program has decoded first, and the statuses must equal that program's), the verify of a plan
-encode, and the whole-file decode."""
+program has decoded first, and the statuses must equal that program's), the host-buffer decode
+in several chunks of max_frames, the verify of a plan encode, and the whole-file decode."""
 import ctypes
 import os
 import sys
@@ -168,6 +168,73 @@ def test_hand_built_frames():
             got, res = d.decode_frames(h["frame"], [len(h["frame"])])
         assert res[0].status == 0 and res[0].number == h["number"] and res[0].block_size == h["block"], h["name"]
         assert got == want, h["name"]
+
+
+_CHUNKED = {}
+
+
+def _chunked_stream():
+    """2 channels, 16 bits, four frames with a short last one: (pcm, frames, sizes), encoded once."""
+    if not _CHUNKED:
+        pcm = synth.synth_pcm(3 * 4096 + 555, 2, 16, 44100, stream=6)
+        fr, sizes, _ = oracle_ref.encode_stream(pcm, 2, 16, 44100)
+        assert len(sizes) == 4
+        _CHUNKED["v"] = (pcm, fr, [int(s) for s in sizes])
+    return _CHUNKED["v"]
+
+
+def _host_decode(d, frames, sizes, cap):
+    """flacgpu_decode_frames through ctypes -> (return code, the whole output buffer, samples, results)."""
+    import flacgpu
+
+    n = len(sizes)
+    out = ctypes.create_string_buffer(b"\xa5" * cap, cap)
+    fb = (ctypes.c_uint32 * n)(*sizes)
+    res = (flacgpu.DecodeResult * n)()
+    ns = ctypes.c_uint64(0)
+    src = ctypes.create_string_buffer(bytes(frames), len(frames))
+    rc = d.lib.flacgpu_decode_frames(d.ctx, src, fb, n, out, cap, ctypes.byref(ns), res)
+    return rc, out.raw, ns.value, list(res)
+
+
+def test_decode_frames_in_chunks():
+    pcm, fr, sizes = _chunked_stream()
+    for max_frames in (1, 2, 3):  # 3: a ragged last chunk of one frame
+        with _decoder(2, 16, max_frames=max_frames) as d:
+            got, res = d.decode_frames(fr, sizes)
+        assert got == pcm, max_frames
+        assert [r.status for r in res] == [0, 0, 0, 0], max_frames
+        assert [r.number for r in res] == [0, 1, 2, 3], max_frames
+        assert [r.block_size for r in res] == [4096, 4096, 4096, 555], max_frames
+
+
+def test_decode_frames_output_too_small_in_second_chunk():
+    pcm, fr, sizes = _chunked_stream()
+    with _decoder(2, 16, max_frames=2) as d:
+        rc, buf, _, _ = _host_decode(d, fr, sizes, len(pcm) - 1)
+    assert rc == -4  # FLACGPU_ERR_OUTPUT_TOO_SMALL
+    first = 2 * 4096 * 4  # the first chunk's two frames
+    assert buf[:first] == pcm[:first]
+
+
+_RESULT_FIELDS = ("status", "block_size", "number", "sample_rate", "first_bad", "channel_assign", "bits")
+
+
+def test_decode_frames_damaged_frame_in_second_chunk():
+    pcm, fr, sizes = _chunked_stream()
+    at = sum(sizes[:2]) + sizes[2] // 2  # a subframe byte of frame 2, far from its header and CRC
+    bad = bytearray(fr)
+    bad[at] ^= 0x08
+    bad = bytes(bad)
+    with _decoder(2, 16, max_frames=64) as d:
+        _, want, n_bad = device_decode(d, _split(bad, sizes), out_bytes=len(pcm))
+    assert n_bad == 1 and [r.status != 0 for r in want] == [False, False, True, False]
+    with _decoder(2, 16, max_frames=2) as d:
+        rc, _, _, res = _host_decode(d, bad, sizes, len(pcm))
+    assert rc == 0
+    for i in range(4):
+        for f in _RESULT_FIELDS:
+            assert getattr(res[i], f) == getattr(want[i], f), (i, f)
 
 
 def _status_batch(tmp_path, exe, c, good_frames, good_pcm, bad_frames):

@@ -19,8 +19,7 @@
 
 #include "../../include/flacgpu.h"
 #include "fg_common.hpp"
-#include "fg_dec.hpp"
-#include "fg_index.hpp"
+#include "fg_ctx.hpp"
 #include "fg_internal.hpp"
 #include "fg_layout.hpp"
 #include "fg_md5_host.hpp"
@@ -30,23 +29,12 @@ hipError_t launch_stage(int stage, const EncodeArgs &a, bool full, uint32_t thre
 hipError_t launch_make_jobs(FrameJob *jobs, uint64_t n_samples, uint32_t block, uint32_t stride, uint64_t first,
                             uint32_t n_frames, hipStream_t st);
 hipError_t launch_frame_totals(const EncodeArgs &a, hipStream_t st);
-hipError_t launch_scan(const uint32_t *sizes, uint64_t *offsets, uint64_t *total, uint32_t n, uint64_t *part,
-                       hipStream_t st, const uint64_t *base = nullptr);
 hipError_t launch_md5_streams(const uint8_t *base, const uint64_t *offs, const uint64_t *lens, const uint8_t *fin,
                               uint32_t n, Md5State *states, uint8_t *digests, hipStream_t st, int kernel, int prio);
 hipError_t launch_advance_jobs(FrameJob *jobs, uint64_t n, uint64_t delta, hipStream_t st);
 hipError_t launch_md5_blocks(uint32_t *state, const uint32_t *blocks, uint64_t n_blocks, hipStream_t st);
 uint32_t md5_workgroups(uint32_t n, int kernel);
 hipError_t launch_streaminfo_replay(const uint32_t *sizes, uint64_t n, uint32_t *minmax, hipStream_t st);
-// fg_dec.hip
-hipError_t launch_dec_parse(const dec::Args &a, hipStream_t st);
-hipError_t launch_dec_recon(const dec::Args &a, hipStream_t st);
-hipError_t launch_dec_expect(const FrameJob *jobs, uint64_t n, uint64_t *pcm_off, uint64_t *number, uint32_t *ns,
-                             hipStream_t st);
-// fg_index.hip
-hipError_t launch_index(const idx::IdxArgs &g, hipStream_t st);
-int decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate,
-                           uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, uint8_t digest[16]);
 }  // namespace fg
 
 using namespace fg;
@@ -54,37 +42,6 @@ using namespace fg;
 static_assert(sizeof(SubRec) == sizeof(flacgpu_subframe_record), "record layout");
 static_assert(sizeof(FrameRec) == sizeof(flacgpu_frame_record), "record layout");
 static_assert(sizeof(Md5State) == sizeof(flacgpu_md5_state), "md5 state layout");
-static_assert(sizeof(dec::Result) == sizeof(flacgpu_decode_result), "decode result layout");
-static_assert(sizeof(idx::IndexResult) == sizeof(flacgpu_index_result), "index result layout");
-static_assert(FLACGPU_INDEX_INVALID == (int)idx::IDX_INVALID && FLACGPU_INDEX_TOO_SMALL == (int)idx::IDX_TOO_SMALL,
-              "index status codes");
-
-// Decode scratch of a context (allocated by its first decode call, max_frames frames): the
-// subframe descriptors k_dec_parse leaves for k_dec_recon, the parsed block sizes and their scan,
-// and the expected frame table of a verify.
-struct DecScratch {
-    dec::DecSub *subs = nullptr;
-    uint32_t *blocks = nullptr, *body = nullptr, *exp_n = nullptr, *ctl = nullptr;  // ctl: [0] ticket
-    uint64_t *samp_off = nullptr, *total = nullptr, *exp_off = nullptr, *exp_number = nullptr;
-    // staging of the host-buffer decode (flacgpu_decode_frames), grow-only
-    uint8_t *d_frames = nullptr, *d_pcm = nullptr;
-    uint64_t frames_cap = 0, pcm_cap = 0;
-    uint64_t *d_foff = nullptr;
-    uint32_t *d_fbytes = nullptr, *d_bad = nullptr;
-    dec::Result *d_results = nullptr;
-};
-
-// Index scratch of a context (flacgpu_flac_index_device), grow-only, sized from the call's len and
-// cap: one allocation carved into the arrays of idx::IdxArgs; and the frame table and result of
-// the whole-file decode, which indexes the file it uploaded.
-struct IdxScratch {
-    uint8_t *buf = nullptr;
-    uint64_t cap = 0;
-    uint64_t *f_off = nullptr;
-    uint32_t *f_bytes = nullptr;
-    uint64_t f_cap = 0;
-    idx::IndexResult *d_res = nullptr;
-};
 
 namespace {
 
@@ -117,141 +74,14 @@ uint32_t q_zpow(uint64_t e) {
     return (r & 0x8000u) ? r ^ 0x8003u : r;
 }
 
-struct TimedLaunch {
-    int kernel;
-    hipEvent_t start, stop;
-};
-
 }  // namespace
-
-// chunk sets of the pipelined host-buffer path (encode_pipelined): chunk i uploads into set i % 3
-// while chunk i-1 encodes and chunks i-2, i-3 download -- with two sets the upload of chunk i had
-// to wait for the encode of chunk i-2 and the encode for the download of chunk i-2, so a slow
-// download or a late host thread stalled both directions of PCIe (round-4 batches reached 33-44 GB/s
-// of H2D against 57 GB/s measured alone)
-constexpr uint32_t kPipeSets = 4;  // the most; flacgpu_ctx::pipe_sets is the number in use (2..4)
-constexpr uint32_t kPipeSetsDefault = 3;
-
-struct flacgpu_ctx {
-    int device = 0;
-    flacgpu_config cfg{};
-    uint32_t max_frames = 0;
-    uint32_t C = 0, B = 0, bits = 0, stereo = 0, nt = 0, nt_pack = 0;
-    uint32_t image_bytes = 0, desc_stride = 0, lds = 0, lds_tail = 0, lds_pack = 0, crc_hmax = 0;
-    bool stage_dbuf = false;
-    bool pack_dbuf = false;
-    hipStream_t stream = nullptr, aux = nullptr;
-    hipStream_t dl = nullptr;  // download stream of the pipelined host-buffer path
-    hipStream_t up = nullptr;  // its upload stream (chunk i+1's upload beside chunk i's encode)
-    hipEvent_t up_done[kPipeSets] = {};  // a chunk set's upload landed (GPU-side waits)
-    hipEvent_t set_done[kPipeSets] = {};  // a chunk set's encode finished (GPU-side waits)
-    hipEvent_t dl_done[kPipeSets] = {};   // a chunk set's frames downloaded (GPU-side waits)
-    uint32_t pipe_sets = kPipeSetsDefault;  // chunk sets in use (FLACGPU_PIPE_SETS = 2: the round-4 schedule; 4)
-    hipEvent_t fork = nullptr, join = nullptr;
-    // host waits of the pipelined host-buffer path (the download stream, the end; the chunk sets'
-    // own events are set_done below):
-    // blocking-sync events, so a waiting thread sleeps instead of spinning on a core the MD5 pool
-    // and the other files' threads need (FLACGPU_SPIN_SYNC=1: spinning events, A/B)
-    hipEvent_t hw[4] = {nullptr, nullptr, nullptr, nullptr};
-    uint16_t *d_crc_pow = nullptr, *d_crc_join = nullptr, *d_crc_pow4 = nullptr;
-    // full 16-bit two-channel frames are packed by k_pack4 (four waves per subframe): 512 threads
-    uint32_t nt_pack4 = 0, lds_pack4 = 0, crc_hmax4 = 0;
-    uint32_t *d_err = nullptr, *d_ctr = nullptr;
-    FrameJob *d_jobs = nullptr;
-    uint8_t *d_desc = nullptr;
-    uint32_t *d_fbytes = nullptr;
-    uint64_t *d_offsets = nullptr, *d_total = nullptr;
-    uint8_t *d_pcm = nullptr;
-    uint64_t pcm_cap = 0;
-    uint8_t *d_out = nullptr;
-    uint64_t out_cap = 0;
-    FrameRec *d_records = nullptr;
-    unsigned long long *d_stamps = nullptr;
-    bool records_on = false;
-    bool records_keep = false;  // encode_files with records: every file's records, concatenated
-    bool ana_split = false;  // full-frame analysis in channel halves (fg_device.hpp k_analyze)
-    bool pack_split = false;  // full-frame pack in channel halves (fg_packw.hpp k_packw<..., true>)
-    uint32_t nt_psplit = 0, lds_psplit = 0, image_split = 0, crc_hmaxs = 0;
-    uint16_t *d_crc_pows = nullptr;  // CRC fold shifts for the split pack's thread count
-    uint16_t *d_crc_x8 = nullptr;    // z^(8 * 2^i) mod P, i < 24
-    uint32_t nt_split = 0, lds_split = 0;
-    uint64_t *d_scan_part = nullptr;  // per-4096-frame block sums of the multi-workgroup scan
-    uint32_t scan_part_cap = 0;
-    std::vector<FrameRec> h_records;
-    bool timing = false;
-    std::vector<TimedLaunch> pending;
-    std::vector<hipEvent_t> event_pool;
-    uint64_t launches[FLACGPU_K_COUNT] = {};
-    double ms[FLACGPU_K_COUNT] = {};
-    // streaming MD5 (one stream): a host core by default (FLACGPU_MD5_HOST), or one GPU
-    // lane fed by bounded chunks (FLACGPU_MD5_DEVICE, opt-in)
-    int md5_engine = FLACGPU_MD5_HOST;
-    int md5_kernel = 1;  // batched stream MD5: 1 = coalesced LDS-DMA ring, 0 = per-lane loads (A/B knob)
-    int md5_prio = 0;    // issue priority of the MD5 waves beside the encode (A/B knob)
-    uint32_t enc_prio = 0;  // issue priority 1 for the C2 encode waves (A/B knob FLACGPU_ENC_PRIO)
-    int md5_reserve = -1;  // 1: the analysis grid leaves one workgroup slot per stream-MD5 workgroup
-                           //    queued beside it, 2: the pack grid too, 0: none, -1: auto (A/B knob)
-    uint32_t grid_reserve = 0;  // per call: slots the next analysis / pack launches leave free
-    // overlapped encode (encode_core): the full frames in `ovl_chunks` ranges, the analysis of
-    // range i+1 on `stream` beside the scan + pack of range i on `ovl`, each grid capped to
-    // ovl_ana / ovl_pack workgroups per CU so both are resident on every CU
-    uint32_t ovl_chunks = 0, ovl_ana = 2, ovl_pack = 2, ovl_min_frames = 4096;
-    bool xcd_queue = true;  // split analysis: per-XCD item queues (fg_device.hpp xcd_ticket)
-    bool pack_xcdq = true;  // split pack: the same (fg_packw.hpp)
-    // split analysis (bit 0) / pack (bit 1): each item's ticket taken right before its DMA, so a
-    // frame's two halves are staged close together (c4 A/B r4l: analysis 5.03 -> 4.95 ms, analysis
-    // traffic 1.82x -> 1.44x of the PCM (r4n); the pack's bit measured no gain, r4o)
-    uint32_t split_jit = 1;
-    // fused single-pass encode of full 16-bit stereo frames (fg_fused.hpp): analysis and pack in
-    // one kernel, frame offsets by an in-kernel look-back over per-slot status words
-    bool fused = false;
-    // one wave per full 16-bit stereo frame (fg_ana1.hpp k_ana1) instead of one per candidate
-    bool ana1 = false;
-    uint32_t ana1_variant = 1;
-    uint32_t lds_fused = 0, crc_hmaxf = 0;
-    uint16_t *d_crc_powf = nullptr;  // CRC fold shifts for its 256 threads
-    uint64_t *d_status = nullptr;    // per-slot status words, grow-only
-    uint64_t status_cap = 0;
-    hipStream_t ovl = nullptr;
-    uint64_t *d_cum = nullptr;  // [chunk] bytes of the frames before the chunk's slot range
-    HostMd5 host_md5;
-    uint32_t *d_md5_state = nullptr;
-    uint32_t *d_md5_blocks = nullptr;
-    uint8_t md5_buf[64] = {};
-    uint32_t md5_fill = 0;
-    uint64_t md5_len = 0;
-    DecScratch *dec = nullptr;  // frame decoder / verifier: allocated by the first decode call
-    IdxScratch *idx = nullptr;  // device frame index: allocated by the first index call
-};
 
 // device MD5 engine: whole blocks move through one bounded device buffer
 constexpr uint64_t kMd5ChunkBlocks = (64ull << 20) / 64;
 // overlapped encode: at most this many frame ranges per call (one ticket set of 4 u32 each)
 constexpr uint32_t kOvlMaxChunks = 64;
 
-struct flacgpu_plan {
-    flacgpu_ctx *ctx = nullptr;
-    uint32_t n_streams = 0;
-    uint32_t B = 0;
-    uint64_t n_frames = 0, n_full = 0, n_tail = 0;
-    FrameJob *d_jobs = nullptr;  // full jobs first, then tail jobs
-    uint64_t *d_md5_offs = nullptr, *d_md5_lens = nullptr;
-    uint8_t *d_md5_fin = nullptr;  // per-stream final-segment flags (NULL: all final)
-    uint64_t md5_max_len = 0;      // longest stream segment (bytes): the MD5 chain of one call
-    uint64_t max_number = 0;       // largest frame number in the table (u36 check on advance)
-    std::vector<uint64_t> first_frame;
-    std::vector<uint32_t> full_slots;  // slot of each full job (host copy: ranges of the overlapped encode)
-    // host copies of the MD5 segments (the host engine, flacgpu_md5_plan_host)
-    std::vector<uint64_t> h_md5_offs, h_md5_lens;
-    std::vector<uint8_t> h_md5_fin;  // empty: all final
-    uint64_t md5_total = 0;          // bytes of all segments
-    uint64_t out_bound = 0;
-    uint8_t *d_desc = nullptr;  // per-plan descriptor area when larger than the context's
-};
-
-namespace {
-
-hipEvent_t get_event(flacgpu_ctx *c) {
+hipEvent_t fg::get_event(flacgpu_ctx *c) {
     if (!c->event_pool.empty()) {
         hipEvent_t e = c->event_pool.back();
         c->event_pool.pop_back();
@@ -261,6 +91,8 @@ hipEvent_t get_event(flacgpu_ctx *c) {
     if (hipEventCreate(&e) != hipSuccess) return nullptr;
     return e;
 }
+
+namespace {
 
 void resolve_timing(flacgpu_ctx *c) {
     for (auto &t : c->pending) {
@@ -274,42 +106,6 @@ void resolve_timing(flacgpu_ctx *c) {
         c->event_pool.push_back(t.stop);
     }
     c->pending.clear();
-}
-
-struct Timed {
-    flacgpu_ctx *c;
-    int k;
-    hipStream_t st;
-    hipEvent_t a = nullptr, b = nullptr;
-    Timed(flacgpu_ctx *c_, int k_, hipStream_t st_) : c(c_), k(k_), st(st_) {
-        if (c->timing) {
-            a = get_event(c);
-            b = get_event(c);
-            if (a) hipEventRecord(a, st);
-        }
-    }
-    ~Timed() {
-        if (c->timing && a && b) {
-            hipEventRecord(b, st);
-            c->pending.push_back({k, a, b});
-        }
-    }
-};
-
-int hip_err(hipError_t e) { return e == hipSuccess ? FLACGPU_OK : (e == hipErrorOutOfMemory ? FLACGPU_ERR_OUT_OF_MEMORY : FLACGPU_ERR_DEVICE); }
-
-#define HIPCHK(x)                               \
-    do {                                        \
-        hipError_t e_ = (x);                    \
-        if (e_ != hipSuccess) return hip_err(e_); \
-    } while (0)
-
-// The C ABI's hip_stream: NULL = the context's own stream, FLACGPU_STREAM_LEGACY = the HIP null
-// stream (legacy default-stream semantics: the handle-0 stream of a framework), else a hipStream_t.
-static hipStream_t pick_stream(const flacgpu_ctx *c, void *hip_stream) {
-    if (!hip_stream) return c->stream;
-    if (hip_stream == FLACGPU_STREAM_LEGACY) return (hipStream_t)0;
-    return (hipStream_t)hip_stream;
 }
 
 int validate(const flacgpu_config *cfg) {
@@ -445,25 +241,13 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
     };
     // the multi-workgroup scan's per-block sums: a grow-only context buffer
     const uint32_t nb = (uint32_t)((n_frames + 4095u) / 4096u);
-    if (nb > c->scan_part_cap) {
-        hipFree(c->d_scan_part);
-        c->d_scan_part = nullptr;
-        c->scan_part_cap = 0;
-        HIPCHK(hipMalloc(&c->d_scan_part, (size_t)nb * 8u));
-        c->scan_part_cap = nb;
-    }
+    HIPCHK(grow(c->d_scan_part, c->scan_part_cap, nb));
 
     if (c->fused && n_full) {
         // fused: the tail frames' analysis first (it publishes their sizes), then analysis + pack of
         // the full frames in one kernel whose frames find their offsets by look-back, then the scan
         // (offsets of every frame, the total) and the tail frames' pack
-        if (n_frames > c->status_cap) {
-            hipFree(c->d_status);
-            c->d_status = nullptr;
-            c->status_cap = 0;
-            HIPCHK(hipMalloc(&c->d_status, (size_t)n_frames * 8u));
-            c->status_cap = n_frames;
-        }
+        HIPCHK(grow(c->d_status, c->status_cap, n_frames));
         HIPCHK(hipMemsetAsync(c->d_status, 0, (size_t)n_frames * 8u, st));
         HIPCHK(hipMemsetAsync(c->d_ctr, 0, 4, st));  // the fused kernel's frame queue (ticket 0)
         a.status = c->d_status;
@@ -917,20 +701,7 @@ void flacgpu_close(flacgpu_ctx *c) {
     hipFree(c->d_status);
     hipFree(c->d_crc_join);
     hipFree(c->d_scan_part);
-    if (c->dec) {
-        DecScratch *d = c->dec;
-        void *bufs[] = {d->subs, d->blocks, d->body, d->exp_n, d->ctl, d->samp_off, d->total, d->exp_off, d->exp_number,
-                        d->d_frames, d->d_pcm, d->d_foff, d->d_fbytes, d->d_bad, d->d_results};
-        for (void *b : bufs) hipFree(b);
-        delete d;
-    }
-    if (c->idx) {
-        hipFree(c->idx->buf);
-        hipFree(c->idx->f_off);
-        hipFree(c->idx->f_bytes);
-        hipFree(c->idx->d_res);
-        delete c->idx;
-    }
+    dec_release(c);
     hipFree(c->d_err);
     hipFree(c->d_ctr);
     hipFree(c->d_cum);
@@ -1767,333 +1538,4 @@ int flacgpu_debug_stamps(flacgpu_ctx *c, uint64_t *out32, int reset) {
     return FLACGPU_OK;
 }
 
-// ---- frame decoder / verifier (fg_dec.hpp, fg_dec.hip) -------------------------------------
-static int dec_scratch(flacgpu_ctx *c) {
-    if (c->dec) return FLACGPU_OK;
-    DecScratch *d = new (std::nothrow) DecScratch();
-    if (!d) return FLACGPU_ERR_OUT_OF_MEMORY;
-    c->dec = d;  // freed by flacgpu_close, whole or partial
-    const uint64_t n = c->max_frames;
-    HIPCHK(hipMalloc(&d->subs, n * c->C * sizeof(dec::DecSub)));
-    HIPCHK(hipMalloc(&d->blocks, n * 4u));
-    HIPCHK(hipMalloc(&d->body, n * 4u));
-    HIPCHK(hipMalloc(&d->exp_n, n * 4u));
-    HIPCHK(hipMalloc(&d->ctl, 64));
-    HIPCHK(hipMalloc(&d->samp_off, n * 8u));
-    HIPCHK(hipMalloc(&d->total, 8));
-    HIPCHK(hipMalloc(&d->exp_off, n * 8u));
-    HIPCHK(hipMalloc(&d->exp_number, n * 8u));
-    HIPCHK(hipMalloc(&d->d_bad, 4));
-    return FLACGPU_OK;
-}
-
-// parse, (scan,) reconstruct of n frames, queued on st
-static int dec_core(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff, const uint32_t *d_fbytes, uint32_t n,
-                    const uint64_t *d_pcm_off, uint8_t *d_out, uint64_t cap, const uint8_t *d_expect, bool verify,
-                    flacgpu_decode_result *d_results, uint32_t *d_bad, hipStream_t st) {
-    DecScratch *d = c->dec;
-    dec::Args a{};
-    a.frames = d_frames;
-    a.frame_off = d_foff;
-    a.frame_bytes = d_fbytes;
-    a.n_frames = n;
-    a.channels = c->C;
-    a.bits = c->bits;
-    a.bps = c->bits / 8u;
-    a.rate = c->cfg.sample_rate;
-    a.block = c->cfg.block_size;
-    a.subs = d->subs;
-    a.blocks = d->blocks;
-    a.body = d->body;
-    a.pcm_off = d_pcm_off;
-    a.samp_off = d->samp_off;
-    a.out = d_out;
-    a.cap = cap;
-    a.expect = d_expect;
-    a.exp_number = verify ? d->exp_number : nullptr;
-    a.exp_n = verify ? d->exp_n : nullptr;
-    a.results = (dec::Result *)d_results;
-    a.bad = d_bad ? d_bad : d->d_bad;
-    a.ticket = d->ctl;
-    {
-        Timed t(c, FLACGPU_K_DEC_PARSE, st);
-        HIPCHK(launch_dec_parse(a, st));
-    }
-    if (!d_pcm_off) {
-        // consecutive blocks of one stream: sample offsets from the scan of the parsed block sizes
-        const uint32_t nb = (n + 4095u) / 4096u;
-        if (nb > c->scan_part_cap) {
-            HIPCHK(hipStreamSynchronize(st));
-            hipFree(c->d_scan_part);
-            c->d_scan_part = nullptr;
-            c->scan_part_cap = 0;
-            HIPCHK(hipMalloc(&c->d_scan_part, (size_t)nb * 8u));
-            c->scan_part_cap = nb;
-        }
-        Timed t(c, FLACGPU_K_SCAN, st);
-        HIPCHK(launch_scan(d->blocks, d->samp_off, d->total, n, c->d_scan_part, st));
-    }
-    Timed t(c, FLACGPU_K_DEC_RECON, st);
-    HIPCHK(launch_dec_recon(a, st));
-    return FLACGPU_OK;
-}
-
-int flacgpu_decode_frames_device(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_frame_offsets,
-                                 const uint32_t *d_frame_bytes, uint64_t n_frames, const uint64_t *d_pcm_offsets,
-                                 uint8_t *d_pcm_out, uint64_t pcm_cap, const uint8_t *d_pcm_expect,
-                                 flacgpu_decode_result *d_results, uint32_t *d_bad_count, void *hip_stream) {
-    if (!c || !d_frames || !d_frame_offsets || !d_frame_bytes || !d_results || !d_bad_count || n_frames > c->max_frames)
-        return FLACGPU_ERR_INVALID_INPUT;
-    HIPCHK(hipSetDevice(c->device));
-    const int rc = dec_scratch(c);
-    if (rc) return rc;
-    hipStream_t st = pick_stream(c, hip_stream);
-    if (n_frames == 0) {
-        HIPCHK(hipMemsetAsync(d_bad_count, 0, 4, st));
-        return FLACGPU_OK;
-    }
-    return dec_core(c, d_frames, d_frame_offsets, d_frame_bytes, (uint32_t)n_frames, d_pcm_offsets, d_pcm_out, pcm_cap,
-                    d_pcm_expect, false, d_results, d_bad_count, st);
-}
-
-int flacgpu_verify_plan_device(flacgpu_ctx *c, const flacgpu_plan *p, const void *d_pcm, const uint8_t *d_out,
-                               const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
-                               flacgpu_decode_result *d_results, uint32_t *d_bad_count, void *hip_stream) {
-    if (!c || !p || p->ctx != c || !d_pcm || !d_out || !d_frame_offsets || !d_frame_bytes || !d_results || !d_bad_count ||
-        p->n_frames > c->max_frames)
-        return FLACGPU_ERR_INVALID_INPUT;
-    HIPCHK(hipSetDevice(c->device));
-    const int rc = dec_scratch(c);
-    if (rc) return rc;
-    hipStream_t st = pick_stream(c, hip_stream);
-    if (p->n_frames == 0) {
-        HIPCHK(hipMemsetAsync(d_bad_count, 0, 4, st));
-        return FLACGPU_OK;
-    }
-    DecScratch *d = c->dec;
-    // the plan's frame table (full jobs, then tail jobs) by output slot
-    HIPCHK(launch_dec_expect(p->d_jobs, p->n_frames, d->exp_off, d->exp_number, d->exp_n, st));
-    return dec_core(c, d_out, d_frame_offsets, d_frame_bytes, (uint32_t)p->n_frames, d->exp_off, nullptr, 0,
-                    (const uint8_t *)d_pcm, true, d_results, d_bad_count, st);
-}
-
-// ---- device frame index (fg_index.hpp, fg_index.hip) ----------------------------------------
-static IdxScratch *idx_scratch(flacgpu_ctx *c) {
-    if (!c->idx) c->idx = new (std::nothrow) IdxScratch();  // freed by flacgpu_close
-    return c->idx;
-}
-
-// the eight stages over [d_data, d_data + len), len > 0, queued on st
-static int index_core(flacgpu_ctx *c, const uint8_t *d_data, uint64_t len, uint32_t stream_bits, uint32_t stream_rate,
-                      uint64_t *d_off, uint32_t *d_bytes, uint64_t cap, idx::IndexResult *d_res, hipStream_t st) {
-    IdxScratch *x = idx_scratch(c);
-    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
-    idx::IdxArgs g{};
-    g.data = d_data;
-    g.len = len;
-    g.lead = (uint32_t)((uintptr_t)d_data & 15u);
-    g.bits = stream_bits;
-    g.rate = stream_rate;
-    g.n_chunks = (g.lead + len + idx::kIdxChunk - 1u) / idx::kIdxChunk;
-    g.n_groups = (uint32_t)((g.n_chunks + idx::kIdxGroup - 1u) / idx::kIdxGroup);
-    g.spos_cap = std::min<uint64_t>(cap, len / 8u + 1u);  // a frame is at least 9 bytes
-    g.offs = d_off;
-    g.bytes = d_bytes;
-    g.cap = cap;
-    g.res = d_res;
-    // the carve: 8-byte arrays first
-    const uint64_t nc = g.n_chunks, ng = g.n_groups;
-    const uint64_t o_cmask = 0, o_smask = o_cmask + nc * 8u, o_grp = o_smask + nc * 8u, o_gcnt = o_grp + ng * 4u,
-                   o_ctl = o_gcnt + ng * 4u, o_spos = o_ctl + 16u, o_terms = o_spos + g.spos_cap * 4u,
-                   need = o_terms + nc * 2u;
-    if (need > x->cap) {
-        HIPCHK(hipStreamSynchronize(st));  // an earlier index on this stream may still use the old one
-        hipFree(x->buf);
-        x->buf = nullptr;
-        x->cap = 0;
-        HIPCHK(hipMalloc(&x->buf, need));
-        x->cap = need;
-    }
-    g.cmask = (uint64_t *)(x->buf + o_cmask);
-    g.smask = (uint64_t *)(x->buf + o_smask);
-    g.grp = (uint32_t *)(x->buf + o_grp);
-    g.gcnt = (uint32_t *)(x->buf + o_gcnt);
-    g.ctl = (uint32_t *)(x->buf + o_ctl);
-    g.spos = (uint32_t *)(x->buf + o_spos);
-    g.terms = (uint16_t *)(x->buf + o_terms);
-    Timed t(c, FLACGPU_K_INDEX, st);
-    HIPCHK(launch_index(g, st));
-    return FLACGPU_OK;
-}
-
-int flacgpu_flac_index_device(flacgpu_ctx *c, const uint8_t *d_data, uint64_t len, uint32_t stream_bits,
-                              uint32_t stream_rate, uint64_t *d_frame_offsets, uint32_t *d_frame_bytes, uint64_t cap,
-                              flacgpu_index_result *d_result, void *hip_stream) {
-    if (!c || !d_data || !d_frame_offsets || !d_frame_bytes || !d_result || len > 0xFFFFFFFFull)
-        return FLACGPU_ERR_INVALID_INPUT;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = pick_stream(c, hip_stream);
-    if (len == 0) {  // no frames: OK, 0
-        HIPCHK(hipMemsetAsync(d_result, 0, sizeof(flacgpu_index_result), st));
-        return FLACGPU_OK;
-    }
-    return index_core(c, d_data, len, stream_bits, stream_rate, d_frame_offsets, d_frame_bytes, cap,
-                      (idx::IndexResult *)d_result, st);
-}
-
-int flacgpu_decode_frames(flacgpu_ctx *c, const uint8_t *frames, const uint32_t *frame_bytes, uint64_t n_frames,
-                          uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, flacgpu_decode_result *results) {
-    if (!c || !n_samples || !results || (n_frames && (!frames || !frame_bytes)) || (pcm_cap && !pcm_out))
-        return FLACGPU_ERR_INVALID_INPUT;
-    *n_samples = 0;
-    if (n_frames == 0) return FLACGPU_OK;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = dec_scratch(c);
-    if (rc) return rc;
-    DecScratch *d = c->dec;
-    hipStream_t st = c->stream;
-    const uint64_t frame_pcm = (uint64_t)c->cfg.block_size * c->C * (c->bits / 8u);
-    if (!d->d_foff) {
-        HIPCHK(hipMalloc(&d->d_foff, (uint64_t)c->max_frames * 8u));
-        HIPCHK(hipMalloc(&d->d_fbytes, (uint64_t)c->max_frames * 4u));
-        HIPCHK(hipMalloc(&d->d_results, (uint64_t)c->max_frames * sizeof(dec::Result)));
-    }
-    std::vector<uint64_t> foff;
-    uint64_t src = 0, written = 0;
-    for (uint64_t f0 = 0; f0 < n_frames; f0 += c->max_frames) {
-        const uint32_t n = (uint32_t)std::min<uint64_t>(c->max_frames, n_frames - f0);
-        foff.assign(n, 0);
-        uint64_t bytes = 0;
-        for (uint32_t i = 0; i < n; i++) {
-            foff[i] = bytes;
-            bytes += frame_bytes[f0 + i];
-        }
-        if (bytes + 16u > d->frames_cap) {
-            hipFree(d->d_frames);
-            d->d_frames = nullptr;
-            d->frames_cap = 0;
-            HIPCHK(hipMalloc(&d->d_frames, bytes + 16u));
-            d->frames_cap = bytes + 16u;
-        }
-        const uint64_t need = (uint64_t)n * frame_pcm;
-        if (need > d->pcm_cap) {
-            hipFree(d->d_pcm);
-            d->d_pcm = nullptr;
-            d->pcm_cap = 0;
-            HIPCHK(hipMalloc(&d->d_pcm, need));
-            d->pcm_cap = need;
-        }
-        HIPCHK(hipMemcpyAsync(d->d_frames, frames + src, bytes, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d->d_foff, foff.data(), (uint64_t)n * 8u, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(d->d_fbytes, frame_bytes + f0, (uint64_t)n * 4u, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemsetAsync(d->d_pcm, 0, need, st));
-        rc = dec_core(c, d->d_frames, d->d_foff, d->d_fbytes, n, nullptr, d->d_pcm, need, nullptr, false,
-                      (flacgpu_decode_result *)d->d_results, nullptr, st);
-        if (rc) return rc;
-        uint64_t total = 0;
-        HIPCHK(hipMemcpyAsync(results + f0, d->d_results, (uint64_t)n * sizeof(dec::Result), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&total, d->total, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        const uint64_t out_bytes = total * c->C * (c->bits / 8u);
-        if (out_bytes > need) return FLACGPU_ERR_INTERNAL;
-        if (written + out_bytes > pcm_cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
-        if (out_bytes) HIPCHK(hipMemcpy(pcm_out + written, d->d_pcm, out_bytes, hipMemcpyDeviceToHost));
-        written += out_bytes;
-        *n_samples += total;
-        src += bytes;
-    }
-    return FLACGPU_OK;
-}
-
 }  // extern "C"
-
-// The device side of flacgpu_decode_file (fg_dec_api.cpp): the frames [p, p + len) of a stream of
-// the context's layout uploaded once, indexed on the device, decoded from there in chunks of
-// max_frames; every chunk's PCM is downloaded to pcm_out and hashed while the next chunk decodes.
-// Returns 1 where the device index does not give a frame table (it refuses the stream, or its
-// scratch cannot be had): the caller then takes the host path, which names the error.
-int fg::decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate,
-                               uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, uint8_t digest[16]) {
-    if (len == 0 || len > 0xFFFFFFFFull) return 1;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = dec_scratch(c);
-    if (rc) return rc;
-    DecScratch *d = c->dec;
-    hipStream_t st = c->stream;
-    IdxScratch *x = idx_scratch(c);
-    if (!x) return 1;
-    const uint64_t fcap = len / 8u + 1u;
-    if (fcap > x->f_cap) {
-        HIPCHK(hipStreamSynchronize(st));
-        hipFree(x->f_off);
-        hipFree(x->f_bytes);
-        x->f_off = nullptr;
-        x->f_bytes = nullptr;
-        x->f_cap = 0;
-        if (hipMalloc(&x->f_off, fcap * 8u) != hipSuccess || hipMalloc(&x->f_bytes, fcap * 4u) != hipSuccess) return 1;
-        x->f_cap = fcap;
-    }
-    if (!x->d_res && hipMalloc(&x->d_res, sizeof(idx::IndexResult)) != hipSuccess) return 1;
-    if (!d->d_foff) {
-        HIPCHK(hipMalloc(&d->d_foff, (uint64_t)c->max_frames * 8u));
-        HIPCHK(hipMalloc(&d->d_fbytes, (uint64_t)c->max_frames * 4u));
-        HIPCHK(hipMalloc(&d->d_results, (uint64_t)c->max_frames * sizeof(dec::Result)));
-    }
-    if (len + 16u > d->frames_cap) {
-        HIPCHK(hipStreamSynchronize(st));
-        hipFree(d->d_frames);
-        d->d_frames = nullptr;
-        d->frames_cap = 0;
-        if (hipMalloc(&d->d_frames, len + 16u) != hipSuccess) return 1;
-        d->frames_cap = len + 16u;
-    }
-    HIPCHK(hipMemcpyAsync(d->d_frames, p, len, hipMemcpyHostToDevice, st));
-    rc = index_core(c, d->d_frames, len, stream_bits, stream_rate, x->f_off, x->f_bytes, fcap, x->d_res, st);
-    if (rc == FLACGPU_ERR_OUT_OF_MEMORY) return 1;
-    if (rc) return rc;
-    idx::IndexResult ir{};
-    HIPCHK(hipMemcpyAsync(&ir, x->d_res, sizeof(ir), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (ir.status != idx::IDX_OK || ir.n_frames > fcap) return 1;
-    const uint64_t n_frames = ir.n_frames;
-    const uint64_t per = (uint64_t)c->C * (c->bits / 8u), frame_pcm = (uint64_t)c->cfg.block_size * per;
-    std::vector<dec::Result> res(c->max_frames);
-    HostMd5 md5;
-    uint64_t written = 0, hashed = 0;
-    bool damaged = false;
-    for (uint64_t f0 = 0; f0 < n_frames; f0 += c->max_frames) {
-        const uint32_t n = (uint32_t)std::min<uint64_t>(c->max_frames, n_frames - f0);
-        const uint64_t need = (uint64_t)n * frame_pcm;
-        if (need > d->pcm_cap) {
-            hipFree(d->d_pcm);
-            d->d_pcm = nullptr;
-            d->pcm_cap = 0;
-            HIPCHK(hipMalloc(&d->d_pcm, need));
-            d->pcm_cap = need;
-        }
-        HIPCHK(hipMemsetAsync(d->d_pcm, 0, need, st));
-        rc = dec_core(c, d->d_frames, x->f_off + f0, x->f_bytes + f0, n, nullptr, d->d_pcm, need, nullptr, false,
-                      (flacgpu_decode_result *)d->d_results, nullptr, st);
-        if (rc) return rc;
-        uint64_t total = 0;
-        HIPCHK(hipMemcpyAsync(res.data(), d->d_results, (uint64_t)n * sizeof(dec::Result), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(&total, d->total, 8, hipMemcpyDeviceToHost, st));
-        // the chunk before this one, already in pcm_out, is hashed while this one decodes
-        md5.update(pcm_out + hashed, (size_t)(written - hashed));
-        hashed = written;
-        HIPCHK(hipStreamSynchronize(st));
-        const uint64_t out_bytes = total * per;
-        if (out_bytes > need) return FLACGPU_ERR_INTERNAL;
-        if (written + out_bytes > pcm_cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
-        if (out_bytes) HIPCHK(hipMemcpy(pcm_out + written, d->d_pcm, out_bytes, hipMemcpyDeviceToHost));
-        written += out_bytes;
-        *n_samples += total;
-        for (uint32_t i = 0; i < n; i++)
-            if (res[i].status) damaged = true;
-    }
-    if (damaged) return FLACGPU_ERR_INVALID_INPUT;  // a damaged frame: not a decodable file
-    md5.update(pcm_out + hashed, (size_t)(written - hashed));
-    md5.final(digest);
-    return FLACGPU_OK;
-}
-

@@ -24,6 +24,7 @@
 #include <new>
 #include <vector>
 
+#include "fg_ctx.hpp"
 #include "fg_internal.hpp"
 
 namespace {
@@ -66,12 +67,6 @@ const Rccl &rccl() {
     return r;
 }
 
-int hip_rc(hipError_t e) { return e == hipSuccess ? FLACGPU_OK : (e == hipErrorOutOfMemory ? FLACGPU_ERR_OUT_OF_MEMORY : FLACGPU_ERR_DEVICE); }
-#define CHK_HIP(x)                                  \
-    do {                                            \
-        const hipError_t e_ = (x);                  \
-        if (e_ != hipSuccess) return hip_rc(e_);    \
-    } while (0)
 #define CHK_NCCL(x)                                  \
     do {                                             \
         if ((x) != ncclSuccess) return FLACGPU_ERR_DEVICE; \
@@ -105,11 +100,11 @@ namespace {
 int exchange_counts(flacgpu_comm *m, const uint64_t entry[kWords], const uint64_t *d_nbytes, hipStream_t st) {
     const Rccl &r = rccl();
     std::memcpy(m->h_cnt, entry, kWords * sizeof(uint64_t));
-    CHK_HIP(hipMemcpyAsync(m->d_cnt, m->h_cnt, kWords * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (d_nbytes) CHK_HIP(hipMemcpyAsync(m->d_cnt + kBytes, d_nbytes, sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    HIPCHK(hipMemcpyAsync(m->d_cnt, m->h_cnt, kWords * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (d_nbytes) HIPCHK(hipMemcpyAsync(m->d_cnt + kBytes, d_nbytes, sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
     CHK_NCCL(r.all_gather(m->d_cnt, m->d_all, kWords, ncclUint64, m->nc, st));
-    CHK_HIP(hipMemcpyAsync(m->h_all, m->d_all, (size_t)m->world * kWords * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    CHK_HIP(hipStreamSynchronize(st));
+    HIPCHK(hipMemcpyAsync(m->h_all, m->d_all, (size_t)m->world * kWords * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
     return FLACGPU_OK;
 }
 
@@ -138,9 +133,9 @@ int transfer(flacgpu_comm *m, const uint8_t *d_frames, const uint32_t *d_sizes, 
     if (m->rank == 0) {
         // its own slice: in place, a device copy, or (self_p2p) send/recv to itself
         const bool pb = my_b && d_frames != d_recv, pf = my_f && d_sizes != d_recv_sizes;
-        if (pb && !m->self_p2p) CHK_HIP(hipMemcpyAsync(d_recv, d_frames, my_b, hipMemcpyDeviceToDevice, st));
+        if (pb && !m->self_p2p) HIPCHK(hipMemcpyAsync(d_recv, d_frames, my_b, hipMemcpyDeviceToDevice, st));
         if (pf && !m->self_p2p)
-            CHK_HIP(hipMemcpyAsync(d_recv_sizes, d_sizes, my_f * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemcpyAsync(d_recv_sizes, d_sizes, my_f * 4, hipMemcpyDeviceToDevice, st));
         const bool self = m->self_p2p && (pb || pf);
         if (m->world == 1 && !self) return FLACGPU_OK;
         CHK_NCCL(r.group_start());
@@ -195,7 +190,7 @@ int flacgpu_comm_init(const uint8_t id[FLACGPU_COMM_ID_BYTES], int world, int ra
     *out = nullptr;
     const Rccl &r = rccl();
     if (!r.ok) return FLACGPU_ERR_DEVICE;
-    CHK_HIP(hipSetDevice(device));
+    HIPCHK(hipSetDevice(device));
     flacgpu_comm *m = new (std::nothrow) flacgpu_comm;
     if (!m) return FLACGPU_ERR_OUT_OF_MEMORY;
     m->world = world;
@@ -248,7 +243,7 @@ int flacgpu_gather_frames_device(flacgpu_comm *m, const uint8_t *d_frames, uint6
     if ((n_frames && !d_sizes) || ((nbytes || d_nbytes) && !d_frames) ||
         (m->rank == 0 && ((recv_cap && !d_recv) || (recv_sizes_cap && !d_recv_sizes))))
         local = FLACGPU_ERR_INVALID_INPUT;
-    CHK_HIP(hipSetDevice(m->device));
+    HIPCHK(hipSetDevice(m->device));
     const hipStream_t st = as_stream(hip_stream);
     uint64_t e[kWords] = {};
     e[kFrames] = local ? 0 : n_frames;
@@ -281,7 +276,7 @@ int flacgpu_encode_frames_sharded(flacgpu_ctx *ctx, flacgpu_comm *m, const void 
     const uint64_t isz = local ? 0 : (uint64_t)d.channels * bytes_per_sample;
     // every rank must run the same number of windows: agree on it (and on any argument error)
     // through one count exchange before the first window
-    CHK_HIP(hipSetDevice(m->device));
+    HIPCHK(hipSetDevice(m->device));
     hipStream_t st = local ? (hipStream_t)0 : (hipStream_t)d.stream;
     uint64_t e[kWords] = {};
     e[kFrames] = frames;
@@ -299,19 +294,9 @@ int flacgpu_encode_frames_sharded(flacgpu_ctx *ctx, flacgpu_comm *m, const void 
     windows = (frames + wf - 1) / wf;
     // rank 0's receive buffers: one window of every rank's frames
     if (m->rank == 0) {
-        const uint64_t need = (uint64_t)m->world * d.out_cap, need_f = wf;
-        if (need > m->recv_cap) {
-            hipFree(m->d_recv);
-            m->d_recv = nullptr;
-            m->recv_cap = 0;
-            if (hipMalloc(&m->d_recv, need) == hipSuccess) m->recv_cap = need;
-        }
-        if (need_f > m->recv_sizes_cap) {
-            hipFree(m->d_recv_sizes);
-            m->d_recv_sizes = nullptr;
-            m->recv_sizes_cap = 0;
-            if (hipMalloc(&m->d_recv_sizes, need_f * 4) == hipSuccess) m->recv_sizes_cap = need_f;
-        }
+        // a failure leaves a null buffer: reported to every rank as out of memory by the first window
+        (void)fg::grow(m->d_recv, m->recv_cap, (uint64_t)m->world * d.out_cap);
+        (void)fg::grow(m->d_recv_sizes, m->recv_sizes_cap, wf);
     }
     uint64_t written = 0, frames_out = 0;
     int err = FLACGPU_OK;
@@ -343,10 +328,10 @@ int flacgpu_encode_frames_sharded(flacgpu_ctx *ctx, flacgpu_comm *m, const void 
             if (written + tb > out_cap) {
                 err = FLACGPU_ERR_OUTPUT_TOO_SMALL;  // rank 0 only: reported to the others next window
             } else {
-                if (tb) CHK_HIP(hipMemcpyAsync(out + written, m->d_recv, tb, hipMemcpyDeviceToHost, st));
+                if (tb) HIPCHK(hipMemcpyAsync(out + written, m->d_recv, tb, hipMemcpyDeviceToHost, st));
                 if (tf && frame_bytes)
-                    CHK_HIP(hipMemcpyAsync(frame_bytes + frames_out, m->d_recv_sizes, tf * 4, hipMemcpyDeviceToHost, st));
-                CHK_HIP(hipStreamSynchronize(st));
+                    HIPCHK(hipMemcpyAsync(frame_bytes + frames_out, m->d_recv_sizes, tf * 4, hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
                 written += tb;
                 frames_out += tf;
             }

@@ -1,6 +1,6 @@
 // fg_dec_api.cpp -- the host-only side of the decoder's C ABI: the frame index of a FLAC file or
 // of a bare run of frames (no GPU), and the whole-file decode: metadata here, the frames through
-// the device index and decode (fg_api.cpp decode_stream_resident), or, where the device index
+// the device index and decode (fg_dec_host.cpp decode_stream_resident), or, where the device index
 // refuses them, through the host index and flacgpu_decode_frames.  Plain C++ over
 // include/flacgpu.h and the shared decode core.
 #include <cstring>
@@ -9,15 +9,10 @@
 #include "../../include/flacgpu.h"
 #include "fg_dec.hpp"
 #include "fg_index.hpp"
+#include "fg_internal.hpp"
 #include "fg_md5_host.hpp"
 
 using namespace fg;
-
-namespace fg {
-// fg_api.cpp: upload once, index and decode on the device; 1 = no frame table from the device index
-int decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate,
-                           uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, uint8_t digest[16]);
-}  // namespace fg
 
 namespace {
 

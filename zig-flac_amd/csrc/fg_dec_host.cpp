@@ -1,0 +1,359 @@
+// fg_dec_host.cpp -- the device-driving side of the decoder's C ABI: the frame decoder / verifier
+// (fg_dec.hpp, fg_dec.hip) and the device frame index (fg_index.hpp, fg_index.hip) over device
+// memory, the host-buffer decode, and the device side of the whole-file decode.  The host-only
+// side (metadata, the host index, flacgpu_decode_file) is fg_dec_api.cpp.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <new>
+#include <vector>
+
+#include "../../include/flacgpu.h"
+#include "fg_ctx.hpp"
+#include "fg_dec.hpp"
+#include "fg_index.hpp"
+#include "fg_internal.hpp"
+
+using namespace fg;
+
+static_assert(sizeof(dec::Result) == sizeof(flacgpu_decode_result), "decode result layout");
+static_assert(sizeof(idx::IndexResult) == sizeof(flacgpu_index_result), "index result layout");
+static_assert(FLACGPU_INDEX_INVALID == (int)idx::IDX_INVALID && FLACGPU_INDEX_TOO_SMALL == (int)idx::IDX_TOO_SMALL,
+              "index status codes");
+
+// Decode scratch of a context (allocated by its first decode call, max_frames frames), one
+// allocation: the subframe descriptors k_dec_parse leaves for k_dec_recon, the parsed block sizes
+// and their scan, the expected frame table of a verify, and a chunk's frame table and results in
+// the host-buffer decodes (decode_chunk).  Those decodes' frames and PCM are grow-only.
+struct DecScratch {
+    uint8_t *buf = nullptr;
+    uint64_t *samp_off, *total, *exp_off, *exp_number, *d_foff;
+    dec::Result *d_results;
+    dec::DecSub *subs;
+    uint32_t *blocks, *body, *exp_n, *d_fbytes, *ctl, *d_bad;  // ctl: [0] ticket
+    uint8_t *d_frames = nullptr, *d_pcm = nullptr;
+    uint64_t frames_cap = 0, pcm_cap = 0;
+};
+
+// Index scratch of a context, grow-only: the arrays of idx::IdxArgs, sized from the call's len and
+// cap; and the frame table and result of the whole-file decode, which indexes the file it uploaded.
+struct IdxScratch {
+    uint8_t *buf = nullptr, *table = nullptr;
+    uint64_t cap = 0, table_cap = 0;
+};
+
+void fg::dec_release(flacgpu_ctx *c) {
+    if (DecScratch *d = c->dec)
+        for (uint8_t *b : {d->buf, d->d_frames, d->d_pcm}) hipFree(b);
+    if (IdxScratch *x = c->idx)
+        for (uint8_t *b : {x->buf, x->table}) hipFree(b);
+    delete c->dec;
+    delete c->idx;
+    c->dec = nullptr;
+    c->idx = nullptr;
+}
+
+namespace {
+
+// Carves one allocation into arrays, each aligned like an allocation of its own: take() hands the
+// next n elements to each of its pointers and returns the bytes used so far.  A carve is written
+// once, as a function of the base, and run twice: on NULL for the size, then on the allocation.
+struct Carve {
+    uint8_t *base;
+    uint64_t at = 0;
+    template <class T, class... R>
+    uint64_t take(uint64_t n, T *&p, R &...rest) {
+        p = base ? (T *)(base + at) : nullptr;
+        at += (n * sizeof(T) + 255u) & ~(uint64_t)255u;
+        if constexpr (sizeof...(rest) > 0) take(n, rest...);
+        return at;
+    }
+};
+
+// All or nothing: c->dec is set only once its allocation is there, so a call that fails here
+// leaves the context as it was and the next one tries again.
+int dec_scratch(flacgpu_ctx *c) {
+    if (c->dec) return FLACGPU_OK;
+    DecScratch *d = new (std::nothrow) DecScratch();
+    if (!d) return FLACGPU_ERR_OUT_OF_MEMORY;
+    auto carve = [&](uint8_t *base) {  // 8-byte members first
+        Carve v{base};
+        v.take(c->max_frames, d->samp_off, d->exp_off, d->exp_number, d->d_foff, d->d_results);
+        v.take(1, d->total);
+        v.take((uint64_t)c->max_frames * c->C, d->subs);
+        v.take(c->max_frames, d->blocks, d->body, d->exp_n, d->d_fbytes);
+        v.take(16, d->ctl);
+        return v.take(1, d->d_bad);
+    };
+    const hipError_t e = hipMalloc(&d->buf, carve(nullptr));
+    if (e != hipSuccess) {
+        delete d;
+        return hip_err(e);
+    }
+    carve(d->buf);
+    c->dec = d;  // freed by dec_release
+    return FLACGPU_OK;
+}
+
+IdxScratch *idx_scratch(flacgpu_ctx *c) {
+    if (!c->idx) c->idx = new (std::nothrow) IdxScratch();  // freed by dec_release
+    return c->idx;
+}
+
+// parse, (scan,) reconstruct of n frames, queued on st
+int dec_core(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff, const uint32_t *d_fbytes, uint32_t n,
+             const uint64_t *d_pcm_off, uint8_t *d_out, uint64_t cap, const uint8_t *d_expect, bool verify,
+             flacgpu_decode_result *d_results, uint32_t *d_bad, hipStream_t st) {
+    DecScratch *d = c->dec;
+    dec::Args a{};
+    a.frames = d_frames;
+    a.frame_off = d_foff;
+    a.frame_bytes = d_fbytes;
+    a.n_frames = n;
+    a.channels = c->C;
+    a.bits = c->bits;
+    a.bps = c->bits / 8u;
+    a.rate = c->cfg.sample_rate;
+    a.block = c->cfg.block_size;
+    a.subs = d->subs;
+    a.blocks = d->blocks;
+    a.body = d->body;
+    a.pcm_off = d_pcm_off;
+    a.samp_off = d->samp_off;
+    a.out = d_out;
+    a.cap = cap;
+    a.expect = d_expect;
+    a.exp_number = verify ? d->exp_number : nullptr;
+    a.exp_n = verify ? d->exp_n : nullptr;
+    a.results = (dec::Result *)d_results;
+    a.bad = d_bad ? d_bad : d->d_bad;
+    a.ticket = d->ctl;
+    {
+        Timed t(c, FLACGPU_K_DEC_PARSE, st);
+        HIPCHK(launch_dec_parse(a, st));
+    }
+    if (!d_pcm_off) {
+        // consecutive blocks of one stream: sample offsets from the scan of the parsed block sizes
+        HIPCHK(grow(c->d_scan_part, c->scan_part_cap, (n + 4095u) / 4096u, &st));
+        Timed t(c, FLACGPU_K_SCAN, st);
+        HIPCHK(launch_scan(d->blocks, d->samp_off, d->total, n, c->d_scan_part, st));
+    }
+    Timed t(c, FLACGPU_K_DEC_RECON, st);
+    HIPCHK(launch_dec_recon(a, st));
+    return FLACGPU_OK;
+}
+
+// the eight stages over [d_data, d_data + len), len > 0, queued on st
+int index_core(flacgpu_ctx *c, const uint8_t *d_data, uint64_t len, uint32_t stream_bits, uint32_t stream_rate,
+               uint64_t *d_off, uint32_t *d_bytes, uint64_t cap, idx::IndexResult *d_res, hipStream_t st) {
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
+    idx::IdxArgs g{};
+    g.data = d_data;
+    g.len = len;
+    g.lead = (uint32_t)((uintptr_t)d_data & 15u);
+    g.bits = stream_bits;
+    g.rate = stream_rate;
+    g.n_chunks = (g.lead + len + idx::kIdxChunk - 1u) / idx::kIdxChunk;
+    g.n_groups = (uint32_t)((g.n_chunks + idx::kIdxGroup - 1u) / idx::kIdxGroup);
+    g.spos_cap = std::min<uint64_t>(cap, len / 8u + 1u);  // a frame is at least 9 bytes
+    g.offs = d_off;
+    g.bytes = d_bytes;
+    g.cap = cap;
+    g.res = d_res;
+    auto carve = [&](uint8_t *base) {  // 8-byte members first
+        Carve v{base};
+        v.take(g.n_chunks, g.cmask, g.smask);
+        v.take(g.n_groups, g.grp, g.gcnt);
+        v.take(4, g.ctl);
+        v.take(g.spos_cap, g.spos);
+        return v.take(g.n_chunks, g.terms);
+    };
+    HIPCHK(grow(x->buf, x->cap, carve(nullptr), &st));  // an earlier index on this stream may still use the old one
+    carve(x->buf);
+    Timed t(c, FLACGPU_K_INDEX, st);
+    HIPCHK(launch_index(g, st));
+    return FLACGPU_OK;
+}
+
+// One chunk of a host-buffer decode on the context's stream: the n <= max_frames consecutive
+// frames of the table (d_foff, d_fbytes) into d_frames are decoded into the zeroed staging PCM (a
+// damaged frame leaves zeros), their results copied to `results`, their PCM to pcm_out + *written;
+// *written and *n_samples grow by the chunk's.  `overlap` runs on the host once the work is
+// queued, before the wait for it.
+template <class F>
+int decode_chunk(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff, const uint32_t *d_fbytes, uint32_t n,
+                 uint8_t *pcm_out, uint64_t pcm_cap, uint64_t *written, uint64_t *n_samples, dec::Result *results,
+                 F overlap) {
+    DecScratch *d = c->dec;
+    hipStream_t st = c->stream;
+    const uint64_t per = (uint64_t)c->C * (c->bits / 8u), need = (uint64_t)n * c->cfg.block_size * per;
+    HIPCHK(grow(d->d_pcm, d->pcm_cap, need));  // the chunk before this one was waited for
+    HIPCHK(hipMemsetAsync(d->d_pcm, 0, need, st));
+    const int rc = dec_core(c, d_frames, d_foff, d_fbytes, n, nullptr, d->d_pcm, need, nullptr, false,
+                            (flacgpu_decode_result *)d->d_results, nullptr, st);
+    if (rc) return rc;
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(results, d->d_results, (uint64_t)n * sizeof(dec::Result), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&total, d->total, 8, hipMemcpyDeviceToHost, st));
+    overlap();
+    HIPCHK(hipStreamSynchronize(st));
+    const uint64_t out_bytes = total * per;
+    if (out_bytes > need) return FLACGPU_ERR_INTERNAL;
+    if (*written + out_bytes > pcm_cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
+    if (out_bytes) HIPCHK(hipMemcpy(pcm_out + *written, d->d_pcm, out_bytes, hipMemcpyDeviceToHost));
+    *written += out_bytes;
+    *n_samples += total;
+    return FLACGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flacgpu_decode_frames_device(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_frame_offsets,
+                                 const uint32_t *d_frame_bytes, uint64_t n_frames, const uint64_t *d_pcm_offsets,
+                                 uint8_t *d_pcm_out, uint64_t pcm_cap, const uint8_t *d_pcm_expect,
+                                 flacgpu_decode_result *d_results, uint32_t *d_bad_count, void *hip_stream) {
+    if (!c || !d_frames || !d_frame_offsets || !d_frame_bytes || !d_results || !d_bad_count || n_frames > c->max_frames)
+        return FLACGPU_ERR_INVALID_INPUT;
+    HIPCHK(hipSetDevice(c->device));
+    const int rc = dec_scratch(c);
+    if (rc) return rc;
+    hipStream_t st = pick_stream(c, hip_stream);
+    if (n_frames == 0) {
+        HIPCHK(hipMemsetAsync(d_bad_count, 0, 4, st));
+        return FLACGPU_OK;
+    }
+    return dec_core(c, d_frames, d_frame_offsets, d_frame_bytes, (uint32_t)n_frames, d_pcm_offsets, d_pcm_out, pcm_cap,
+                    d_pcm_expect, false, d_results, d_bad_count, st);
+}
+
+int flacgpu_verify_plan_device(flacgpu_ctx *c, const flacgpu_plan *p, const void *d_pcm, const uint8_t *d_out,
+                               const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                               flacgpu_decode_result *d_results, uint32_t *d_bad_count, void *hip_stream) {
+    if (!c || !p || p->ctx != c || !d_pcm || !d_out || !d_frame_offsets || !d_frame_bytes || !d_results || !d_bad_count ||
+        p->n_frames > c->max_frames)
+        return FLACGPU_ERR_INVALID_INPUT;
+    HIPCHK(hipSetDevice(c->device));
+    const int rc = dec_scratch(c);
+    if (rc) return rc;
+    hipStream_t st = pick_stream(c, hip_stream);
+    if (p->n_frames == 0) {
+        HIPCHK(hipMemsetAsync(d_bad_count, 0, 4, st));
+        return FLACGPU_OK;
+    }
+    DecScratch *d = c->dec;
+    // the plan's frame table (full jobs, then tail jobs) by output slot
+    HIPCHK(launch_dec_expect(p->d_jobs, p->n_frames, d->exp_off, d->exp_number, d->exp_n, st));
+    return dec_core(c, d_out, d_frame_offsets, d_frame_bytes, (uint32_t)p->n_frames, d->exp_off, nullptr, 0,
+                    (const uint8_t *)d_pcm, true, d_results, d_bad_count, st);
+}
+
+int flacgpu_flac_index_device(flacgpu_ctx *c, const uint8_t *d_data, uint64_t len, uint32_t stream_bits,
+                              uint32_t stream_rate, uint64_t *d_frame_offsets, uint32_t *d_frame_bytes, uint64_t cap,
+                              flacgpu_index_result *d_result, void *hip_stream) {
+    if (!c || !d_data || !d_frame_offsets || !d_frame_bytes || !d_result || len > 0xFFFFFFFFull)
+        return FLACGPU_ERR_INVALID_INPUT;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = pick_stream(c, hip_stream);
+    if (len == 0) {  // no frames: OK, 0
+        HIPCHK(hipMemsetAsync(d_result, 0, sizeof(flacgpu_index_result), st));
+        return FLACGPU_OK;
+    }
+    return index_core(c, d_data, len, stream_bits, stream_rate, d_frame_offsets, d_frame_bytes, cap,
+                      (idx::IndexResult *)d_result, st);
+}
+
+// every chunk's frames and frame table are uploaded, its results land at results + f0
+int flacgpu_decode_frames(flacgpu_ctx *c, const uint8_t *frames, const uint32_t *frame_bytes, uint64_t n_frames,
+                          uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, flacgpu_decode_result *results) {
+    if (!c || !n_samples || !results || (n_frames && (!frames || !frame_bytes)) || (pcm_cap && !pcm_out))
+        return FLACGPU_ERR_INVALID_INPUT;
+    *n_samples = 0;
+    if (n_frames == 0) return FLACGPU_OK;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = dec_scratch(c);
+    if (rc) return rc;
+    DecScratch *d = c->dec;
+    hipStream_t st = c->stream;
+    std::vector<uint64_t> foff;
+    uint64_t src = 0, written = 0;
+    for (uint64_t f0 = 0; f0 < n_frames; f0 += c->max_frames) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(c->max_frames, n_frames - f0);
+        foff.assign(n, 0);
+        uint64_t bytes = 0;
+        for (uint32_t i = 0; i < n; i++) {
+            foff[i] = bytes;
+            bytes += frame_bytes[f0 + i];
+        }
+        HIPCHK(grow(d->d_frames, d->frames_cap, bytes + 16u));  // the chunk before this one was waited for
+        HIPCHK(hipMemcpyAsync(d->d_frames, frames + src, bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d->d_foff, foff.data(), (uint64_t)n * 8u, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(d->d_fbytes, frame_bytes + f0, (uint64_t)n * 4u, hipMemcpyHostToDevice, st));
+        rc = decode_chunk(c, d->d_frames, d->d_foff, d->d_fbytes, n, pcm_out, pcm_cap, &written, n_samples,
+                          (dec::Result *)results + f0, [] {});
+        if (rc) return rc;
+        src += bytes;
+    }
+    return FLACGPU_OK;
+}
+
+}  // extern "C"
+
+// The frames are uploaded once and indexed on the device, and every chunk's table is a slice of
+// that index; a chunk's PCM, once in pcm_out, is hashed while the next chunk decodes.  Returns 1
+// where the device index does not give a frame table (it refuses the stream, or its scratch cannot
+// be had): the caller then takes the host path, which names the error.
+int fg::decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate,
+                               uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, uint8_t digest[16]) {
+    if (len == 0 || len > 0xFFFFFFFFull) return 1;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = dec_scratch(c);
+    if (rc) return rc;
+    DecScratch *d = c->dec;
+    hipStream_t st = c->stream;
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return 1;
+    const uint64_t fcap = len / 8u + 1u;
+    uint64_t *f_off = nullptr;
+    uint32_t *f_bytes = nullptr;
+    idx::IndexResult *d_res = nullptr;
+    auto table = [&](uint8_t *base) {
+        Carve v{base};
+        v.take(fcap, f_off, f_bytes);
+        return v.take(1, d_res);
+    };
+    if (grow(x->table, x->table_cap, table(nullptr), &st) != hipSuccess) return 1;
+    table(x->table);
+    if (grow(d->d_frames, d->frames_cap, len + 16u, &st) != hipSuccess) return 1;
+    HIPCHK(hipMemcpyAsync(d->d_frames, p, len, hipMemcpyHostToDevice, st));
+    rc = index_core(c, d->d_frames, len, stream_bits, stream_rate, f_off, f_bytes, fcap, d_res, st);
+    if (rc == FLACGPU_ERR_OUT_OF_MEMORY) return 1;
+    if (rc) return rc;
+    idx::IndexResult ir{};
+    HIPCHK(hipMemcpyAsync(&ir, d_res, sizeof(ir), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (ir.status != idx::IDX_OK || ir.n_frames > fcap) return 1;
+    const uint64_t n_frames = ir.n_frames;
+    std::vector<dec::Result> res(c->max_frames);
+    HostMd5 md5;
+    uint64_t written = 0, hashed = 0;
+    bool damaged = false;
+    auto hash = [&] {
+        md5.update(pcm_out + hashed, (size_t)(written - hashed));
+        hashed = written;
+    };
+    for (uint64_t f0 = 0; f0 < n_frames; f0 += c->max_frames) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(c->max_frames, n_frames - f0);
+        rc = decode_chunk(c, d->d_frames, f_off + f0, f_bytes + f0, n, pcm_out, pcm_cap, &written, n_samples, res.data(),
+                          hash);
+        if (rc) return rc;
+        for (uint32_t i = 0; i < n; i++)
+            if (res[i].status) damaged = true;
+    }
+    if (damaged) return FLACGPU_ERR_INVALID_INPUT;  // a damaged frame: not a decodable file
+    hash();
+    md5.final(digest);
+    return FLACGPU_OK;
+}

@@ -37,4 +37,9 @@ CtxDevice ctx_device(const flacgpu_ctx *c);
 // the device's shared file pipeline (fg_file.cpp) instead of on its own streams.
 bool ctx_plain(const flacgpu_ctx *c);
 void ctx_finish(flacgpu_ctx *c);  // fold pending timing events
+// fg_dec_host.cpp, the device side of flacgpu_decode_file: the frames [p, p + len) uploaded once,
+// indexed and decoded on the device, the PCM to pcm_out, its MD5 to digest.  1 = no frame table
+// from the device index: the caller takes the host index and flacgpu_decode_frames.
+int decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate,
+                           uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, uint8_t digest[16]);
 }  // namespace fg
