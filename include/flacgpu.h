@@ -489,6 +489,59 @@ int flacgpu_flac_index_device(flacgpu_ctx *ctx, const uint8_t *d_data, uint64_t 
  * STREAMINFO's.  A damaged frame makes the call fail with FLACGPU_ERR_INVALID_INPUT. */
 int flacgpu_decode_file(flacgpu_ctx *ctx, const void *flac, size_t len, uint8_t *pcm_out, size_t pcm_cap,
                         uint64_t *n_samples, int *md5_ok);
+/* flacgpu_flac_index_device over n_streams (<= 65535, more: FLACGPU_ERR_INVALID_INPUT) bare runs of
+ * frames of one device buffer in one call: stream s is the stream_lens[s] (<= 2^32 - 1) bytes at
+ * d_data + stream_offsets[s], any alignment, with its own stream_bits[s] / stream_rates[s] (NULL:
+ * 16 / 0 for all).  It owns entries [table_first[s], + table_caps[s]) of d_frame_offsets[] and
+ * d_frame_bytes[] and d_results[s]; these are exactly what the single call leaves for that stream
+ * alone (a zero-length stream: OK, 0 frames), but the offsets are relative to d_data, so a slice
+ * feeds flacgpu_decode_frames_device with d_frames = d_data.  One stream's verdict touches no
+ * other stream's slice or result.  The five stream arrays are host memory.  The number of kernel
+ * launches does not depend on n_streams; the whole call is one timed launch of FLACGPU_K_INDEX.
+ * Asynchronous on hip_stream: one table of n_streams entries is copied to the device, and the
+ * host waits only when the context's index scratch (sized from the lengths and caps) has to grow. */
+int flacgpu_flac_index_streams_device(flacgpu_ctx *ctx, const uint8_t *d_data, uint32_t n_streams,
+                                      const uint64_t *stream_offsets, const uint64_t *stream_lens,
+                                      const uint32_t *stream_bits, const uint32_t *stream_rates,
+                                      const uint64_t *table_first, const uint64_t *table_caps,
+                                      uint64_t *d_frame_offsets, uint32_t *d_frame_bytes,
+                                      flacgpu_index_result *d_results, void *hip_stream);
+/* Index (the call above, into a table the context owns) and decode n_streams device-resident
+ * streams of the context's channel count and bit depth: stream s's PCM goes to the pcm_caps[s]
+ * bytes at d_pcm_out + pcm_offsets[s] (host arrays), each frame at the place its predecessors'
+ * block sizes give it.  All frames of all streams, in stream order, are cut into chunks of
+ * max_frames_per_call that run on from one stream into the next.  A frame whose region would pass
+ * its stream's capacity gets RANGE and writes nothing; a stream whose index is not OK decodes
+ * nothing.  d_results[s] (device memory) sums the stream up.  d_md5 (device, 16 * n_streams bytes,
+ * or NULL): the MD5 of every stream's decoded PCM by one batched device launch, 16 zero bytes for
+ * a stream with a bad index or a bad frame; it needs every pcm_offsets[s] to be a multiple of 4.
+ * The call waits for hip_stream ONCE, after the index, to read the frame counts; everything after
+ * that is only queued. */
+typedef struct {            /* 32 bytes, device memory */
+    uint64_t n_frames, n_samples;      /* interchannel samples of the frames with status 0 */
+    uint32_t index_status;             /* FLACGPU_INDEX_* */
+    uint32_t bad_frames;               /* frames with a non-zero status */
+    uint32_t first_bad_frame;          /* 0xFFFFFFFF: none */
+    uint32_t first_bad_status;         /* FLACGPU_DEC_* of that frame */
+} flacgpu_stream_result;
+int flacgpu_decode_streams_device(flacgpu_ctx *ctx, const uint8_t *d_data, uint32_t n_streams,
+                                  const uint64_t *stream_offsets, const uint64_t *stream_lens,
+                                  const uint32_t *stream_bits, const uint32_t *stream_rates,
+                                  uint8_t *d_pcm_out, const uint64_t *pcm_offsets, const uint64_t *pcm_caps,
+                                  flacgpu_stream_result *d_results, uint8_t *d_md5, void *hip_stream);
+/* flacgpu_decode_file for n_files (<= 65535) files in one call: status[i], n_samples[i], md5_ok[i]
+ * (md5_ok may be NULL) and the bytes at pcm_out[i] (capacity pcm_cap[i]) are what
+ * flacgpu_decode_file gives for file i alone on this context; one bad file (metadata, channel
+ * count or bit depth, a damaged frame, a capacity too small) does not fail the others, and the
+ * return value is for the call's own errors only.  All files' frames are uploaded into one device
+ * buffer and go through flacgpu_decode_streams_device; the MD5s are hashed in one batch by the
+ * engine flacgpu_md5_engine_for picks (the device kernel, or flacgpu_md5_many on the host pool).
+ * A file the batch does not decode cleanly goes through flacgpu_decode_file afterwards.  The
+ * whole batch is resident at once: a device allocation that fails returns
+ * FLACGPU_ERR_OUT_OF_MEMORY; splitting an oversized batch into groups of files is the caller's. */
+int flacgpu_decode_files(flacgpu_ctx *ctx, uint32_t n_files, const void *const *flac, const size_t *len,
+                         uint8_t *const *pcm_out, const size_t *pcm_cap, uint64_t *n_samples, int *md5_ok,
+                         int *status);
 
 /* ---- Instrumentation ---------------------------------------------------- */
 /* Kernel ids for flacgpu_kernel_time: frame analysis (4096-sample frames /

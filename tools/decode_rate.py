@@ -15,6 +15,14 @@ decode of the frames it found (the same way), and flacgpu_decode_file end to end
 
     python tools/decode_rate.py --out profiles/dec_rate.json --index-out profiles/index_rate.json
     python tools/decode_rate.py --legs index --index-out profiles/index_rate.json
+
+The files leg (--files-out) cuts the same C2 batch into 64 files of 256 frames: a loop of
+flacgpu_decode_file against one flacgpu_decode_files on the same context (wall clock, the two
+alternated, best of 3 each after one warm call each, the MD5 engine the batch chose recorded), and
+64 flacgpu_flac_index_device calls against one flacgpu_flac_index_streams_device over the same
+bytes in HBM (HIP events, warm-up, the median).
+
+    python tools/decode_rate.py --legs files --files-out profiles/decode_files_rate.json
 """
 import argparse
 import ctypes
@@ -216,6 +224,135 @@ def index_rate(frames: int, warmup: int, repeats: int) -> dict:
     return res
 
 
+def files_rate(n_files: int, frames_each: int, warmup: int, repeats: int) -> dict:
+    import numpy as np
+    import torch
+
+    import flacgpu
+    import synth
+
+    ch, bits, rate, _ = PRESETS["c2"]
+    per = ch * (bits // 8)
+    dev = torch.device("cuda", 0)
+    unit = synth.synth_pcm(64 * 4096, ch, bits, rate)
+    n_each = frames_each * 4096
+    pcm = (unit * ((frames_each + 63) // 64))[: n_each * per]
+    L = flacgpu.load_library()
+    with flacgpu.Encoder(ch, bits, rate, device=0, max_frames=n_files * frames_each) as enc:
+        flacs = enc.encode_files([pcm] * n_files)
+        first = flacgpu.flac_index(flacs[0])[1]
+        P = ctypes.c_void_p
+        srcs = [ctypes.create_string_buffer(f, len(f)) for f in flacs]
+        outs = [ctypes.create_string_buffer(len(pcm)) for _ in flacs]
+        a_src = (P * n_files)(*[ctypes.addressof(b) for b in srcs])
+        a_out = (P * n_files)(*[ctypes.addressof(b) for b in outs])
+        a_len = (ctypes.c_size_t * n_files)(*[len(f) for f in flacs])
+        a_cap = (ctypes.c_size_t * n_files)(*[len(pcm)] * n_files)
+        ns = (ctypes.c_uint64 * n_files)()
+        ok = (ctypes.c_int * n_files)()
+        status = (ctypes.c_int * n_files)()
+
+        def loop():
+            one_ns, one_ok = ctypes.c_uint64(0), ctypes.c_int(0)
+            t = time.perf_counter()
+            for i in range(n_files):
+                rc = L.flacgpu_decode_file(enc.ctx, srcs[i], len(flacs[i]), outs[i], len(pcm), ctypes.byref(one_ns),
+                                           ctypes.byref(one_ok))
+                assert rc == 0 and one_ok.value == 1 and one_ns.value == n_each
+            return time.perf_counter() - t
+
+        def batch():
+            t = time.perf_counter()
+            rc = L.flacgpu_decode_files(enc.ctx, n_files, a_src, a_len, a_out, a_cap, ns, ok, status)
+            dt = time.perf_counter() - t
+            assert rc == 0 and list(status) == [0] * n_files and list(ok) == [1] * n_files and list(ns) == [n_each] * n_files
+            return dt
+
+        loop()  # one warm call each: the allocations
+        batch()
+        assert all(o.raw == pcm for o in outs)
+        t_loop, t_batch = [], []
+        for _ in range(3):
+            t_loop.append(loop())
+            t_batch.append(batch())
+        engine = flacgpu.md5_engine_for(n_files, len(pcm), n_files * len(pcm))
+        total = n_files * n_each
+        res = {"files": n_files, "frames_per_file": frames_each, "channels": ch, "bits": bits,
+               "pcm_bytes": n_files * len(pcm), "flac_bytes": sum(len(f) for f in flacs),
+               "md5_engine": "device" if engine == flacgpu.MD5_DEVICE else "host",
+               "md5_rates": flacgpu.md5_rates().as_dict(),
+               "decode_file_loop": {"seconds_best_of_3": min(t_loop), "seconds": t_loop,
+                                    "msamples_per_s": total / min(t_loop) / 1e6},
+               "decode_files": {"seconds_best_of_3": min(t_batch), "seconds": t_batch,
+                                "msamples_per_s": total / min(t_batch) / 1e6}}
+        res["decode_files"]["x_loop"] = min(t_loop) / min(t_batch)
+
+        # the index alone: the files' frames in one HBM buffer, each at a 64-byte aligned offset
+        bodies = [f[first:] for f in flacs]
+        offs, at = [], 0
+        for b in bodies:
+            offs.append(at)
+            at += (len(b) + 63) & ~63
+        host = np.zeros(at + 16, dtype=np.uint8)
+        for o, b in zip(offs, bodies):
+            host[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        d_buf = torch.from_numpy(host).to(dev)
+        caps = [len(b) // 8 + 1 for b in bodies]
+        tfirst = [int(v) for v in np.cumsum([0] + caps)[:-1]]
+        d_off = torch.zeros(sum(caps), dtype=torch.int64, device=dev)
+        d_fb = torch.zeros(sum(caps), dtype=torch.int32, device=dev)
+        d_ir = torch.zeros(16 * n_files, dtype=torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        lens = [len(b) for b in bodies]
+        # the host arrays of the batched call, built once: the timed region is the C call
+        u64 = lambda v: (ctypes.c_uint64 * len(v))(*v)  # noqa: E731
+        h_offs, h_lens, h_first, h_caps = u64(offs), u64(lens), u64(tfirst), u64(caps)
+        h_bits, h_rates = (ctypes.c_uint32 * n_files)(*[bits] * n_files), (ctypes.c_uint32 * n_files)(*[rate] * n_files)
+        stream = flacgpu._stream(st)
+
+        def singles():
+            for i in range(n_files):
+                rc = L.flacgpu_flac_index_device(enc.ctx, d_buf.data_ptr() + offs[i], lens[i], bits, rate,
+                                                 d_off.data_ptr() + 8 * tfirst[i], d_fb.data_ptr() + 4 * tfirst[i], caps[i],
+                                                 d_ir.data_ptr() + 16 * i, stream)
+                assert rc == 0
+
+        def batched():
+            rc = L.flacgpu_flac_index_streams_device(enc.ctx, d_buf.data_ptr(), n_files, h_offs, h_lens, h_bits, h_rates,
+                                                     h_first, h_caps, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(),
+                                                     stream)
+            assert rc == 0
+
+        def timed(fn):
+            for _ in range(warmup):
+                fn()
+            enc.sync_check(st)
+            ms = []
+            for _ in range(repeats):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                ms.append(a.elapsed_time(b))
+            return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
+
+        def counts():
+            raw = d_ir.cpu().numpy().tobytes()
+            return [(r.status, r.n_frames) for r in (flacgpu.IndexResult * n_files).from_buffer_copy(raw)]
+
+        res["index_singles"] = timed(singles)
+        assert counts() == [(0, frames_each)] * n_files
+        table = d_fb.cpu().numpy().copy()
+        d_fb.zero_()
+        d_ir.zero_()
+        res["index_streams"] = timed(batched)
+        assert counts() == [(0, frames_each)] * n_files and (d_fb.cpu().numpy() == table).all()
+        res["index_streams"]["x_singles"] = res["index_singles"]["ms_median"] / res["index_streams"]["ms_median"]
+        res["index_bytes"] = sum(lens)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dec_rate.json"))
@@ -223,9 +360,19 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--legs", choices=("all", "decode", "index"), default="all")
+    ap.add_argument("--legs", choices=("all", "decode", "index", "files"), default="all")
+    ap.add_argument("--files-out", default=os.path.join(ROOT, "profiles", "decode_files_rate.json"))
+    ap.add_argument("--files", type=int, default=64)
     ap.add_argument("--index-out", default=os.path.join(ROOT, "profiles", "index_rate.json"))
     a = ap.parse_args()
+    if a.legs in ("all", "files"):
+        fr = {"c2": files_rate(a.files, a.frames // a.files, a.warmup, a.repeats)}
+        print(json.dumps({"files": fr}), flush=True)
+        with open(a.files_out, "w") as f:
+            json.dump(fr, f, indent=1)
+            f.write("\n")
+        if a.legs == "files":
+            return
     if a.legs != "decode":
         idx = {"c2": index_rate(a.frames, a.warmup, a.repeats)}
         print(json.dumps({"index": idx}), flush=True)

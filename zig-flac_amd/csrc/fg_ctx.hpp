@@ -147,9 +147,15 @@ namespace fg {
 
 namespace dec {
 struct Args;
+struct Result;
 }
 namespace idx {
 struct IdxArgs;
+struct IndexResult;
+}
+namespace streams {
+struct Segment;
+struct StreamResult;
 }
 
 // shared by the translation units that include this header, not exported from libflacgpu.so
@@ -168,6 +174,23 @@ hipError_t launch_dec_expect(const FrameJob *jobs, uint64_t n, uint64_t *pcm_off
                              hipStream_t st);
 // fg_index.hip
 hipError_t launch_index(const idx::IdxArgs &g, hipStream_t st);
+hipError_t launch_index_streams(const idx::IdxArgs *d_tab, uint32_t n, uint32_t max_groups, uint64_t max_spos,
+                                hipStream_t st);
+// fg_dec_streams.hip
+hipError_t launch_streams_init(const idx::IndexResult *ires, streams::StreamResult *res, uint64_t *carried, uint32_t n,
+                               hipStream_t st);
+hipError_t launch_streams_gather(const streams::Segment *segs, uint32_t n_segs, const uint64_t *table_first,
+                                 const uint64_t *f_off, const uint32_t *f_bytes, uint64_t *p_off, uint32_t *p_bytes,
+                                 hipStream_t st);
+hipError_t launch_seg_offsets(const streams::Segment *segs, uint32_t n_segs, const uint32_t *blocks, const uint64_t *pcm_base,
+                              const uint64_t *pcm_cap, uint64_t *carried, uint32_t per, uint64_t *pcm_off, hipStream_t st);
+hipError_t launch_seg_fold(const streams::Segment *segs, uint32_t n_segs, const dec::Result *results,
+                           streams::StreamResult *res, hipStream_t st);
+hipError_t launch_streams_md5_lens(const streams::StreamResult *res, uint32_t per, uint64_t *lens, uint32_t n, hipStream_t st);
+hipError_t launch_streams_md5_mask(const streams::StreamResult *res, uint8_t *digests, uint32_t n, hipStream_t st);
+// fg_misc.hip
+hipError_t launch_md5_streams(const uint8_t *base, const uint64_t *offs, const uint64_t *lens, const uint8_t *fin,
+                              uint32_t n, Md5State *states, uint8_t *digests, hipStream_t st, int kernel, int prio);
 
 struct FG_LOCAL Timed {
     flacgpu_ctx *c;

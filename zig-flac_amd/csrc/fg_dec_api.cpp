@@ -1,7 +1,8 @@
 // fg_dec_api.cpp -- the host-only side of the decoder's C ABI: the frame index of a FLAC file or
 // of a bare run of frames (no GPU), and the whole-file decode: metadata here, the frames through
 // the device index and decode (fg_dec_host.cpp decode_stream_resident), or, where the device index
-// refuses them, through the host index and flacgpu_decode_frames.  Plain C++ over
+// refuses them, through the host index and flacgpu_decode_frames; flacgpu_decode_files does the
+// same for many files through one batch (fg_dec_host.cpp decode_files_resident).  Plain C++ over
 // include/flacgpu.h and the shared decode core.
 #include <cstring>
 #include <vector>
@@ -151,6 +152,66 @@ int flacgpu_decode_file(flacgpu_ctx *ctx, const void *flac, size_t len, uint8_t 
     if (md5_ok)
         *md5_ok = std::memcmp(digest, si.md5, 16) == 0 &&
                   (si.interchannel_samples == 0 || si.interchannel_samples == *n_samples);
+    return FLACGPU_OK;
+}
+
+// The files whose metadata and stream parameters are good go through the device in one batch
+// (fg_dec_host.cpp decode_files_resident); a file that is not clean there is decoded again by
+// flacgpu_decode_file, so its status, sample count and bytes are the single-file ones.
+int flacgpu_decode_files(flacgpu_ctx *ctx, uint32_t n_files, const void *const *flac, const size_t *len,
+                         uint8_t *const *pcm_out, const size_t *pcm_cap, uint64_t *n_samples, int *md5_ok, int *status) {
+    if (!ctx || (n_files && (!flac || !len || !pcm_out || !pcm_cap || !n_samples || !status)))
+        return FLACGPU_ERR_INVALID_INPUT;
+    if (n_files == 0) return FLACGPU_OK;
+    flacgpu_config cfg;
+    int rc = flacgpu_get_config(ctx, &cfg);
+    if (rc) return rc;
+    std::vector<flacgpu_streaminfo> si(n_files);
+    std::vector<uint32_t> which, bits, rates;  // the batch: file index, STREAMINFO's depth and rate
+    std::vector<const uint8_t *> ptr;
+    std::vector<size_t> lens, caps;
+    std::vector<uint8_t *> outs;
+    for (uint32_t i = 0; i < n_files; i++) {
+        n_samples[i] = 0;
+        if (md5_ok) md5_ok[i] = 0;
+        size_t first = 0;
+        if (!flac[i] || (pcm_cap[i] && !pcm_out[i])) {
+            status[i] = FLACGPU_ERR_INVALID_INPUT;
+            continue;
+        }
+        const uint8_t *p = (const uint8_t *)flac[i];
+        status[i] = parse_metadata(p, len[i], &si[i], &first);
+        if (status[i]) continue;
+        if (si[i].channels != cfg.channels || si[i].bit_depth != cfg.bits_per_sample) {
+            status[i] = FLACGPU_ERR_INVALID_INPUT;
+            continue;
+        }
+        which.push_back(i);
+        bits.push_back(si[i].bit_depth);
+        rates.push_back(si[i].sample_rate);
+        ptr.push_back(p + first);
+        lens.push_back(len[i] - first);
+        outs.push_back(pcm_out[i]);
+        caps.push_back(pcm_cap[i]);
+    }
+    const uint32_t nb = (uint32_t)which.size();
+    std::vector<uint64_t> ns(nb, 0);
+    std::vector<uint8_t> digests(16u * (size_t)nb + 1u), single(nb + 1u, 0);
+    rc = decode_files_resident(ctx, nb, ptr.data(), lens.data(), bits.data(), rates.data(), outs.data(), caps.data(),
+                               ns.data(), digests.data(), single.data());
+    if (rc) return rc;
+    for (uint32_t k = 0; k < nb; k++) {
+        const uint32_t i = which[k];
+        if (single[k]) {
+            status[i] = flacgpu_decode_file(ctx, flac[i], len[i], pcm_out[i], pcm_cap[i], &n_samples[i],
+                                            md5_ok ? &md5_ok[i] : nullptr);
+            continue;
+        }
+        n_samples[i] = ns[k];
+        if (md5_ok)
+            md5_ok[i] = std::memcmp(&digests[16u * (size_t)k], si[i].md5, 16) == 0 &&
+                        (si[i].interchannel_samples == 0 || si[i].interchannel_samples == ns[k]);
+    }
     return FLACGPU_OK;
 }
 

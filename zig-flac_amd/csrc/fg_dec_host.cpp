@@ -1,7 +1,9 @@
 // fg_dec_host.cpp -- the device-driving side of the decoder's C ABI: the frame decoder / verifier
 // (fg_dec.hpp, fg_dec.hip) and the device frame index (fg_index.hpp, fg_index.hip) over device
-// memory, the host-buffer decode, and the device side of the whole-file decode.  The host-only
-// side (metadata, the host index, flacgpu_decode_file) is fg_dec_api.cpp.
+// memory, the host-buffer decode, and the device side of the whole-file decode; and their
+// many-streams forms: the index of n streams in one call, decode chunks that span streams
+// (fg_streams.hpp, fg_dec_streams.hip), and the device side of flacgpu_decode_files.  The
+// host-only side (metadata, the host index, flacgpu_decode_file / _files) is fg_dec_api.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,11 +15,13 @@
 #include "fg_dec.hpp"
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
+#include "fg_streams.hpp"
 
 using namespace fg;
 
 static_assert(sizeof(dec::Result) == sizeof(flacgpu_decode_result), "decode result layout");
 static_assert(sizeof(idx::IndexResult) == sizeof(flacgpu_index_result), "index result layout");
+static_assert(sizeof(streams::StreamResult) == sizeof(flacgpu_stream_result), "stream result layout");
 static_assert(FLACGPU_INDEX_INVALID == (int)idx::IDX_INVALID && FLACGPU_INDEX_TOO_SMALL == (int)idx::IDX_TOO_SMALL,
               "index status codes");
 
@@ -37,16 +41,18 @@ struct DecScratch {
 
 // Index scratch of a context, grow-only: the arrays of idx::IdxArgs, sized from the call's len and
 // cap; and the frame table and result of the whole-file decode, which indexes the file it uploaded.
+// The many-streams decode adds the packed frame table with the per-stream arrays and segment table
+// of a call (packed), and the per-file results and digests of flacgpu_decode_files (files).
 struct IdxScratch {
-    uint8_t *buf = nullptr, *table = nullptr;
-    uint64_t cap = 0, table_cap = 0;
+    uint8_t *buf = nullptr, *table = nullptr, *packed = nullptr, *files = nullptr;
+    uint64_t cap = 0, table_cap = 0, packed_cap = 0, files_cap = 0;
 };
 
 void fg::dec_release(flacgpu_ctx *c) {
     if (DecScratch *d = c->dec)
         for (uint8_t *b : {d->buf, d->d_frames, d->d_pcm}) hipFree(b);
     if (IdxScratch *x = c->idx)
-        for (uint8_t *b : {x->buf, x->table}) hipFree(b);
+        for (uint8_t *b : {x->buf, x->table, x->packed, x->files}) hipFree(b);
     delete c->dec;
     delete c->idx;
     c->dec = nullptr;
@@ -100,11 +106,23 @@ IdxScratch *idx_scratch(flacgpu_ctx *c) {
     return c->idx;
 }
 
-// parse, (scan,) reconstruct of n frames, queued on st
+// a chunk that holds frames of several streams: its segments and the per-stream arrays (device)
+struct ChunkStreams {
+    const streams::Segment *segs;
+    uint32_t n_segs;
+    const uint64_t *pcm_base, *pcm_cap;
+    uint64_t *carried;
+    streams::StreamResult *res;
+};
+
+// parse, (scan / segment offsets,) reconstruct(, fold) of n frames, queued on st.  The PCM offsets:
+// d_pcm_off per frame; or NULL and no `cs`: consecutive blocks of one stream; or `cs`: frames of
+// several streams, offsets from the segments (the verify arrays' exp_off holds them).
 int dec_core(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff, const uint32_t *d_fbytes, uint32_t n,
              const uint64_t *d_pcm_off, uint8_t *d_out, uint64_t cap, const uint8_t *d_expect, bool verify,
-             flacgpu_decode_result *d_results, uint32_t *d_bad, hipStream_t st) {
+             flacgpu_decode_result *d_results, uint32_t *d_bad, hipStream_t st, const ChunkStreams *cs = nullptr) {
     DecScratch *d = c->dec;
+    if (cs) d_pcm_off = d->exp_off;
     dec::Args a{};
     a.frames = d_frames;
     a.frame_off = d_foff;
@@ -132,14 +150,21 @@ int dec_core(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff, co
         Timed t(c, FLACGPU_K_DEC_PARSE, st);
         HIPCHK(launch_dec_parse(a, st));
     }
-    if (!d_pcm_off) {
+    if (cs) {
+        Timed t(c, FLACGPU_K_SCAN, st);
+        HIPCHK(launch_seg_offsets(cs->segs, cs->n_segs, d->blocks, cs->pcm_base, cs->pcm_cap, cs->carried, c->C * a.bps,
+                                  d->exp_off, st));
+    } else if (!d_pcm_off) {
         // consecutive blocks of one stream: sample offsets from the scan of the parsed block sizes
         HIPCHK(grow(c->d_scan_part, c->scan_part_cap, (n + 4095u) / 4096u, &st));
         Timed t(c, FLACGPU_K_SCAN, st);
         HIPCHK(launch_scan(d->blocks, d->samp_off, d->total, n, c->d_scan_part, st));
     }
-    Timed t(c, FLACGPU_K_DEC_RECON, st);
-    HIPCHK(launch_dec_recon(a, st));
+    {
+        Timed t(c, FLACGPU_K_DEC_RECON, st);
+        HIPCHK(launch_dec_recon(a, st));
+    }
+    if (cs) HIPCHK(launch_seg_fold(cs->segs, cs->n_segs, a.results, cs->res, st));
     return FLACGPU_OK;
 }
 
@@ -150,16 +175,11 @@ int index_core(flacgpu_ctx *c, const uint8_t *d_data, uint64_t len, uint32_t str
     if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
     idx::IdxArgs g{};
     g.data = d_data;
-    g.len = len;
-    g.lead = (uint32_t)((uintptr_t)d_data & 15u);
+    idx::stream_geometry(g, (uint64_t)(uintptr_t)d_data, len, cap);
     g.bits = stream_bits;
     g.rate = stream_rate;
-    g.n_chunks = (g.lead + len + idx::kIdxChunk - 1u) / idx::kIdxChunk;
-    g.n_groups = (uint32_t)((g.n_chunks + idx::kIdxGroup - 1u) / idx::kIdxGroup);
-    g.spos_cap = std::min<uint64_t>(cap, len / 8u + 1u);  // a frame is at least 9 bytes
     g.offs = d_off;
     g.bytes = d_bytes;
-    g.cap = cap;
     g.res = d_res;
     auto carve = [&](uint8_t *base) {  // 8-byte members first
         Carve v{base};
@@ -173,6 +193,175 @@ int index_core(flacgpu_ctx *c, const uint8_t *d_data, uint64_t len, uint32_t str
     carve(x->buf);
     Timed t(c, FLACGPU_K_INDEX, st);
     HIPCHK(launch_index(g, st));
+    return FLACGPU_OK;
+}
+
+// The eight stages, once, over n streams of one device buffer (0 < n <= kIdxMaxStreams, every
+// length < 2^32): stream s owns entries [table_first[s], + table_caps[s]) of the two tables and
+// d_res[s].  One table of n IdxArgs goes to the device; the host waits only where the scratch grows.
+int index_streams_core(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const uint64_t *offs, const uint64_t *lens,
+                       const uint32_t *bits, const uint32_t *rates, const uint64_t *table_first, const uint64_t *table_caps,
+                       uint64_t *d_off, uint32_t *d_bytes, idx::IndexResult *d_res, hipStream_t st) {
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
+    std::vector<idx::IdxArgs> tab;
+    try {
+        tab.assign(n, idx::IdxArgs{});
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    idx::IdxTotals tot;
+    for (uint32_t s = 0; s < n; s++) {
+        idx::IdxArgs &g = tab[s];
+        g.data = d_data + offs[s];
+        idx::stream_geometry(g, (uint64_t)(uintptr_t)g.data, lens[s], table_caps[s]);
+        g.bits = bits ? bits[s] : 16u;
+        g.rate = rates ? rates[s] : 0u;
+        g.offs = d_off + table_first[s];
+        g.bytes = d_bytes + table_first[s];
+        g.res = d_res + s;
+        g.base_off = offs[s];
+        idx::totals_add(tot, g);
+    }
+    idx::IdxPool pool{};
+    idx::IdxArgs *d_tab = nullptr;
+    auto carve = [&](uint8_t *base) {  // 8-byte members first
+        Carve v{base};
+        v.take(tot.chunks, pool.cmask, pool.smask);
+        v.take(n, d_tab);
+        v.take(tot.groups, pool.grp, pool.gcnt);
+        v.take(4u * (uint64_t)n, pool.ctl);
+        v.take(tot.spos, pool.spos);
+        return v.take(tot.chunks, pool.terms);
+    };
+    HIPCHK(grow(x->buf, x->cap, carve(nullptr), &st));  // an earlier index on this stream may still use the old one
+    carve(x->buf);
+    idx::IdxTotals at;
+    for (uint32_t s = 0; s < n; s++) idx::carve_stream(tab[s], pool, at);
+    HIPCHK(hipMemcpyAsync(d_tab, tab.data(), (uint64_t)n * sizeof(idx::IdxArgs), hipMemcpyHostToDevice, st));
+    Timed t(c, FLACGPU_K_INDEX, st);
+    HIPCHK(launch_index_streams(d_tab, n, tot.max_groups, tot.max_spos, st));
+    return FLACGPU_OK;
+}
+
+bool streams_args_ok(uint32_t n, const uint64_t *lens) {
+    if (n > idx::kIdxMaxStreams) return false;
+    for (uint32_t s = 0; s < n; s++)
+        if (lens[s] > 0xFFFFFFFFull) return false;
+    return true;
+}
+
+// The frame tables of a many-streams decode, in the context's index scratch: stream s owns
+// lens[s] / 8 + 1 entries (a frame is at least 9 bytes) from first[s].
+struct StreamTables {
+    std::vector<uint64_t> first, caps;
+    uint64_t *f_off = nullptr;
+    uint32_t *f_bytes = nullptr;
+    idx::IndexResult *d_ires = nullptr;
+};
+
+// Index all streams into the context's table, wait for hip_stream once, and leave the index
+// results in `ires`.
+int streams_index(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const uint64_t *offs, const uint64_t *lens,
+                  const uint32_t *bits, const uint32_t *rates, StreamTables &tb, std::vector<idx::IndexResult> &ires,
+                  hipStream_t st) {
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
+    uint64_t total = 0;
+    try {
+        tb.first.resize(n);
+        tb.caps.resize(n);
+        ires.resize(n);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    for (uint32_t s = 0; s < n; s++) {
+        tb.first[s] = total;
+        tb.caps[s] = lens[s] / 8u + 1u;
+        total += tb.caps[s];
+    }
+    auto table = [&](uint8_t *base) {
+        Carve v{base};
+        v.take(total, tb.f_off);
+        v.take(n, tb.d_ires);
+        return v.take(total, tb.f_bytes);
+    };
+    HIPCHK(grow(x->table, x->table_cap, table(nullptr), &st));
+    table(x->table);
+    const int rc = index_streams_core(c, d_data, n, offs, lens, bits, rates, tb.first.data(), tb.caps.data(), tb.f_off,
+                                      tb.f_bytes, tb.d_ires, st);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(ires.data(), tb.d_ires, (uint64_t)n * sizeof(idx::IndexResult), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FLACGPU_OK;
+}
+
+// Everything after the index of a many-streams decode, only queued: the streams' results set up,
+// the frame tables of the OK streams packed, every chunk of max_frames frames through parse,
+// segment offsets, reconstruct and fold, then (d_md5) one batched MD5 over the decoded regions.
+int streams_decode(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const StreamTables &tb,
+                   const std::vector<idx::IndexResult> &ires, uint8_t *d_pcm_out, const uint64_t *pcm_offsets,
+                   const uint64_t *pcm_caps, streams::StreamResult *d_results, uint8_t *d_md5, hipStream_t st) {
+    DecScratch *d = c->dec;
+    IdxScratch *x = c->idx;
+    std::vector<uint64_t> frames, host;
+    std::vector<streams::Segment> segs;
+    std::vector<uint32_t> chunk_seg;
+    uint64_t whole = 0;  // the capacity k_dec_recon checks: the end of the last region
+    try {
+        frames.assign(n, 0);
+        for (uint32_t s = 0; s < n; s++) {
+            if (ires[s].status == idx::IDX_OK && ires[s].n_frames <= tb.caps[s]) frames[s] = ires[s].n_frames;
+            whole = std::max(whole, pcm_offsets[s] + pcm_caps[s]);
+        }
+        streams::cut_segments(frames, c->max_frames, segs, chunk_seg);
+        host.resize(3u * (uint64_t)n);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    const uint32_t n_chunks = chunk_seg.empty() ? 0u : (uint32_t)chunk_seg.size() - 1u;
+    const uint64_t n_packed = (uint64_t)n_chunks * c->max_frames;
+    uint64_t *p_off = nullptr, *meta = nullptr, *carried = nullptr, *md5_lens = nullptr;
+    uint32_t *p_bytes = nullptr;
+    streams::Segment *d_segs = nullptr;
+    auto carve = [&](uint8_t *base) {
+        Carve v{base};
+        v.take(n_packed, p_off);
+        v.take(3u * (uint64_t)n, meta);  // pcm base, pcm cap, table first: one upload
+        v.take(n, carried, md5_lens);
+        v.take(segs.size(), d_segs);
+        return v.take(n_packed, p_bytes);
+    };
+    HIPCHK(grow(x->packed, x->packed_cap, carve(nullptr), &st));
+    carve(x->packed);
+    uint64_t *d_base = meta, *d_cap = meta + n, *d_first = meta + 2u * (uint64_t)n;
+    for (uint32_t s = 0; s < n; s++) {
+        host[s] = pcm_offsets[s];
+        host[n + s] = pcm_caps[s];
+        host[2u * (uint64_t)n + s] = tb.first[s];
+    }
+    HIPCHK(hipMemcpyAsync(meta, host.data(), host.size() * 8u, hipMemcpyHostToDevice, st));
+    if (!segs.empty())
+        HIPCHK(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(streams::Segment), hipMemcpyHostToDevice, st));
+    HIPCHK(launch_streams_init(tb.d_ires, d_results, carried, n, st));
+    HIPCHK(launch_streams_gather(d_segs, (uint32_t)segs.size(), d_first, tb.f_off, tb.f_bytes, p_off, p_bytes, st));
+    for (uint32_t k = 0; k < n_chunks; k++) {
+        const uint32_t s0 = chunk_seg[k], s1 = chunk_seg[k + 1u];
+        const uint32_t nf = segs[s1 - 1u].first + segs[s1 - 1u].count;
+        const ChunkStreams cs{d_segs + s0, s1 - s0, d_base, d_cap, carried, d_results};
+        const int rc = dec_core(c, d_data, p_off + (uint64_t)k * c->max_frames, p_bytes + (uint64_t)k * c->max_frames, nf,
+                                nullptr, d_pcm_out, whole, nullptr, false, (flacgpu_decode_result *)d->d_results, nullptr,
+                                st, &cs);
+        if (rc) return rc;
+    }
+    if (d_md5) {
+        HIPCHK(launch_streams_md5_lens(d_results, c->C * (c->bits / 8u), md5_lens, n, st));
+        {
+            Timed t(c, FLACGPU_K_MD5, st);
+            HIPCHK(launch_md5_streams(d_pcm_out, d_base, md5_lens, nullptr, n, nullptr, d_md5, st, c->md5_kernel, c->md5_prio));
+        }
+        HIPCHK(launch_streams_md5_mask(d_results, d_md5, n, st));
+    }
     return FLACGPU_OK;
 }
 
@@ -265,6 +454,45 @@ int flacgpu_flac_index_device(flacgpu_ctx *c, const uint8_t *d_data, uint64_t le
                       (idx::IndexResult *)d_result, st);
 }
 
+int flacgpu_flac_index_streams_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams,
+                                      const uint64_t *stream_offsets, const uint64_t *stream_lens,
+                                      const uint32_t *stream_bits, const uint32_t *stream_rates,
+                                      const uint64_t *table_first, const uint64_t *table_caps, uint64_t *d_frame_offsets,
+                                      uint32_t *d_frame_bytes, flacgpu_index_result *d_results, void *hip_stream) {
+    if (!c || !d_data || !stream_offsets || !stream_lens || !table_first || !table_caps || !d_frame_offsets ||
+        !d_frame_bytes || !d_results || !streams_args_ok(n_streams, stream_lens))
+        return FLACGPU_ERR_INVALID_INPUT;
+    if (n_streams == 0) return FLACGPU_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return index_streams_core(c, d_data, n_streams, stream_offsets, stream_lens, stream_bits, stream_rates, table_first,
+                              table_caps, d_frame_offsets, d_frame_bytes, (idx::IndexResult *)d_results,
+                              pick_stream(c, hip_stream));
+}
+
+int flacgpu_decode_streams_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *stream_offsets,
+                                  const uint64_t *stream_lens, const uint32_t *stream_bits, const uint32_t *stream_rates,
+                                  uint8_t *d_pcm_out, const uint64_t *pcm_offsets, const uint64_t *pcm_caps,
+                                  flacgpu_stream_result *d_results, uint8_t *d_md5, void *hip_stream) {
+    if (!c || !d_data || !stream_offsets || !stream_lens || !d_pcm_out || !pcm_offsets || !pcm_caps || !d_results ||
+        !streams_args_ok(n_streams, stream_lens))
+        return FLACGPU_ERR_INVALID_INPUT;
+    for (uint32_t s = 0; s < n_streams; s++) {
+        if (pcm_offsets[s] + pcm_caps[s] < pcm_offsets[s]) return FLACGPU_ERR_INVALID_INPUT;
+        if (d_md5 && (pcm_offsets[s] & 3u)) return FLACGPU_ERR_INVALID_INPUT;  // the MD5 kernel loads words
+    }
+    if (n_streams == 0) return FLACGPU_OK;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = dec_scratch(c);
+    if (rc) return rc;
+    hipStream_t st = pick_stream(c, hip_stream);
+    StreamTables tb;
+    std::vector<idx::IndexResult> ires;
+    rc = streams_index(c, d_data, n_streams, stream_offsets, stream_lens, stream_bits, stream_rates, tb, ires, st);
+    if (rc) return rc;
+    return streams_decode(c, d_data, n_streams, tb, ires, d_pcm_out, pcm_offsets, pcm_caps, (streams::StreamResult *)d_results,
+                          d_md5, st);
+}
+
 // every chunk's frames and frame table are uploaded, its results land at results + f0
 int flacgpu_decode_frames(flacgpu_ctx *c, const uint8_t *frames, const uint32_t *frame_bytes, uint64_t n_frames,
                           uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, flacgpu_decode_result *results) {
@@ -355,5 +583,103 @@ int fg::decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uin
     if (damaged) return FLACGPU_ERR_INVALID_INPUT;  // a damaged frame: not a decodable file
     hash();
     md5.final(digest);
+    return FLACGPU_OK;
+}
+
+// The device side of flacgpu_decode_files.  All files' frames go into one device buffer, each at a
+// 64-byte aligned offset, and are indexed in one call; the PCM regions are then sized from every
+// file's frame count and capacity, and all frames decode in chunks that run on from one file into
+// the next.  The MD5 engine is flacgpu_md5_engine_for's choice for the batch: the device kernel over
+// the decoded regions, or the host pool over the downloaded PCM.  take_single[i] = 1: the file is
+// not clean here (the index refuses it, a frame is damaged or passes the capacity): the caller
+// puts it through the single-file path, which names the error.
+int fg::decode_files_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *p, const size_t *len, const uint32_t *bits,
+                              const uint32_t *rates, uint8_t *const *pcm_out, const size_t *pcm_cap, uint64_t *n_samples,
+                              uint8_t *digests, uint8_t *take_single) {
+    if (n == 0) return FLACGPU_OK;
+    if (n > idx::kIdxMaxStreams) return FLACGPU_ERR_INVALID_INPUT;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = dec_scratch(c);
+    if (rc) return rc;
+    DecScratch *d = c->dec;
+    hipStream_t st = c->stream;
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
+    const uint64_t per = (uint64_t)c->C * (c->bits / 8u);
+    std::vector<uint64_t> offs, lens, pcm_offs, pcm_caps;
+    std::vector<idx::IndexResult> ires;
+    std::vector<streams::StreamResult> res;
+    StreamTables tb;
+    try {
+        offs.resize(n);
+        lens.resize(n);
+        pcm_offs.resize(n);
+        pcm_caps.resize(n);
+        res.resize(n);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (len[i] > 0xFFFFFFFFull) return FLACGPU_ERR_INVALID_INPUT;
+        offs[i] = total;
+        lens[i] = len[i];
+        total += (len[i] + 63u) & ~(uint64_t)63u;
+    }
+    HIPCHK(grow(d->d_frames, d->frames_cap, total + 16u, &st));
+    for (uint32_t i = 0; i < n; i++)
+        if (len[i]) HIPCHK(hipMemcpyAsync(d->d_frames + offs[i], p[i], len[i], hipMemcpyHostToDevice, st));
+    rc = streams_index(c, d->d_frames, n, offs.data(), lens.data(), bits, rates, tb, ires, st);
+    if (rc) return rc;
+    // the regions: what the file's frames can hold at most, cut to the caller's capacity
+    uint64_t pcm_total = 0, longest = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const bool ok = ires[i].status == idx::IDX_OK && ires[i].n_frames <= tb.caps[i];
+        const uint64_t most = ok ? ires[i].n_frames * c->cfg.block_size * per : 0u;
+        pcm_offs[i] = pcm_total;
+        pcm_caps[i] = std::min<uint64_t>(most, pcm_cap[i]);
+        pcm_total += (pcm_caps[i] + 63u) & ~(uint64_t)63u;
+        longest = std::max(longest, pcm_caps[i]);
+    }
+    const bool device_md5 = flacgpu_md5_engine_for(n, longest, pcm_total) == FLACGPU_MD5_DEVICE;
+    HIPCHK(grow(d->d_pcm, d->pcm_cap, pcm_total + 16u, &st));
+    streams::StreamResult *d_res = nullptr;
+    uint8_t *d_dig = nullptr;
+    auto carve = [&](uint8_t *base) {
+        Carve v{base};
+        v.take(n, d_res);
+        return v.take(16u * (uint64_t)n, d_dig);
+    };
+    HIPCHK(grow(x->files, x->files_cap, carve(nullptr), &st));
+    carve(x->files);
+    rc = streams_decode(c, d->d_frames, n, tb, ires, d->d_pcm, pcm_offs.data(), pcm_caps.data(), d_res,
+                        device_md5 ? d_dig : nullptr, st);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(res.data(), d_res, (uint64_t)n * sizeof(streams::StreamResult), hipMemcpyDeviceToHost, st));
+    if (device_md5) HIPCHK(hipMemcpyAsync(digests, d_dig, 16u * (uint64_t)n, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::vector<const void *> hp;
+    std::vector<uint64_t> hl;
+    std::vector<uint32_t> hi;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint64_t bytes = res[i].n_samples * per;
+        const bool clean = res[i].index_status == idx::IDX_OK && res[i].bad_frames == 0 && bytes <= pcm_caps[i];
+        take_single[i] = clean ? 0 : 1;
+        if (!clean) continue;
+        n_samples[i] = res[i].n_samples;
+        if (bytes) HIPCHK(hipMemcpyAsync(pcm_out[i], d->d_pcm + pcm_offs[i], bytes, hipMemcpyDeviceToHost, st));
+        if (!device_md5) {
+            hp.push_back(pcm_out[i]);
+            hl.push_back(bytes);
+            hi.push_back(i);
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (!device_md5 && !hi.empty()) {
+        std::vector<uint8_t> dg(16u * hi.size());
+        rc = flacgpu_md5_many((uint32_t)hi.size(), hp.data(), hl.data(), nullptr, nullptr, dg.data());
+        if (rc) return rc;
+        for (size_t k = 0; k < hi.size(); k++) std::copy(dg.begin() + 16 * k, dg.begin() + 16 * (k + 1), digests + 16u * hi[k]);
+    }
     return FLACGPU_OK;
 }

@@ -18,6 +18,11 @@
 //
 // Every stage is its own launch and reads the counts of the stage before from device memory: no
 // workgroup waits on another, and the host sizes every grid from len and cap alone.
+//
+// Many streams in one call (launch_index_streams): the same kernels instantiated with MANY, each
+// picking its stream's IdxArgs from a table in device memory by blockIdx.y; the grids' x extents
+// are the longest stream's, and a workgroup past its stream's groups exits at once.  The
+// one-stream instances take their IdxArgs by value as before.
 #include <hip/hip_runtime.h>
 
 #include "fg_common.hpp"
@@ -80,7 +85,13 @@ __device__ __forceinline__ void load_inner(const IdxArgs &g, uint64_t a, uint32_
 __device__ __forceinline__ uint32_t byte_of(const uint32_t (&w)[16], int k) { return (w[k >> 2] >> (8 * (k & 3))) & 255u; }
 
 // ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kGroup) k_idx_terms(IdxArgs g) {
+template <bool MANY>
+__global__ void __launch_bounds__(kGroup) k_idx_terms(IdxArgs g0, const IdxArgs *tab) {
+    IdxArgs g = g0;
+    if constexpr (MANY) {
+        g = tab[blockIdx.y];
+        if (blockIdx.x >= g.n_groups) return;
+    }
     __shared__ uint32_t s_x[kGroup / 64];
     const uint32_t tid = threadIdx.x;
     const uint64_t j = (uint64_t)blockIdx.x * kGroup + tid;
@@ -113,7 +124,7 @@ __global__ void __launch_bounds__(kGroup) k_idx_terms(IdxArgs g) {
 // One workgroup: v[0, n) becomes its exclusive scan (XOR or add), *total the sum.  With a result:
 // the default verdict (no frame start found: INVALID) that k_idx_place's last frame start replaces.
 template <bool ADD>
-__global__ void __launch_bounds__(1024) k_idx_scan(uint32_t *v, uint32_t n, uint32_t *total, IndexResult *res) {
+__device__ __forceinline__ void scan_one(uint32_t *v, uint32_t n, uint32_t *total, IndexResult *res) {
     __shared__ uint32_t s_wave[16];
     uint32_t carry = 0;
     for (uint32_t base = 0; base < n; base += 1024u) {
@@ -132,6 +143,25 @@ __global__ void __launch_bounds__(1024) k_idx_scan(uint32_t *v, uint32_t n, uint
             res->reserved = 0;
         }
     }
+}
+template <bool ADD>
+__global__ void __launch_bounds__(1024) k_idx_scan(uint32_t *v, uint32_t n, uint32_t *total, IndexResult *res) {
+    scan_one<ADD>(v, n, total, res);
+}
+// many streams: workgroup s scans stream s's group sums; a stream of no bytes is OK with 0 frames
+template <bool ADD>
+__global__ void __launch_bounds__(1024) k_idx_scan_streams(const IdxArgs *tab) {
+    const IdxArgs g = tab[blockIdx.x];
+    if (g.len == 0) {
+        if (ADD && threadIdx.x == 0) {
+            g.res->n_frames = 0;
+            g.res->status = IDX_OK;
+            g.res->reserved = 0;
+        }
+        return;
+    }
+    if constexpr (ADD) scan_one<true>(g.gcnt, g.n_groups, g.ctl + 1, g.res);
+    else scan_one<false>(g.grp, g.n_groups, g.ctl, nullptr);
 }
 
 // 32 mask bits from grid position v on (v may be negative or past the end: zeros there)
@@ -153,7 +183,13 @@ __device__ __noinline__ uint32_t cand_hdr(const IdxArgs &g, int64_t v) {
     return header_at(g.data + x, g.len - x, g.bits, g.rate, &h) ? h : 0u;
 }
 
-__global__ void __launch_bounds__(kGroup) k_idx_cands(IdxArgs g) {
+template <bool MANY>
+__global__ void __launch_bounds__(kGroup) k_idx_cands(IdxArgs g0, const IdxArgs *tab) {
+    IdxArgs g = g0;
+    if constexpr (MANY) {
+        g = tab[blockIdx.y];
+        if (blockIdx.x >= g.n_groups) return;
+    }
     __shared__ uint32_t s_wave[kGroup / 64];
     const uint32_t tid = threadIdx.x;
     const uint64_t j = (uint64_t)blockIdx.x * kGroup + tid;
@@ -191,7 +227,13 @@ __global__ void __launch_bounds__(kGroup) k_idx_cands(IdxArgs g) {
     g.smask[j] = 0;
 }
 
-__global__ void __launch_bounds__(kGroup) k_idx_resolve(IdxArgs g) {
+template <bool MANY>
+__global__ void __launch_bounds__(kGroup) k_idx_resolve(IdxArgs g0, const IdxArgs *tab) {
+    IdxArgs g = g0;
+    if constexpr (MANY) {
+        g = tab[blockIdx.y];
+        if (blockIdx.x >= g.n_groups) return;
+    }
     const uint64_t j = (uint64_t)blockIdx.x * kGroup + threadIdx.x;
     if (j >= g.n_chunks) return;
     auto win = [&](int64_t v) { return mask_window(g.cmask, g.n_chunks, v); };
@@ -202,7 +244,13 @@ __global__ void __launch_bounds__(kGroup) k_idx_resolve(IdxArgs g) {
         resolve_from((int64_t)(j * kChunk + (uint64_t)__builtin_ctzll(m)), win, hdr_of, mark);
 }
 
-__global__ void __launch_bounds__(kGroup) k_idx_count(IdxArgs g) {
+template <bool MANY>
+__global__ void __launch_bounds__(kGroup) k_idx_count(IdxArgs g0, const IdxArgs *tab) {
+    IdxArgs g = g0;
+    if constexpr (MANY) {
+        g = tab[blockIdx.y];
+        if (blockIdx.x >= g.n_groups) return;
+    }
     __shared__ uint32_t s_wave[kGroup / 64];
     const uint64_t j = (uint64_t)blockIdx.x * kGroup + threadIdx.x;
     uint32_t all;
@@ -210,7 +258,13 @@ __global__ void __launch_bounds__(kGroup) k_idx_count(IdxArgs g) {
     if (threadIdx.x == 0) g.gcnt[blockIdx.x] = all;
 }
 
-__global__ void __launch_bounds__(kGroup) k_idx_place(IdxArgs g) {
+template <bool MANY>
+__global__ void __launch_bounds__(kGroup) k_idx_place(IdxArgs g0, const IdxArgs *tab) {
+    IdxArgs g = g0;
+    if constexpr (MANY) {
+        g = tab[blockIdx.y];
+        if (blockIdx.x >= g.n_groups) return;
+    }
     __shared__ uint32_t s_wave[kGroup / 64];
     const uint64_t j = (uint64_t)blockIdx.x * kGroup + threadIdx.x;
     const uint64_t sel = j < g.n_chunks ? g.smask[j] : 0ull;
@@ -231,13 +285,16 @@ __global__ void __launch_bounds__(kGroup) k_idx_place(IdxArgs g) {
     }
 }
 
-__global__ void __launch_bounds__(256) k_idx_emit(IdxArgs g) {
+template <bool MANY>
+__global__ void __launch_bounds__(256) k_idx_emit(IdxArgs g0, const IdxArgs *tab) {
+    IdxArgs g = g0;
+    if constexpr (MANY) g = tab[blockIdx.y];
     const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (g.res->status != IDX_OK) return;
     const uint64_t n = g.res->n_frames;  // <= cap and <= spos_cap: a frame is at least 9 bytes
     if (i >= n || n > g.spos_cap) return;
     const uint64_t s = g.spos[i], e = i + 1u < n ? (uint64_t)g.spos[i + 1u] : g.len;
-    g.offs[i] = s;
+    g.offs[i] = g.base_off + s;
     g.bytes[i] = (uint32_t)(e - s);
 }
 
@@ -246,15 +303,37 @@ __global__ void __launch_bounds__(256) k_idx_emit(IdxArgs g) {
 // queues the eight stages on st; g.len > 0
 hipError_t launch_index(const IdxArgs &g, hipStream_t st) {
     const uint32_t ng = g.n_groups;
-    hipLaunchKernelGGL(k_idx_terms, dim3(ng), dim3(kGroup), 0, st, g);
+    const IdxArgs *one = nullptr;
+    hipLaunchKernelGGL(k_idx_terms<false>, dim3(ng), dim3(kGroup), 0, st, g, one);
     hipLaunchKernelGGL(k_idx_scan<false>, dim3(1), dim3(1024), 0, st, g.grp, ng, g.ctl, (IndexResult *)nullptr);
-    hipLaunchKernelGGL(k_idx_cands, dim3(ng), dim3(kGroup), 0, st, g);
-    hipLaunchKernelGGL(k_idx_resolve, dim3(ng), dim3(kGroup), 0, st, g);
-    hipLaunchKernelGGL(k_idx_count, dim3(ng), dim3(kGroup), 0, st, g);
+    hipLaunchKernelGGL(k_idx_cands<false>, dim3(ng), dim3(kGroup), 0, st, g, one);
+    hipLaunchKernelGGL(k_idx_resolve<false>, dim3(ng), dim3(kGroup), 0, st, g, one);
+    hipLaunchKernelGGL(k_idx_count<false>, dim3(ng), dim3(kGroup), 0, st, g, one);
     hipLaunchKernelGGL(k_idx_scan<true>, dim3(1), dim3(1024), 0, st, g.gcnt, ng, g.ctl + 1, g.res);
-    hipLaunchKernelGGL(k_idx_place, dim3(ng), dim3(kGroup), 0, st, g);
+    hipLaunchKernelGGL(k_idx_place<false>, dim3(ng), dim3(kGroup), 0, st, g, one);
     const uint64_t ne = (g.spos_cap + 255u) / 256u;
-    if (ne) hipLaunchKernelGGL(k_idx_emit, dim3((uint32_t)ne), dim3(256), 0, st, g);
+    if (ne) hipLaunchKernelGGL(k_idx_emit<false>, dim3((uint32_t)ne), dim3(256), 0, st, g, one);
+    return hipGetLastError();
+}
+
+// The same eight stages, once, over the n <= kIdxMaxStreams streams of d_tab (device memory): the
+// x extents come from the longest stream (max_groups groups, max_spos rank entries), y is the
+// stream.  The launch count does not depend on n.
+hipError_t launch_index_streams(const IdxArgs *d_tab, uint32_t n, uint32_t max_groups, uint64_t max_spos, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    const IdxArgs none{};
+    const dim3 grid(max_groups, n);
+    if (max_groups) hipLaunchKernelGGL(k_idx_terms<true>, grid, dim3(kGroup), 0, st, none, d_tab);
+    hipLaunchKernelGGL(k_idx_scan_streams<false>, dim3(n), dim3(1024), 0, st, d_tab);
+    if (max_groups) {
+        hipLaunchKernelGGL(k_idx_cands<true>, grid, dim3(kGroup), 0, st, none, d_tab);
+        hipLaunchKernelGGL(k_idx_resolve<true>, grid, dim3(kGroup), 0, st, none, d_tab);
+        hipLaunchKernelGGL(k_idx_count<true>, grid, dim3(kGroup), 0, st, none, d_tab);
+    }
+    hipLaunchKernelGGL(k_idx_scan_streams<true>, dim3(n), dim3(1024), 0, st, d_tab);
+    if (max_groups) hipLaunchKernelGGL(k_idx_place<true>, grid, dim3(kGroup), 0, st, none, d_tab);
+    const uint64_t ne = (max_spos + 255u) / 256u;
+    if (ne) hipLaunchKernelGGL(k_idx_emit<true>, dim3((uint32_t)ne, n), dim3(256), 0, st, none, d_tab);
     return hipGetLastError();
 }
 

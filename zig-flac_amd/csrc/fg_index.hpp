@@ -152,7 +152,57 @@ struct IdxArgs {
     uint32_t *bytes;
     uint64_t cap;
     IndexResult *res;
+    uint64_t base_off;       // added to every offset written to offs[] (many streams: the stream's offset in the buffer)
 };
+
+// ---- many streams in one call ---------------------------------------------------------------
+// Every stream is indexed on its own: its IdxArgs is one entry of a table in device memory, the
+// kernels pick theirs from blockIdx.y (the two scans: one workgroup per stream), and every grid's
+// x extent is sized from the longest stream; workgroups past a stream's groups exit at once.
+constexpr uint32_t kIdxMaxStreams = 65535;  // gridDim.y
+
+// what a stream's length, address and table capacity fix: the chunk grid and the rank array
+FG_HD void stream_geometry(IdxArgs &g, uint64_t addr, uint64_t len, uint64_t cap) {
+    g.len = len;
+    g.lead = (uint32_t)(addr & 15u);
+    g.n_chunks = len ? (g.lead + len + kIdxChunk - 1u) / kIdxChunk : 0u;
+    g.n_groups = (uint32_t)((g.n_chunks + kIdxGroup - 1u) / kIdxGroup);
+    const uint64_t most = len / 8u + 1u;  // a frame is at least 9 bytes
+    g.spos_cap = len ? (cap < most ? cap : most) : 0u;
+    g.cap = cap;
+}
+
+// the elements of each scratch array that the streams so far take, and the longest stream's grids
+struct IdxTotals {
+    uint64_t chunks = 0, groups = 0, spos = 0, streams = 0;
+    uint32_t max_groups = 0;
+    uint64_t max_spos = 0;
+};
+// the scratch arrays of all streams, each one allocation-aligned array over all of them
+struct IdxPool {
+    uint64_t *cmask, *smask;
+    uint32_t *grp, *gcnt, *ctl, *spos;
+    uint16_t *terms;
+};
+FG_HD void totals_add(IdxTotals &t, const IdxArgs &g) {
+    t.chunks += g.n_chunks;
+    t.groups += g.n_groups;
+    t.spos += g.spos_cap;
+    t.streams += 1u;
+    if (g.n_groups > t.max_groups) t.max_groups = g.n_groups;
+    if (g.spos_cap > t.max_spos) t.max_spos = g.spos_cap;
+}
+// stream g's carve of the pool: the elements after those of the streams counted in t; then counts g
+FG_HD void carve_stream(IdxArgs &g, const IdxPool &p, IdxTotals &t) {
+    g.cmask = p.cmask + t.chunks;
+    g.smask = p.smask + t.chunks;
+    g.terms = p.terms + t.chunks;
+    g.grp = p.grp + t.groups;
+    g.gcnt = p.gcnt + t.groups;
+    g.spos = p.spos + t.spos;
+    g.ctl = p.ctl + 4u * t.streams;
+    totals_add(t, g);
+}
 
 }  // namespace idx
 }  // namespace fg

@@ -42,4 +42,11 @@ void ctx_finish(flacgpu_ctx *c);  // fold pending timing events
 // from the device index: the caller takes the host index and flacgpu_decode_frames.
 int decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uint32_t stream_bits, uint32_t stream_rate,
                            uint8_t *pcm_out, size_t pcm_cap, uint64_t *n_samples, uint8_t digest[16]);
+// fg_dec_host.cpp, the device side of flacgpu_decode_files: n bare runs of frames (the files past
+// their metadata) uploaded into one buffer, indexed in one call and decoded in chunks that span
+// files; n_samples[i], the PCM at pcm_out[i] and digests[16 i ..] for every file with
+// take_single[i] = 0.  take_single[i] = 1: the file goes through flacgpu_decode_file.
+int decode_files_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *p, const size_t *len, const uint32_t *bits,
+                          const uint32_t *rates, uint8_t *const *pcm_out, const size_t *pcm_cap, uint64_t *n_samples,
+                          uint8_t *digests, uint8_t *take_single);
 }  // namespace fg

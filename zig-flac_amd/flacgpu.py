@@ -356,6 +356,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_flac_index": (I32, [P, SZ, P, ctypes.POINTER(SZ), P, SZ, ctypes.POINTER(SZ)]),
         "flacgpu_decode_file": (I32, [P, P, SZ, P, SZ, ctypes.POINTER(U64), ctypes.POINTER(I32)]),
         "flacgpu_flac_index_device": (I32, [P, P, U64, U32, U32, P, P, U64, P, P]),
+        "flacgpu_flac_index_streams_device": (I32, [P, P, U32, P, P, P, P, P, P, P, P, P, P]),
+        "flacgpu_decode_streams_device": (I32, [P, P, U32, P, P, P, P, P, P, P, P, P, P]),
+        "flacgpu_decode_files": (I32, [P, U32, P, P, P, P, P, P, P]),
     }
     # an older build named by FLACGPU_LIB (same-box A/B runs, tools/ab.sh) may predate later entry
     # points: those stay unbound there; the in-tree library must export every one
@@ -391,6 +394,7 @@ def exported_symbols() -> list:
         "flacgpu_comm_size", "flacgpu_gather_frames_device", "flacgpu_encode_frames_sharded",
         "flacgpu_decode_frames_device", "flacgpu_verify_plan_device", "flacgpu_decode_frames", "flacgpu_flac_index",
         "flacgpu_decode_file", "flacgpu_flac_index_device",
+        "flacgpu_flac_index_streams_device", "flacgpu_decode_streams_device", "flacgpu_decode_files",
     ]
 
 
@@ -489,6 +493,21 @@ class DecodeResult(ctypes.Structure):
                 ("bits", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 6)]
 
 
+class StreamResult(ctypes.Structure):
+    """flacgpu_stream_result: one stream of flacgpu_decode_streams_device (device memory, 32 bytes)."""
+    _fields_ = [("n_frames", ctypes.c_uint64), ("n_samples", ctypes.c_uint64), ("index_status", ctypes.c_uint32),
+                ("bad_frames", ctypes.c_uint32), ("first_bad_frame", ctypes.c_uint32),
+                ("first_bad_status", ctypes.c_uint32)]
+
+
+def _u64s(v: Sequence[int]):
+    return (ctypes.c_uint64 * max(len(v), 1))(*v)
+
+
+def _u32s(v: Optional[Sequence[int]]):
+    return (ctypes.c_uint32 * max(len(v), 1))(*v) if v is not None else None
+
+
 def flac_index(buf: bytes, raw_frames: bool = False):
     """flacgpu_flac_index (host only): (StreamInfo or None, first frame offset, [frame sizes]) of a
     FLAC file in memory; raw_frames: `buf` is a bare run of frames (no "fLaC", no metadata)."""
@@ -522,6 +541,59 @@ class _DecodeOps:
         addresses in, *d_result (an IndexResult) in device memory, nothing synchronised."""
         _check(self.lib.flacgpu_flac_index_device(self.ctx, d_data, length, stream_bits, stream_rate, d_frame_offsets,
                                                   d_frame_bytes, cap, d_result, _stream(stream)), "flac_index_device")
+
+    def flac_index_streams_device(self, d_data: int, offsets: Sequence[int], lengths: Sequence[int],
+                                  table_first: Sequence[int], table_caps: Sequence[int], d_frame_offsets: int,
+                                  d_frame_bytes: int, d_results: int, stream_bits: Optional[Sequence[int]] = None,
+                                  stream_rates: Optional[Sequence[int]] = None, stream: Optional[int] = None) -> None:
+        """flacgpu_flac_index_streams_device: the frame tables of len(offsets) bare runs of frames of one
+        device buffer in one call; d_results: IndexResult per stream in device memory."""
+        _check(self.lib.flacgpu_flac_index_streams_device(
+            self.ctx, d_data, len(offsets), _u64s(offsets), _u64s(lengths), _u32s(stream_bits), _u32s(stream_rates),
+            _u64s(table_first), _u64s(table_caps), d_frame_offsets, d_frame_bytes, d_results, _stream(stream)),
+            "flac_index_streams_device")
+
+    def decode_streams_device(self, d_data: int, offsets: Sequence[int], lengths: Sequence[int], d_pcm_out: int,
+                              pcm_offsets: Sequence[int], pcm_caps: Sequence[int], d_results: int,
+                              d_md5: Optional[int] = None, stream_bits: Optional[Sequence[int]] = None,
+                              stream_rates: Optional[Sequence[int]] = None, stream: Optional[int] = None) -> None:
+        """flacgpu_decode_streams_device: index and decode len(offsets) device-resident streams into
+        their PCM regions; d_results: StreamResult per stream, d_md5: 16 bytes per stream (device)."""
+        _check(self.lib.flacgpu_decode_streams_device(
+            self.ctx, d_data, len(offsets), _u64s(offsets), _u64s(lengths), _u32s(stream_bits), _u32s(stream_rates),
+            d_pcm_out, _u64s(pcm_offsets), _u64s(pcm_caps), d_results, d_md5 or None, _stream(stream)),
+            "decode_streams_device")
+
+    def decode_files(self, flacs: Sequence[bytes], pcm_caps: Optional[Sequence[int]] = None, guard: int = 0):
+        """flacgpu_decode_files: whole FLAC files in one call -> [(status, PCM bytes, md5_ok)] per
+        file.  pcm_caps: each file's capacity (default: its frame count times the block size);
+        guard: that many extra bytes after every capacity, returned as a fourth tuple member."""
+        n = len(flacs)
+        per = self.channels * self.bytes_per_sample
+        if pcm_caps is None:
+            pcm_caps = []
+            for f in flacs:
+                try:
+                    pcm_caps.append(len(flac_index(f)[2]) * self.block_size * per)
+                except FlacGpuError:
+                    pcm_caps.append(0)
+        srcs = [ctypes.create_string_buffer(bytes(f), max(len(f), 1)) for f in flacs]
+        outs = [ctypes.create_string_buffer(b"\xA5" * (c + guard + 1), c + guard + 1) for c in pcm_caps]
+        P = ctypes.c_void_p
+        a_src = (P * max(n, 1))(*[ctypes.addressof(b) for b in srcs])
+        a_out = (P * max(n, 1))(*[ctypes.addressof(b) for b in outs])
+        a_len = (ctypes.c_size_t * max(n, 1))(*[len(f) for f in flacs])
+        a_cap = (ctypes.c_size_t * max(n, 1))(*pcm_caps)
+        ns = (ctypes.c_uint64 * max(n, 1))()
+        ok = (ctypes.c_int * max(n, 1))()
+        st = (ctypes.c_int * max(n, 1))()
+        _check(self.lib.flacgpu_decode_files(self.ctx, n, a_src, a_len, a_out, a_cap, ns, ok, st), "decode_files")
+        res = []
+        for i in range(n):
+            pcm = outs[i].raw[: min(ns[i] * per, pcm_caps[i])]
+            item = (int(st[i]), pcm, bool(ok[i]))
+            res.append(item + (outs[i].raw[pcm_caps[i]: pcm_caps[i] + guard],) if guard else item)
+        return res
 
     def decode_frames(self, frames: bytes, sizes: Sequence[int]):
         """flacgpu_decode_frames: concatenated frames of one stream -> (PCM bytes, [DecodeResult])."""
