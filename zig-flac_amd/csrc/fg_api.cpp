@@ -74,6 +74,24 @@ uint32_t q_zpow(uint64_t e) {
     return (r & 0x8000u) ? r ^ 0x8003u : r;
 }
 
+// CRC-16 shift constants of the table-free fold (mod Q, fg_device.hpp crc_lane_q) for a pack
+// kernel of T threads: thread t folds 2H words, followed by 2H (T - 1 - t) words and the CRC's
+// z^16.  Row H - 1 for H = 1..hmax, and one spare entry so that a kernel not in use still has a table.
+std::vector<uint16_t> crc_fold_shifts(uint32_t T, uint32_t hmax) {
+    std::vector<uint16_t> pw((size_t)hmax * T + 1);
+    for (uint32_t h = 1; h <= hmax; h++)
+        for (uint32_t t = 0; t < T; t++) pw[(size_t)(h - 1) * T + t] = (uint16_t)q_zpow(16ull + 64ull * h * (T - 1u - t));
+    return pw;
+}
+
+// The one reader of the knobs' environment variables (fg_geom.hpp: kKnobNames, knob_set)
+Knobs knobs_from_env() {
+    Knobs k;
+    for (const char *name : kKnobNames)
+        if (const char *e = std::getenv(name)) knob_set(k, name, e);
+    return k;
+}
+
 }  // namespace
 
 // device MD5 engine: whole blocks move through one bounded device buffer
@@ -147,22 +165,22 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
     if (n_frames > 0xFFFFFFFFull) return FLACGPU_ERR_INVALID_INPUT;
     EncodeArgs a{};
     a.pcm = d_pcm;
-    a.channels = c->C;
-    a.bits = c->bits;
-    a.bytes_per_sample = c->B;
+    a.channels = c->g.C;
+    a.bits = c->g.bits;
+    a.bytes_per_sample = c->g.B;
     a.sample_rate = c->cfg.sample_rate;
-    a.stereo = c->stereo;
+    a.stereo = c->g.stereo;
     a.max_part_order = c->cfg.max_rice_part_order;
     a.max_param = c->cfg.max_rice_param;
     a.lpc_order = c->cfg.prediction;
     a.block_size = c->cfg.block_size;
     a.desc = d_desc;
-    a.desc_stride = c->desc_stride;
-    a.image_bytes = c->image_bytes;
-    a.stage_dbuf = c->stage_dbuf ? 1u : 0u;
-    a.pack_dbuf = c->pack_dbuf ? 1u : 0u;
-    a.enc_prio = c->enc_prio;
-    a.ana1_variant = c->ana1_variant;
+    a.desc_stride = c->g.desc_stride;
+    a.image_bytes = c->g.image_bytes;
+    a.stage_dbuf = c->g.stage_dbuf ? 1u : 0u;
+    a.pack_dbuf = c->g.pack_dbuf ? 1u : 0u;
+    a.enc_prio = c->k.enc_prio;
+    a.ana1_variant = c->g.ana1_variant;
     a.frame_bytes = d_fbytes;
     a.offsets = d_offsets;
     a.out = d_out;
@@ -171,9 +189,9 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
     a.work_ctr = c->d_ctr;
     a.crc_pow = c->d_crc_pow;
     a.crc_pow4 = c->d_crc_pow4;
-    a.crc_hmax4 = c->crc_hmax4;
+    a.crc_hmax4 = c->g.crc_hmax4;
     a.crc_join = c->d_crc_join;
-    a.crc_hmax = c->crc_hmax;
+    a.crc_hmax = c->g.crc_hmax;
     a.records = c->records_on ? c->d_records : nullptr;
     a.stamps = c->d_stamps;
     a.crc_x8 = c->d_crc_x8;
@@ -187,16 +205,16 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
         h.work_ctr = c->d_ctr + kCtrSet * set;
         h.grid_reserve = c->grid_reserve;
         h.grid_per_cu = per_cu;
-        if (c->ana_split) {
-            h.channels = c->C / 2u;
+        if (c->g.ana_split) {
+            h.channels = c->g.C / 2u;
             h.ch_split = 1;
-            h.xcd_queue = c->xcd_queue ? ((c->split_jit & 1u) ? 3u : 1u) : 0u;
-            HIPCHK(launch_stage(0, h, true, c->nt_split, c->lds_split, s));
+            h.xcd_queue = c->k.xcd_queue ? ((c->k.split_jit & 1u) ? 3u : 1u) : 0u;
+            HIPCHK(launch_stage(0, h, true, c->g.nt_split, c->g.lds_split, s));
             HIPCHK(launch_frame_totals(h, s));
-        } else if (c->ana1) {
+        } else if (c->g.ana1) {
             HIPCHK(launch_stage(3, h, true, 64u, (uint32_t)Ana1Layout::total, s));
         } else {
-            HIPCHK(launch_stage(0, h, true, c->nt, c->lds, s));
+            HIPCHK(launch_stage(0, h, true, c->g.nt, c->g.lds, s));
         }
         return FLACGPU_OK;
     };
@@ -206,20 +224,20 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
         h.jobs = d_jobs + j0;
         h.n_jobs = (uint32_t)n;
         h.work_ctr = c->d_ctr + kCtrSet * set;
-        h.grid_reserve = c->md5_reserve == 2 ? c->grid_reserve : 0u;
+        h.grid_reserve = c->k.md5_reserve == 2 ? c->grid_reserve : 0u;
         h.grid_per_cu = per_cu;
-        if (c->pack_split) {
-            h.channels = c->C / 2u;
+        if (c->g.pack_split) {
+            h.channels = c->g.C / 2u;
             h.ch_split = 1;
-            h.image_bytes = c->image_split;
+            h.image_bytes = c->g.image_split;
             h.crc_pow4 = c->d_crc_pows;
-            h.crc_hmax4 = c->crc_hmaxs;
-            h.xcd_queue = c->pack_xcdq ? ((c->split_jit & 2u) ? 3u : 1u) : 0u;
-            HIPCHK(launch_stage(1, h, true, c->nt_psplit, c->lds_psplit, s));
-        } else if (c->nt_pack4) {
-            HIPCHK(launch_stage(1, h, true, c->nt_pack4, c->lds_pack4, s));
+            h.crc_hmax4 = c->g.crc_hmaxs;
+            h.xcd_queue = c->k.pack_xcdq ? ((c->k.split_jit & 2u) ? 3u : 1u) : 0u;
+            HIPCHK(launch_stage(1, h, true, c->g.nt_psplit, c->g.lds_psplit, s));
+        } else if (c->g.nt_pack4) {
+            HIPCHK(launch_stage(1, h, true, c->g.nt_pack4, c->g.lds_pack4, s));
         } else {
-            HIPCHK(launch_stage(1, h, true, c->nt_pack, c->lds_pack, s));
+            HIPCHK(launch_stage(1, h, true, c->g.nt_pack, c->g.lds_pack, s));
         }
         return FLACGPU_OK;
     };
@@ -228,7 +246,7 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
         EncodeArgs h = a;
         h.jobs = d_jobs + n_full;
         h.n_jobs = (uint32_t)n_tail;
-        HIPCHK(launch_stage(0, h, false, c->nt, c->lds_tail, s));
+        HIPCHK(launch_stage(0, h, false, c->g.nt, c->g.lds_tail, s));
         return FLACGPU_OK;
     };
     auto pack_tail = [&](hipStream_t s) -> int {
@@ -236,14 +254,14 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
         EncodeArgs h = a;
         h.jobs = d_jobs + n_full;
         h.n_jobs = (uint32_t)n_tail;
-        HIPCHK(launch_stage(1, h, false, c->nt_pack, c->lds_pack, s));
+        HIPCHK(launch_stage(1, h, false, c->g.nt_pack, c->g.lds_pack, s));
         return FLACGPU_OK;
     };
     // the multi-workgroup scan's per-block sums: a grow-only context buffer
     const uint32_t nb = (uint32_t)((n_frames + 4095u) / 4096u);
     HIPCHK(grow(c->d_scan_part, c->scan_part_cap, nb));
 
-    if (c->fused && n_full) {
+    if (c->g.fused && n_full) {
         // fused: the tail frames' analysis first (it publishes their sizes), then analysis + pack of
         // the full frames in one kernel whose frames find their offsets by look-back, then the scan
         // (offsets of every frame, the total) and the tail frames' pack
@@ -260,9 +278,9 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
             h.n_jobs = (uint32_t)n_full;
             h.stage_dbuf = 0;
             h.crc_pow4 = c->d_crc_powf;
-            h.crc_hmax4 = c->crc_hmaxf;
+            h.crc_hmax4 = c->g.crc_hmaxf;
             h.grid_reserve = c->grid_reserve;
-            HIPCHK(launch_stage(2, h, true, 256u, c->lds_fused, st));
+            HIPCHK(launch_stage(2, h, true, 256u, c->g.lds_fused, st));
         }
         a.status = nullptr;
         {
@@ -329,14 +347,18 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
     return FLACGPU_OK;
 }
 
+// The device error word, read back, as a return code (bit 0 invariant, bit 1 output too small); a
+// set word is cleared for the next call.
+int device_error_code(flacgpu_ctx *c, uint32_t err) {
+    if (!err) return FLACGPU_OK;
+    hipMemset(c->d_err, 0, 4);
+    return (err & 2u) && !(err & 1u) ? FLACGPU_ERR_OUTPUT_TOO_SMALL : FLACGPU_ERR_INTERNAL;
+}
+
 int check_device_error(flacgpu_ctx *c) {
     uint32_t err = 0;
     HIPCHK(hipMemcpy(&err, c->d_err, 4, hipMemcpyDeviceToHost));
-    if (err) {
-        hipMemset(c->d_err, 0, 4);
-        return (err & 2u) && !(err & 1u) ? FLACGPU_ERR_OUTPUT_TOO_SMALL : FLACGPU_ERR_INTERNAL;
-    }
-    return FLACGPU_OK;
+    return device_error_code(c, err);
 }
 
 // Wait on the host for everything queued on st so far, through the context's event i (blocking
@@ -351,11 +373,7 @@ int check_device_error_on(flacgpu_ctx *c, hipStream_t st) {
     uint32_t err = 0;
     HIPCHK(hipMemcpyAsync(&err, c->d_err, 4, hipMemcpyDeviceToHost, st));
     HIPCHK(wait_host(c, st, 3));
-    if (err) {
-        hipMemset(c->d_err, 0, 4);
-        return (err & 2u) && !(err & 1u) ? FLACGPU_ERR_OUTPUT_TOO_SMALL : FLACGPU_ERR_INTERNAL;
-    }
-    return FLACGPU_OK;
+    return device_error_code(c, err);
 }
 
 int fetch_records(flacgpu_ctx *c, uint64_t n_frames, hipStream_t st) {
@@ -379,8 +397,8 @@ int fg::ctx_encode_chunk(flacgpu_ctx *c, const uint8_t *src, uint64_t ns, uint64
     *total = 0;
     if (nf == 0) return FLACGPU_OK;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(c->d_pcm, src, ns * c->C * c->B, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_make_jobs(c->d_jobs, ns, bs, (uint32_t)((uint64_t)bs * c->C * c->B), first_number, (uint32_t)nf,
+    HIPCHK(hipMemcpyAsync(c->d_pcm, src, ns * c->g.C * c->g.B, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(launch_make_jobs(c->d_jobs, ns, bs, (uint32_t)((uint64_t)bs * c->g.C * c->g.B), first_number, (uint32_t)nf,
                             c->stream));
     // frames with n == 4096 take the lane-owned-partition kernel, the rest the general one
     const uint64_t n_full = (bs == (uint32_t)kBlock) ? ns / kBlock : 0;
@@ -402,9 +420,9 @@ int fg::ctx_download_chunk(flacgpu_ctx *c, uint8_t *out, uint64_t total) {
 }
 
 uint32_t fg::ctx_max_frames(const flacgpu_ctx *c) { return c->max_frames; }
-bool fg::ctx_plain(const flacgpu_ctx *c) { return !c->records_on && !c->timing && c->ovl_chunks <= 1 && !c->fused; }
+bool fg::ctx_plain(const flacgpu_ctx *c) { return !c->records_on && !c->timing && c->ovl_chunks <= 1 && !c->g.fused; }
 fg::CtxDevice fg::ctx_device(const flacgpu_ctx *c) {
-    return {c->device, (void *)c->stream, c->d_out, c->d_fbytes, c->d_total, c->out_cap, c->C, c->B,
+    return {c->device, (void *)c->stream, c->d_out, c->d_fbytes, c->d_total, c->out_cap, c->g.C, c->g.B,
             c->cfg.block_size};
 }
 void fg::ctx_finish(flacgpu_ctx *c) { resolve_timing(c); }
@@ -486,196 +504,60 @@ int flacgpu_open(int device, const flacgpu_config *cfg, uint32_t max_frames_per_
     c->device = device;
     c->cfg = *cfg;
     c->max_frames = max_frames_per_call ? max_frames_per_call : 32768u;
-    c->C = cfg->channels;
-    c->bits = cfg->bits_per_sample;
-    c->B = c->bits / 8;
-    c->stereo = (c->C == 2 && cfg->stereo_decorrelation) ? 1u : 0u;
-    const uint32_t nw = c->stereo ? 4u : c->C;
-    const uint32_t n_out = c->stereo ? 2u : c->C;
-    c->nt = 64u * nw;
-    c->nt_pack = 64u * n_out;
-    c->image_bytes = fg_round16(frame_bound_bytes(kBlock, c->C, c->bits, c->stereo != 0) + 16u);
-    c->desc_stride = desc_stride(n_out);
-    const bool lpc = c->cfg.prediction != 0;
-    // 24-bit LPC analysis runs three waves per SIMD (fg_device.hpp): double-buffer only where
-    // three workgroups still fit the LDS
-    const uint32_t ana_wgs = (lpc && c->B == 3) ? (FG_C3_W == 3 ? 3u : 2u) : 1u;
-    c->stage_dbuf = ana_layout(c->C, c->B, nw, true, true, lpc).total * ana_wgs <= 160u * 1024u;
-    c->lds = ana_layout(c->C, c->B, nw, true, c->stage_dbuf, lpc).total;
-    c->lds_tail = ana_layout(c->C, c->B, nw, false, false, lpc).total;
-    // Frames of 4+ independent channels too large to double-buffer: analyse them in channel
-    // halves (one workgroup per half, staged single-buffered) when a half is whole dwords of
-    // every interchannel row and two halves fit a CU -- c4: three 51-KiB workgroups per CU
-    // instead of one 96-KiB frame (analysis 5.35 -> 4.77 ms per 65536 frames, same-box A/B).
-    if (!c->stereo && c->C >= 4u && (c->C & 1u) == 0 && ((c->C / 2u) * c->B) % 4u == 0 && !c->stage_dbuf) {
-        const uint32_t ch = c->C / 2u, lh = ana_layout(ch, c->B, ch, true, false, lpc).total;
-        if (2u * lh <= 160u * 1024u) {
-            c->ana_split = true;
-            c->nt_split = 64u * ch;
-            c->lds_split = lh;
-        }
-    }
-    // pack: double-buffer the staging when that keeps the register-limited occupancy
-    // (4 workgroups per CU; 2 for 32-bit samples)
-    const uint32_t pack_wgs = c->B == 4 ? 2u : 4u;
-    c->pack_dbuf = pack_layout(c->C, c->B, c->image_bytes, true).total * pack_wgs <= 160u * 1024u;
-    // output-invariant tuning knobs (schedule / kernel-variant choices; every setting is
-    // parity-tested: tests/test_gpu_parity.py, test_gpu_plan.py; INTEGRATION.md lists them)
-    if (const char *e = std::getenv("FLACGPU_PACK_DBUF")) c->pack_dbuf = c->pack_dbuf && e[0] == '1';
-    // 32-bit samples (c5): the 48-KiB three-chunk ring (kernel 2) -- same-box A/B r4m, 2 reps:
-    // c5 24.19-24.25k -> 24.67-24.68k MS/s (MD5 10.1 -> 9.5 ms, analysis 8.84 -> 8.58 ms beside
-    // it); c3 neutral, C2 -4 %, so the others keep kernel 1
-    if (c->B == 4u) c->md5_kernel = 2;
-    if (const char *e = std::getenv("FLACGPU_MD5_KERNEL")) c->md5_kernel = std::atoi(e);
-    if (const char *e = std::getenv("FLACGPU_XCD_QUEUE")) c->xcd_queue = e[0] != '0';
-    if (const char *e = std::getenv("FLACGPU_PACK_XCDQ")) c->pack_xcdq = e[0] != '0';
-    if (const char *e = std::getenv("FLACGPU_SPLIT_JIT")) c->split_jit = (uint32_t)std::atoi(e) & 3u;
-    if (const char *e = std::getenv("FLACGPU_PIPE_SETS")) {
-        const int v = std::atoi(e);
-        c->pipe_sets = v >= 2 && v <= (int)kPipeSets ? (uint32_t)v : kPipeSetsDefault;
-    }
-    // issue priority of the stream-MD5 waves (output-invariant): 1 trades 2-5 % of the encode for a
-    // 35-58 % shorter MD5 chain -- for a workload whose MD5 would bind the step
-    if (const char *e = std::getenv("FLACGPU_MD5_PRIO")) c->md5_prio = std::atoi(e) ? 1 : 0;
-#if FG_DIAG
-    // diagnostic build only: grid reserves, the overlapped schedule's shape
-    if (const char *e = std::getenv("FLACGPU_ENC_PRIO")) c->enc_prio = e[0] == '1' ? 1u : 0u;
-    if (const char *e = std::getenv("FLACGPU_MD5_RESERVE")) c->md5_reserve = std::atoi(e);
-    if (const char *e = std::getenv("FLACGPU_MD5_DIAG")) c->md5_prio |= std::atoi(e) << 8;
-    if (const char *e = std::getenv("FLACGPU_OVERLAP")) c->ovl_chunks = (uint32_t)std::atoi(e);
-    if (const char *e = std::getenv("FLACGPU_OVL_ANA")) c->ovl_ana = (uint32_t)std::atoi(e);
-    if (const char *e = std::getenv("FLACGPU_OVL_PACK")) c->ovl_pack = (uint32_t)std::atoi(e);
-    if (const char *e = std::getenv("FLACGPU_OVL_MIN")) c->ovl_min_frames = (uint32_t)std::max(1, std::atoi(e));
-#endif
-    c->lds_pack = pack_layout(c->C, c->B, c->image_bytes, c->pack_dbuf).total;
-    // CRC fold: half-segments of H words (odd), H <= ceil(image words / (2 * pack threads))
-    c->crc_hmax = ((c->image_bytes / 4u + 2u * c->nt_pack - 1u) / (2u * c->nt_pack)) | 1u;
-    if (c->C == 2 && c->B == 2 && !lpc) {
-        c->nt_pack4 = 512u;
-        if (const char *e = std::getenv("FLACGPU_PACK4")) c->nt_pack4 = e[0] == '0' ? 0u : 512u;  // A/B knob
-    }
-    bool packw_dbuf = true;
-    // k_packw (fg_packw.hpp) where k_pack's occupancy is poor: 32-bit samples (i64 lanes, 2 waves
-    // per SIMD) or more than two written subframes (one workgroup per CU).  Mono/stereo 8-24-bit
-    // frames stay on k_pack: its small single-buffered workgroups keep 4-5 frames in flight per
-    // CU, which measured faster (c3 pack alone: 1.26 ms vs 1.40-1.66 ms for the packw variants).
-    bool use_packw = c->B == 4u || n_out > 2u;
-    if (const char *e = std::getenv("FLACGPU_PACKW")) use_packw = e[0] == '1' ? true : (e[0] == '0' ? false : use_packw);  // A/B knob
-    if (!c->nt_pack4 && use_packw) {
-        // WPS waves per written subframe, 16 (<= 4 subframes) or 32 samples per lane;
-        // double-buffered staging where two workgroups per CU still fit
-        uint32_t wps = n_out <= 4u ? 4u : 2u;
-        if (const char *e = std::getenv("FLACGPU_PACKW_WPS")) wps = (e[0] == '2' && n_out <= 8u) ? 2u : wps;  // tuning knob
-        c->nt_pack4 = 64u * n_out * wps;
-        packw_dbuf = packw_layout(c->C, c->B, wps, c->image_bytes, true, n_out).total * 2u <= 160u * 1024u;
-        if (const char *e = std::getenv("FLACGPU_PACKW_DBUF")) packw_dbuf = packw_dbuf && e[0] == '1';  // tuning knob
-        c->pack_dbuf = packw_dbuf;  // k_pack then runs tail frames only (never double-buffered)
-    }
-    if (c->nt_pack4) {
-        c->lds_pack4 = (c->C == 2 && c->B == 2 && !lpc) ? pack4_layout(c->image_bytes).total
-                                                         : packw_layout(c->C, c->B, c->nt_pack4 / (64u * n_out), c->image_bytes, packw_dbuf, n_out).total;
-        c->crc_hmax4 = ((c->image_bytes / 4u + 2u * c->nt_pack4 - 1u) / (2u * c->nt_pack4)) | 1u;
-    }
-    // Frames whose single-buffered k_packw staging admits one workgroup per CU and whose analysis
-    // runs in channel halves are packed in channel halves too (two workgroups per CU, see k_packw)
-    if (c->ana_split && use_packw && !packw_dbuf) {
-        const uint32_t ch = c->C / 2u;
-        const uint32_t img = fg_round16(frame_bound_bytes(kBlock, ch, c->bits, false) + 16u);
-        const uint32_t lh = packw_layout(ch, c->B, 2u, img, false, ch).total;
-        bool on = 2u * lh <= 160u * 1024u;
-        if (const char *e = std::getenv("FLACGPU_PACK_SPLIT")) on = on && e[0] != '0';  // A/B knob
-        if (on) {
-            c->pack_split = true;
-            c->nt_psplit = 64u * ch * 2u;
-            c->lds_psplit = lh;
-            c->image_split = img;
-            c->crc_hmaxs = ((img / 4u + 2u * c->nt_psplit - 1u) / (2u * c->nt_psplit)) | 1u;
-        }
-    }
-#if FG_DIAG
-    if (c->C == 2 && c->B == 2 && !lpc && c->stereo) {
-        c->ana1 = false;  // measured slower than k_analyze so far: opt-in
-        if (const char *e = std::getenv("FLACGPU_ANA1")) {  // A/B knob: 0 = k_analyze, 1 / 2 = k_ana1 variant
-            c->ana1 = e[0] != '0';
-            c->ana1_variant = e[0] == '2' ? 2u : 1u;
-        }
-        c->fused = false;
-        if (const char *e = std::getenv("FLACGPU_FUSED")) c->fused = e[0] == '1';  // A/B knob
-        c->lds_fused = ana_layout(2, 2, 4, true, false, false, c->image_bytes).total;
-        c->crc_hmaxf = ((c->image_bytes / 4u + 2u * 256u - 1u) / (2u * 256u)) | 1u;
-    }
-#endif
-    if (c->lds > 160u * 1024u || c->lds_tail > 160u * 1024u || c->lds_pack > 160u * 1024u ||
-        c->lds_pack4 > 160u * 1024u) {
+    c->k = knobs_from_env();
+    if ((rc = enc_geometry(c->cfg, c->k, c->g))) {  // a kernel's LDS does not fit: no HIP resource yet
         delete c;
-        return FLACGPU_ERR_INVALID_CONFIG;
+        return rc;
     }
+    const EncGeom &g = c->g;
+    c->ovl_chunks = c->k.ovl_chunks;
+    c->ovl_ana = c->k.ovl_ana;
+    c->ovl_pack = c->k.ovl_pack;
+    c->ovl_min_frames = c->k.ovl_min_frames;
 
     auto fail = [&](int code) {
         flacgpu_close(c);
         return code;
     };
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
-    if (hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
-    if (hipStreamCreateWithFlags(&c->dl, hipStreamNonBlocking) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
-    if (hipStreamCreateWithFlags(&c->up, hipStreamNonBlocking) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
-    for (hipEvent_t &ev : c->up_done)
-        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
-    if (hipStreamCreateWithFlags(&c->ovl, hipStreamNonBlocking) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
-    if (hipEventCreateWithFlags(&c->fork, hipEventDisableTiming) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
-    if (hipEventCreateWithFlags(&c->join, hipEventDisableTiming) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
-    {
-        unsigned fl = hipEventDisableTiming | hipEventBlockingSync;
-#if FG_DIAG
-        if (const char *e = std::getenv("FLACGPU_SPIN_SYNC")) fl = e[0] == '1' ? hipEventDisableTiming : fl;
-#endif
-        for (hipEvent_t &ev : c->hw)
-            if (hipEventCreateWithFlags(&ev, fl) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
-        for (hipEvent_t &ev : c->set_done)
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
-        for (hipEvent_t &ev : c->dl_done)
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
-    }
+    for (hipStream_t *s : {&c->stream, &c->aux, &c->dl, &c->up, &c->ovl})
+        if (hipStreamCreateWithFlags(s, hipStreamNonBlocking) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
+    const unsigned quiet = hipEventDisableTiming;
+    const struct {
+        hipEvent_t *ev;
+        size_t n;
+        unsigned flags;
+    } events[] = {{c->up_done, kPipeSets, quiet}, {c->set_done, kPipeSets, quiet}, {c->dl_done, kPipeSets, quiet},
+                  {&c->fork, 1, quiet},           {&c->join, 1, quiet},
+                  {c->hw, 4, c->k.spin_sync ? quiet : quiet | hipEventBlockingSync}};
+    for (const auto &a : events)
+        for (size_t i = 0; i < a.n; i++)
+            if (hipEventCreateWithFlags(&a.ev[i], a.flags) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
 
-    // CRC-16 shift constants of the table-free fold (mod Q, fg_device.hpp crc_lane_q): thread t
-    // of T folds 2H words, followed by 2H (T - 1 - t) words and the CRC's z^16
-    const uint32_t T = c->nt_pack, HM = c->crc_hmax;
-    std::vector<uint16_t> pw((size_t)HM * T), pj(HM);
-    for (uint32_t h = 1; h <= HM; h++) {
-        pj[h - 1] = (uint16_t)q_zpow(32ull * h);
-        for (uint32_t t = 0; t < T; t++) pw[(size_t)(h - 1) * T + t] = (uint16_t)q_zpow(16ull + 64ull * h * (T - 1u - t));
-    }
-    const uint32_t T4 = c->nt_pack4, HM4 = c->crc_hmax4;
-    std::vector<uint16_t> pw4((size_t)HM4 * T4 + 1);
-    for (uint32_t h = 1; h <= HM4; h++)
-        for (uint32_t t = 0; t < T4; t++) pw4[(size_t)(h - 1) * T4 + t] = (uint16_t)q_zpow(16ull + 64ull * h * (T4 - 1u - t));
-
-    if (c->crc_hmaxf) {
-        std::vector<uint16_t> pwf((size_t)c->crc_hmaxf * 256u);
-        for (uint32_t h = 1; h <= c->crc_hmaxf; h++)
-            for (uint32_t t = 0; t < 256u; t++) pwf[(size_t)(h - 1) * 256u + t] = (uint16_t)q_zpow(16ull + 64ull * h * (255u - t));
+    // the CRC fold's shifts for each pack kernel's thread count (an unused one: hmax = 0)
+    const std::vector<uint16_t> pw = crc_fold_shifts(g.nt_pack, g.crc_hmax), pw4 = crc_fold_shifts(g.nt_pack4, g.crc_hmax4),
+                                pws = crc_fold_shifts(g.nt_psplit, g.crc_hmaxs);
+    std::vector<uint16_t> pj(g.crc_hmax), x8(24);
+    for (uint32_t h = 1; h <= g.crc_hmax; h++) pj[h - 1] = (uint16_t)q_zpow(32ull * h);
+    for (uint32_t i = 0; i < 24; i++) x8[i] = (uint16_t)crc_zpow(8ull << i);
+    if (g.crc_hmaxf) {
+        const std::vector<uint16_t> pwf = crc_fold_shifts(256u, g.crc_hmaxf);
         if (hipMalloc(&c->d_crc_powf, pwf.size() * 2) ||
             hipMemcpy(c->d_crc_powf, pwf.data(), pwf.size() * 2, hipMemcpyHostToDevice))
             return fail(FLACGPU_ERR_DEVICE);
     }
-    std::vector<uint16_t> pws((size_t)c->crc_hmaxs * c->nt_psplit + 1), x8(24);
-    for (uint32_t h = 1; h <= c->crc_hmaxs; h++)
-        for (uint32_t t = 0; t < c->nt_psplit; t++)
-            pws[(size_t)(h - 1) * c->nt_psplit + t] = (uint16_t)q_zpow(16ull + 64ull * h * (c->nt_psplit - 1u - t));
-    for (uint32_t i = 0; i < 24; i++) x8[i] = (uint16_t)crc_zpow(8ull << i);
     if (hipMalloc(&c->d_crc_pows, pws.size() * 2) || hipMalloc(&c->d_crc_x8, 48) ||
         hipMemcpy(c->d_crc_pows, pws.data(), pws.size() * 2, hipMemcpyHostToDevice) ||
         hipMemcpy(c->d_crc_x8, x8.data(), 48, hipMemcpyHostToDevice))
         return fail(FLACGPU_ERR_DEVICE);
 
     const uint64_t F = c->max_frames;
-    c->pcm_cap = F * (uint64_t)kBlock * c->C * c->B + 64;
-    c->out_cap = F * (uint64_t)c->image_bytes;
+    c->pcm_cap = F * (uint64_t)kBlock * g.C * g.B + 64;
+    c->out_cap = F * (uint64_t)g.image_bytes;
     if (hipMalloc(&c->d_crc_pow, pw.size() * 2) ||
         hipMalloc(&c->d_crc_pow4, pw4.size() * 2) ||
         hipMalloc(&c->d_crc_join, pj.size() * 2) || hipMalloc(&c->d_err, 16) || hipMalloc(&c->d_ctr, 4u * kCtrSet * kOvlMaxChunks) ||
         hipMalloc(&c->d_cum, 8u * (kOvlMaxChunks + 1u)) ||
-        hipMalloc(&c->d_jobs, F * sizeof(FrameJob)) || hipMalloc(&c->d_desc, F * (uint64_t)c->desc_stride) ||
+        hipMalloc(&c->d_jobs, F * sizeof(FrameJob)) || hipMalloc(&c->d_desc, F * (uint64_t)g.desc_stride) ||
         hipMalloc(&c->d_fbytes, F * 4) || hipMalloc(&c->d_offsets, F * 8) || hipMalloc(&c->d_total, 8u * (kPipeSets + 1u)) ||
         hipMalloc(&c->d_pcm, c->pcm_cap) || hipMalloc(&c->d_out, c->out_cap) || hipMalloc(&c->d_md5_state, 16) || hipMalloc(&c->d_stamps, 32 * 8))
         return fail(FLACGPU_ERR_OUT_OF_MEMORY);
@@ -756,14 +638,14 @@ constexpr int kNoWorker = -1000;
 
 static int encode_pipelined(flacgpu_ctx *c, PipeSeg *segs, size_t nseg) {
     const uint32_t bs = c->cfg.block_size;
-    const uint64_t stride = (uint64_t)bs * c->C * c->B;
+    const uint64_t stride = (uint64_t)bs * c->g.C * c->g.B;
     // chunks of at most 2048 frames (32 MiB of 16-bit stereo) so that long inputs keep both
     // PCIe directions busy; the thirds of the context's buffers hold one chunk each
-    const uint32_t NS = c->pipe_sets;
+    const uint32_t NS = c->k.pipe_sets;
     const uint64_t part = c->max_frames / NS;  // frames of one chunk set
     const uint64_t F = std::min<uint64_t>(part, 2048u);
-    const uint64_t pcm_half = part * kBlock * c->C * c->B;  // 16-B multiple
-    const uint64_t out_half = part * c->image_bytes;
+    const uint64_t pcm_half = part * kBlock * c->g.C * c->g.B;  // 16-B multiple
+    const uint64_t out_half = part * c->g.image_bytes;
     const uint64_t fb_half = part;
     hipEvent_t *done = c->set_done;  // a chunk set's encode finished
     struct Dl {
@@ -846,7 +728,7 @@ static int encode_pipelined(flacgpu_ctx *c, PipeSeg *segs, size_t nseg) {
             // upload: the PCM part was last read by chunk i-3's encode (its `done` event, a GPU-side
             // wait); it runs beside chunk i-1's encode and the downloads of chunks i-2, i-3
             if ((chunk >= NS && hipStreamWaitEvent(c->up, done[set], 0) != hipSuccess) ||
-                hipMemcpyAsync(dp, sg->src + s0 * c->C * c->B, ns * c->C * c->B, hipMemcpyHostToDevice, c->up) !=
+                hipMemcpyAsync(dp, sg->src + s0 * c->g.C * c->g.B, ns * c->g.C * c->g.B, hipMemcpyHostToDevice, c->up) !=
                     hipSuccess ||
                 hipEventRecord(c->up_done[set], c->up) != hipSuccess) {
                 rc = FLACGPU_ERR_DEVICE;
@@ -910,7 +792,7 @@ int fg::ctx_encode_segments(flacgpu_ctx *c, uint32_t n, const uint8_t *const *sr
         if (c->records_on) c->h_records.clear();
         c->records_keep = true;
         for (uint32_t i = 0; i < n; i++) {
-            const int r = flacgpu_encode_frames(c, src[i], c->B, n_samples[i], 0, out[i], out_cap[i], &out_len[i],
+            const int r = flacgpu_encode_frames(c, src[i], c->g.B, n_samples[i], 0, out[i], out_cap[i], &out_len[i],
                                                 frame_bytes ? frame_bytes[i] : nullptr);
             if (r) {
                 c->records_keep = false;
@@ -921,7 +803,7 @@ int fg::ctx_encode_segments(flacgpu_ctx *c, uint32_t n, const uint8_t *const *sr
         c->records_keep = false;
         return FLACGPU_OK;
     };
-    if (c->max_frames < c->pipe_sets || c->records_on) return one_by_one();
+    if (c->max_frames < c->k.pipe_sets || c->records_on) return one_by_one();
     std::vector<PipeSeg> segs;
     try {
         segs.resize(n);
@@ -946,11 +828,10 @@ int flacgpu_encode_frames(flacgpu_ctx *c, const void *pcm, uint32_t bytes_per_sa
                           uint64_t first_frame_number, uint8_t *out, size_t out_cap, size_t *out_len,
                           uint32_t *frame_bytes) {
     if (!c || (!pcm && n_samples) || !out_len) return FLACGPU_ERR_INVALID_INPUT;
-    if (bytes_per_sample != c->B) return FLACGPU_ERR_INVALID_INPUT;
+    if (bytes_per_sample != c->g.B) return FLACGPU_ERR_INVALID_INPUT;
     HIPCHK(hipSetDevice(c->device));
     *out_len = 0;
     const uint32_t bs = c->cfg.block_size;
-    const uint64_t stride = (uint64_t)bs * c->C * c->B;
     const uint64_t total_frames = frames_for(n_samples, bs);
     // frame numbers are u36 (frame_writer.zig:153, wav2flac.zig:75)
     if (total_frames && (first_frame_number >= (1ull << 36) || total_frames - 1 > (1ull << 36) - 1 - first_frame_number))
@@ -959,8 +840,8 @@ int flacgpu_encode_frames(flacgpu_ctx *c, const void *pcm, uint32_t bytes_per_sa
     uint64_t frame0 = 0;
     size_t written = 0;
     if (c->records_on && !c->records_keep) c->h_records.clear();
-    if (!c->records_on && c->max_frames >= c->pipe_sets &&
-        total_frames > std::min<uint64_t>(c->max_frames / c->pipe_sets, 2048u)) {
+    if (!c->records_on && c->max_frames >= c->k.pipe_sets &&
+        total_frames > std::min<uint64_t>(c->max_frames / c->k.pipe_sets, 2048u)) {
         PipeSeg seg{src, n_samples, first_frame_number, out, out_cap, 0, frame_bytes};
         const int rc = encode_pipelined(c, &seg, 1);
         if (rc != kNoWorker) {
@@ -969,13 +850,12 @@ int flacgpu_encode_frames(flacgpu_ctx *c, const void *pcm, uint32_t bytes_per_sa
             return rc;
         }
     }
-    (void)stride;
     while (frame0 < total_frames) {
         const uint64_t nf = std::min<uint64_t>(c->max_frames, total_frames - frame0);
         const uint64_t s0 = frame0 * bs;
         const uint64_t ns = std::min<uint64_t>(nf * bs, n_samples - s0);
         uint64_t total = 0;
-        int rc = fg::ctx_encode_chunk(c, src + s0 * c->C * c->B, ns, first_frame_number + frame0, &total,
+        int rc = fg::ctx_encode_chunk(c, src + s0 * c->g.C * c->g.B, ns, first_frame_number + frame0, &total,
                                       frame_bytes ? frame_bytes + frame0 : nullptr);
         if (rc) return rc;
         if (written + total > out_cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
@@ -991,19 +871,19 @@ int flacgpu_encode_frames(flacgpu_ctx *c, const void *pcm, uint32_t bytes_per_sa
 int flacgpu_encode_frame_planar(flacgpu_ctx *c, const int32_t *const planes[8], uint32_t n, uint64_t frame_number,
                                 uint8_t *out, size_t out_cap, uint32_t *frame_bytes) {
     if (!c || !planes || !out || n == 0 || n > c->cfg.block_size) return FLACGPU_ERR_INVALID_INPUT;
-    for (uint32_t ch = 0; ch < c->C; ch++)
+    for (uint32_t ch = 0; ch < c->g.C; ch++)
         if (!planes[ch]) return FLACGPU_ERR_INVALID_INPUT;
     // Encoder.samples[ch][0..n] -> the little-endian interleaved layout the kernels stage
-    std::vector<uint8_t> pcm((size_t)n * c->C * c->B + 4);
+    std::vector<uint8_t> pcm((size_t)n * c->g.C * c->g.B + 4);
     for (uint32_t i = 0; i < n; i++)
-        for (uint32_t ch = 0; ch < c->C; ch++) {
+        for (uint32_t ch = 0; ch < c->g.C; ch++) {
             const uint32_t v = (uint32_t)planes[ch][i];
-            uint8_t *d = &pcm[((size_t)i * c->C + ch) * c->B];
-            for (uint32_t k = 0; k < c->B; k++) d[k] = (uint8_t)(v >> (8 * k));
+            uint8_t *d = &pcm[((size_t)i * c->g.C + ch) * c->g.B];
+            for (uint32_t k = 0; k < c->g.B; k++) d[k] = (uint8_t)(v >> (8 * k));
         }
     size_t len = 0;
     uint32_t fb = 0;
-    int rc = flacgpu_encode_frames(c, pcm.data(), c->B, n, frame_number, out, out_cap, &len, &fb);
+    int rc = flacgpu_encode_frames(c, pcm.data(), c->g.B, n, frame_number, out, out_cap, &len, &fb);
     if (rc) return rc;
     if (frame_bytes) *frame_bytes = fb;
     return FLACGPU_OK;
@@ -1282,11 +1162,11 @@ int flacgpu_plan_md5_engine(const flacgpu_plan *p) {
 int flacgpu_plan_create_segments(flacgpu_ctx *c, uint32_t n_streams, const uint64_t *offs, const uint64_t *samples,
                                  uint32_t bytes_per_sample, const uint64_t *first_frame_numbers,
                                  const uint8_t *final_segment, flacgpu_plan **out) {
-    if (!c || !out || (n_streams && (!offs || !samples)) || bytes_per_sample != c->B) return FLACGPU_ERR_INVALID_INPUT;
+    if (!c || !out || (n_streams && (!offs || !samples)) || bytes_per_sample != c->g.B) return FLACGPU_ERR_INVALID_INPUT;
     *out = nullptr;
     HIPCHK(hipSetDevice(c->device));
     const uint32_t bs = c->cfg.block_size;
-    const uint64_t fbytes_in = (uint64_t)c->C * c->B;
+    const uint64_t fbytes_in = (uint64_t)c->g.C * c->g.B;
     std::vector<FrameJob> full, tail;
     std::vector<uint64_t> lens(n_streams);
     uint64_t max_number = 0;
@@ -1339,7 +1219,7 @@ int flacgpu_plan_create_segments(flacgpu_ctx *c, uint32_t n_streams, const uint6
     p->n_frames = slot;
     p->n_full = full.size() - tail.size();
     p->n_tail = tail.size();
-    p->out_bound = slot * (uint64_t)c->image_bytes;
+    p->out_bound = slot * (uint64_t)c->g.image_bytes;
     auto fail = [&](int code) {
         flacgpu_plan_destroy(p);
         return code;
@@ -1361,7 +1241,7 @@ int flacgpu_plan_create_segments(flacgpu_ctx *c, uint32_t n_streams, const uint6
             if (hipMemcpy(p->d_md5_fin, final_segment, n_streams, hipMemcpyHostToDevice)) return fail(FLACGPU_ERR_DEVICE);
         }
     }
-    if (slot > c->max_frames && hipMalloc(&p->d_desc, slot * (uint64_t)c->desc_stride))
+    if (slot > c->max_frames && hipMalloc(&p->d_desc, slot * (uint64_t)c->g.desc_stride))
         return fail(FLACGPU_ERR_OUT_OF_MEMORY);
     *out = p;
     return FLACGPU_OK;
@@ -1426,7 +1306,7 @@ int flacgpu_encode_plan_device_ex(flacgpu_ctx *c, const flacgpu_plan *p, const v
         {
             Timed t(c, FLACGPU_K_MD5, ms);
             HIPCHK(launch_md5_streams((const uint8_t *)d_pcm, p->d_md5_offs, p->d_md5_lens, p->d_md5_fin, p->n_streams,
-                                      (Md5State *)d_md5_state, d_md5, ms, c->md5_kernel, c->md5_prio));
+                                      (Md5State *)d_md5_state, d_md5, ms, c->g.md5_kernel, c->k.md5_prio));
         }
         if (join) HIPCHK(hipEventRecord(c->join, ms));
     }
@@ -1434,8 +1314,8 @@ int flacgpu_encode_plan_device_ex(flacgpu_ctx *c, const flacgpu_plan *p, const v
     // auto: only for long chains (>= 4096 blocks per stream per call, e.g. c4's 4 x 96-KiB frames).  A
     // persistent grid cannot grow back, so the reserved slots idle once the MD5 is done; a shorter
     // chain started late (after the analysis) still ends before the pack
-    const bool reserve = c->md5_reserve > 0 || (c->md5_reserve < 0 && p->md5_max_len >= (256u << 10));
-    c->grid_reserve = (md5 && reserve) ? md5_workgroups(p->n_streams, c->md5_kernel) : 0u;
+    const bool reserve = c->k.md5_reserve > 0 || (c->k.md5_reserve < 0 && p->md5_max_len >= (256u << 10));
+    c->grid_reserve = (md5 && reserve) ? md5_workgroups(p->n_streams, c->g.md5_kernel) : 0u;
     int rc = encode_core(c, (const uint8_t *)d_pcm, p->d_jobs, p->n_full, p->n_tail, desc, d_frame_bytes, d_out,
                          out_cap, d_frame_offsets, d_total, st, p->full_slots.data());
     c->grid_reserve = 0;

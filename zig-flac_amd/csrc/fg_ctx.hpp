@@ -9,6 +9,7 @@
 
 #include "../../include/flacgpu.h"
 #include "fg_common.hpp"
+#include "fg_geom.hpp"
 #include "fg_md5_host.hpp"
 
 struct DecScratch;  // fg_dec_host.cpp: decode scratch of a context
@@ -23,38 +24,26 @@ struct TimedLaunch {
 
 }  // namespace fg
 
-// chunk sets of the pipelined host-buffer path (encode_pipelined): chunk i uploads into set i % 3
-// while chunk i-1 encodes and chunks i-2, i-3 download -- with two sets the upload of chunk i had
-// to wait for the encode of chunk i-2 and the encode for the download of chunk i-2, so a slow
-// download or a late host thread stalled both directions of PCIe (round-4 batches reached 33-44 GB/s
-// of H2D against 57 GB/s measured alone)
-constexpr uint32_t kPipeSets = 4;  // the most; flacgpu_ctx::pipe_sets is the number in use (2..4)
-constexpr uint32_t kPipeSetsDefault = 3;
-
 struct flacgpu_ctx {
     int device = 0;
     flacgpu_config cfg{};
     uint32_t max_frames = 0;
-    uint32_t C = 0, B = 0, bits = 0, stereo = 0, nt = 0, nt_pack = 0;
-    uint32_t image_bytes = 0, desc_stride = 0, lds = 0, lds_tail = 0, lds_pack = 0, crc_hmax = 0;
-    bool stage_dbuf = false;
-    bool pack_dbuf = false;
+    fg::Knobs k;    // the environment's knobs when the context was opened
+    fg::EncGeom g;  // kernel variants, thread counts, LDS and image sizes: enc_geometry(cfg, k)
+
+    // ---- streams and events ----
     hipStream_t stream = nullptr, aux = nullptr;
     hipStream_t dl = nullptr;  // download stream of the pipelined host-buffer path
     hipStream_t up = nullptr;  // its upload stream (chunk i+1's upload beside chunk i's encode)
-    hipEvent_t up_done[kPipeSets] = {};  // a chunk set's upload landed (GPU-side waits)
-    hipEvent_t set_done[kPipeSets] = {};  // a chunk set's encode finished (GPU-side waits)
-    hipEvent_t dl_done[kPipeSets] = {};   // a chunk set's frames downloaded (GPU-side waits)
-    uint32_t pipe_sets = kPipeSetsDefault;  // chunk sets in use (FLACGPU_PIPE_SETS = 2: the round-4 schedule; 4)
+    hipStream_t ovl = nullptr;  // overlapped encode: scan + pack of range i
     hipEvent_t fork = nullptr, join = nullptr;
-    // host waits of the pipelined host-buffer path (the download stream, the end; the chunk sets'
-    // own events are set_done below):
-    // blocking-sync events, so a waiting thread sleeps instead of spinning on a core the MD5 pool
-    // and the other files' threads need (FLACGPU_SPIN_SYNC=1: spinning events, A/B)
-    hipEvent_t hw[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<hipEvent_t> event_pool;
+
+    // ---- encode buffers ----
     uint16_t *d_crc_pow = nullptr, *d_crc_join = nullptr, *d_crc_pow4 = nullptr;
-    // full 16-bit two-channel frames are packed by k_pack4 (four waves per subframe): 512 threads
-    uint32_t nt_pack4 = 0, lds_pack4 = 0, crc_hmax4 = 0;
+    uint16_t *d_crc_pows = nullptr;  // CRC fold shifts for the split pack's thread count
+    uint16_t *d_crc_powf = nullptr;  // CRC fold shifts for the fused kernel's 256 threads
+    uint16_t *d_crc_x8 = nullptr;    // z^(8 * 2^i) mod P, i < 24
     uint32_t *d_err = nullptr, *d_ctr = nullptr;
     fg::FrameJob *d_jobs = nullptr;
     uint8_t *d_desc = nullptr;
@@ -64,61 +53,50 @@ struct flacgpu_ctx {
     uint64_t pcm_cap = 0;
     uint8_t *d_out = nullptr;
     uint64_t out_cap = 0;
-    fg::FrameRec *d_records = nullptr;
-    unsigned long long *d_stamps = nullptr;
-    bool records_on = false;
-    bool records_keep = false;  // encode_files with records: every file's records, concatenated
-    bool ana_split = false;  // full-frame analysis in channel halves (fg_device.hpp k_analyze)
-    bool pack_split = false;  // full-frame pack in channel halves (fg_packw.hpp k_packw<..., true>)
-    uint32_t nt_psplit = 0, lds_psplit = 0, image_split = 0, crc_hmaxs = 0;
-    uint16_t *d_crc_pows = nullptr;  // CRC fold shifts for the split pack's thread count
-    uint16_t *d_crc_x8 = nullptr;    // z^(8 * 2^i) mod P, i < 24
-    uint32_t nt_split = 0, lds_split = 0;
     uint64_t *d_scan_part = nullptr;  // per-4096-frame block sums of the multi-workgroup scan
     uint32_t scan_part_cap = 0;
-    std::vector<fg::FrameRec> h_records;
-    bool timing = false;
-    std::vector<fg::TimedLaunch> pending;
-    std::vector<hipEvent_t> event_pool;
-    uint64_t launches[FLACGPU_K_COUNT] = {};
-    double ms[FLACGPU_K_COUNT] = {};
-    // streaming MD5 (one stream): a host core by default (FLACGPU_MD5_HOST), or one GPU
-    // lane fed by bounded chunks (FLACGPU_MD5_DEVICE, opt-in)
-    int md5_engine = FLACGPU_MD5_HOST;
-    int md5_kernel = 1;  // batched stream MD5: 1 = coalesced LDS-DMA ring, 0 = per-lane loads (A/B knob)
-    int md5_prio = 0;    // issue priority of the MD5 waves beside the encode (A/B knob)
-    uint32_t enc_prio = 0;  // issue priority 1 for the C2 encode waves (A/B knob FLACGPU_ENC_PRIO)
-    int md5_reserve = -1;  // 1: the analysis grid leaves one workgroup slot per stream-MD5 workgroup
-                           //    queued beside it, 2: the pack grid too, 0: none, -1: auto (A/B knob)
+    uint64_t *d_status = nullptr;  // fused encode: per-slot status words, grow-only
+    uint64_t status_cap = 0;
+    uint64_t *d_cum = nullptr;  // [chunk] bytes of the frames before the chunk's slot range
     uint32_t grid_reserve = 0;  // per call: slots the next analysis / pack launches leave free
     // overlapped encode (encode_core): the full frames in `ovl_chunks` ranges, the analysis of
     // range i+1 on `stream` beside the scan + pack of range i on `ovl`, each grid capped to
-    // ovl_ana / ovl_pack workgroups per CU so both are resident on every CU
+    // ovl_ana / ovl_pack workgroups per CU so both are resident on every CU (flacgpu_set_overlap)
     uint32_t ovl_chunks = 0, ovl_ana = 2, ovl_pack = 2, ovl_min_frames = 4096;
-    bool xcd_queue = true;  // split analysis: per-XCD item queues (fg_device.hpp xcd_ticket)
-    bool pack_xcdq = true;  // split pack: the same (fg_packw.hpp)
-    // split analysis (bit 0) / pack (bit 1): each item's ticket taken right before its DMA, so a
-    // frame's two halves are staged close together (c4 A/B r4l: analysis 5.03 -> 4.95 ms, analysis
-    // traffic 1.82x -> 1.44x of the PCM (r4n); the pack's bit measured no gain, r4o)
-    uint32_t split_jit = 1;
-    // fused single-pass encode of full 16-bit stereo frames (fg_fused.hpp): analysis and pack in
-    // one kernel, frame offsets by an in-kernel look-back over per-slot status words
-    bool fused = false;
-    // one wave per full 16-bit stereo frame (fg_ana1.hpp k_ana1) instead of one per candidate
-    bool ana1 = false;
-    uint32_t ana1_variant = 1;
-    uint32_t lds_fused = 0, crc_hmaxf = 0;
-    uint16_t *d_crc_powf = nullptr;  // CRC fold shifts for its 256 threads
-    uint64_t *d_status = nullptr;    // per-slot status words, grow-only
-    uint64_t status_cap = 0;
-    hipStream_t ovl = nullptr;
-    uint64_t *d_cum = nullptr;  // [chunk] bytes of the frames before the chunk's slot range
+
+    // ---- pipelined host-buffer path (encode_pipelined) ----
+    hipEvent_t up_done[kPipeSets] = {};  // a chunk set's upload landed (GPU-side waits)
+    hipEvent_t set_done[kPipeSets] = {};  // a chunk set's encode finished (GPU-side waits)
+    hipEvent_t dl_done[kPipeSets] = {};   // a chunk set's frames downloaded (GPU-side waits)
+    // host waits of the pipelined host-buffer path (the download stream, the end; the chunk sets'
+    // own events are set_done above):
+    // blocking-sync events, so a waiting thread sleeps instead of spinning on a core the MD5 pool
+    // and the other files' threads need (FLACGPU_SPIN_SYNC=1: spinning events, A/B)
+    hipEvent_t hw[4] = {nullptr, nullptr, nullptr, nullptr};
+
+    // ---- decision records, kernel timing, clock stamps ----
+    fg::FrameRec *d_records = nullptr;
+    bool records_on = false;
+    bool records_keep = false;  // encode_files with records: every file's records, concatenated
+    std::vector<fg::FrameRec> h_records;
+    bool timing = false;
+    std::vector<fg::TimedLaunch> pending;
+    uint64_t launches[FLACGPU_K_COUNT] = {};
+    double ms[FLACGPU_K_COUNT] = {};
+    unsigned long long *d_stamps = nullptr;
+
+    // ---- MD5 ----
+    // streaming MD5 (one stream): a host core by default (FLACGPU_MD5_HOST), or one GPU
+    // lane fed by bounded chunks (FLACGPU_MD5_DEVICE, opt-in)
+    int md5_engine = FLACGPU_MD5_HOST;
     fg::HostMd5 host_md5;
     uint32_t *d_md5_state = nullptr;
     uint32_t *d_md5_blocks = nullptr;
     uint8_t md5_buf[64] = {};
     uint32_t md5_fill = 0;
     uint64_t md5_len = 0;
+
+    // ---- decoder scratch ----
     DecScratch *dec = nullptr;  // frame decoder / verifier: allocated by the first decode call
     IdxScratch *idx = nullptr;  // device frame index: allocated by the first index call
 };

@@ -86,7 +86,7 @@ int dec_scratch(flacgpu_ctx *c) {
         Carve v{base};
         v.take(c->max_frames, d->samp_off, d->exp_off, d->exp_number, d->d_foff, d->d_results);
         v.take(1, d->total);
-        v.take((uint64_t)c->max_frames * c->C, d->subs);
+        v.take((uint64_t)c->max_frames * c->g.C, d->subs);
         v.take(c->max_frames, d->blocks, d->body, d->exp_n, d->d_fbytes);
         v.take(16, d->ctl);
         return v.take(1, d->d_bad);
@@ -128,9 +128,9 @@ int dec_core(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff, co
     a.frame_off = d_foff;
     a.frame_bytes = d_fbytes;
     a.n_frames = n;
-    a.channels = c->C;
-    a.bits = c->bits;
-    a.bps = c->bits / 8u;
+    a.channels = c->g.C;
+    a.bits = c->g.bits;
+    a.bps = c->g.bits / 8u;
     a.rate = c->cfg.sample_rate;
     a.block = c->cfg.block_size;
     a.subs = d->subs;
@@ -152,7 +152,7 @@ int dec_core(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff, co
     }
     if (cs) {
         Timed t(c, FLACGPU_K_SCAN, st);
-        HIPCHK(launch_seg_offsets(cs->segs, cs->n_segs, d->blocks, cs->pcm_base, cs->pcm_cap, cs->carried, c->C * a.bps,
+        HIPCHK(launch_seg_offsets(cs->segs, cs->n_segs, d->blocks, cs->pcm_base, cs->pcm_cap, cs->carried, c->g.C * a.bps,
                                   d->exp_off, st));
     } else if (!d_pcm_off) {
         // consecutive blocks of one stream: sample offsets from the scan of the parsed block sizes
@@ -355,10 +355,10 @@ int streams_decode(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const Stre
         if (rc) return rc;
     }
     if (d_md5) {
-        HIPCHK(launch_streams_md5_lens(d_results, c->C * (c->bits / 8u), md5_lens, n, st));
+        HIPCHK(launch_streams_md5_lens(d_results, c->g.C * (c->g.bits / 8u), md5_lens, n, st));
         {
             Timed t(c, FLACGPU_K_MD5, st);
-            HIPCHK(launch_md5_streams(d_pcm_out, d_base, md5_lens, nullptr, n, nullptr, d_md5, st, c->md5_kernel, c->md5_prio));
+            HIPCHK(launch_md5_streams(d_pcm_out, d_base, md5_lens, nullptr, n, nullptr, d_md5, st, c->g.md5_kernel, c->k.md5_prio));
         }
         HIPCHK(launch_streams_md5_mask(d_results, d_md5, n, st));
     }
@@ -376,7 +376,7 @@ int decode_chunk(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff
                  F overlap) {
     DecScratch *d = c->dec;
     hipStream_t st = c->stream;
-    const uint64_t per = (uint64_t)c->C * (c->bits / 8u), need = (uint64_t)n * c->cfg.block_size * per;
+    const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u), need = (uint64_t)n * c->cfg.block_size * per;
     HIPCHK(grow(d->d_pcm, d->pcm_cap, need));  // the chunk before this one was waited for
     HIPCHK(hipMemsetAsync(d->d_pcm, 0, need, st));
     const int rc = dec_core(c, d_frames, d_foff, d_fbytes, n, nullptr, d->d_pcm, need, nullptr, false,
@@ -605,7 +605,7 @@ int fg::decode_files_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *
     hipStream_t st = c->stream;
     IdxScratch *x = idx_scratch(c);
     if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
-    const uint64_t per = (uint64_t)c->C * (c->bits / 8u);
+    const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u);
     std::vector<uint64_t> offs, lens, pcm_offs, pcm_caps;
     std::vector<idx::IndexResult> ires;
     std::vector<streams::StreamResult> res;
