@@ -75,38 +75,46 @@ def _wave(n, amp, seed):
     return [int(amp * math.sin(0.05 * i + seed) + rng.randrange(-3, 4)) for i in range(n)]
 
 
+def interleave(planes, bits: int) -> bytes:
+    """Channels of integer samples -> interleaved little-endian PCM of bits / 8 bytes a sample."""
+    return b"".join((v & ((1 << bits) - 1)).to_bytes(bits // 8, "little") for row in zip(*planes) for v in row)
+
+
 def hand_built():
+    """Each with "pcm": the samples the frame was written from, known without any decoder."""
     out = []
 
-    def add(name, ch, bits, number, bs, chc, writer):
+    def add(name, ch, bits, number, bs, chc, writer, planes):
         marks = {}
         fr = fb.frame(number, bs, chc, bits, lambda w: writer(w, marks), marks)
-        out.append({"name": name, "channels": ch, "bits": bits, "number": number, "block": bs, "frame": fr, "marks": marks})
+        assert len(planes) == ch and all(len(p) == bs for p in planes)
+        out.append({"name": name, "channels": ch, "bits": bits, "number": number, "block": bs, "frame": fr, "marks": marks,
+                    "pcm": interleave(planes, bits)})
 
     # LPC order 32, precision 15
     x = _wave(192, 9000, 1)
     rng = random.Random(2)
     coefs = [rng.randrange(-900, 900) for _ in range(32)]
     coefs[0] = 16000
-    add("lpc32_prec15", 1, 16, 5, 192, 0, lambda w, m: fb.sub_lpc(w, x, 16, coefs, 15, 14, 0, 1, [9, 10]))
+    add("lpc32_prec15", 1, 16, 5, 192, 0, lambda w, m: fb.sub_lpc(w, x, 16, coefs, 15, 14, 0, 1, [9, 10]), [x])
     # an escape partition of width 0 (all-zero residuals) beside a Rice one
     x2 = [7] * 64 + _wave(64, 500, 3)
     x2[64] = 7
     add("escape_width0", 1, 16, 6, 128, 0,
-        lambda w, m: fb.sub_fixed(w, x2, 16, 1, 0, 1, [("esc", 0), 8]))
+        lambda w, m: fb.sub_fixed(w, x2, 16, 1, 0, 1, [("esc", 0), 8]), [x2])
     # method 1 (5-bit parameters) with k = 20
     rng3 = random.Random(4)
     x3 = [rng3.randrange(-(1 << 22), 1 << 22) for _ in range(64)]
-    add("method1_k20", 1, 24, 7, 64, 0, lambda w, m: fb.sub_fixed(w, x3, 24, 0, 1, 0, [20]))
+    add("method1_k20", 1, 24, 7, 64, 0, lambda w, m: fb.sub_fixed(w, x3, 24, 0, 1, 0, [20]), [x3])
     # FIXED order 4 in a 16-sample block, partition order 0
     x4 = _wave(16, 300, 5)
-    add("fixed4_block16", 1, 16, 8, 16, 0, lambda w, m: fb.sub_fixed(w, x4, 16, 4, 0, 0, [4], m))
+    add("fixed4_block16", 1, 16, 8, 16, 0, lambda w, m: fb.sub_fixed(w, x4, 16, 4, 0, 0, [4], m), [x4])
     # CONSTANT with wasted bits
-    add("constant_waste", 1, 16, 9, 100, 0, lambda w, m: fb.sub_constant(w, -1024, 16, waste=3))
+    add("constant_waste", 1, 16, 9, 100, 0, lambda w, m: fb.sub_constant(w, -1024, 16, waste=3), [[-1024] * 100])
     # block 4096, partition order 8 (16-sample partitions, the first with 12 residuals), FIXED order 4
     x6 = _wave(4096, 12000, 6)
     add("fixed4_porder8", 1, 16, 10, 4096, 0,
-        lambda w, m: fb.sub_fixed(w, x6, 16, 4, 0, 8, [5 + (p % 3) for p in range(256)]))
+        lambda w, m: fb.sub_fixed(w, x6, 16, 4, 0, 8, [5 + (p % 3) for p in range(256)]), [x6])
     # mid/side with odd side samples
     left = _wave(64, 1000, 7)
     right = [v + 2 * (i % 5) + 1 for i, v in enumerate(left)]  # left - right odd
@@ -117,7 +125,7 @@ def hand_built():
         fb.sub_fixed(w, mid, 16, 2, 0, 0, [6])
         fb.sub_fixed(w, side, 17, 1, 0, 0, [3])
 
-    add("midside_odd", 2, 16, 11, 64, 10, ms)
+    add("midside_odd", 2, 16, 11, 64, 10, ms, [left, right])
     return out
 
 

@@ -128,10 +128,12 @@ def fixed_residual(x, order: int):
     return [x[i] - sum(cj * x[i - 1 - j] for j, cj in enumerate(c)) for i in range(order, len(x))]
 
 
-def sub_fixed(w, x, bps: int, order: int, method: int, porder: int, params, marks=None):
-    sub_header(w, 8 + order, 0)
+def sub_fixed(w, x, bps: int, order: int, method: int, porder: int, params, marks=None, waste: int = 0):
+    """9.2.5; waste: x holds multiples of 2^waste, coded as x >> waste at bps - waste bits."""
+    sub_header(w, 8 + order, waste)
+    x = [v >> waste for v in x]
     for v in x[:order]:
-        w.s(v, bps)
+        w.s(v, bps - waste)
     residual(w, fixed_residual(x, order), len(x), order, method, porder, params, marks)
 
 
@@ -140,11 +142,13 @@ def lpc_residual(x, coefs, shift: int):
     return [x[i] - (sum(c * x[i - 1 - j] for j, c in enumerate(coefs)) >> shift) for i in range(o, len(x))]
 
 
-def sub_lpc(w, x, bps: int, coefs, prec: int, shift: int, method: int, porder: int, params):
+def sub_lpc(w, x, bps: int, coefs, prec: int, shift: int, method: int, porder: int, params, waste: int = 0):
+    """9.2.6; waste as in sub_fixed."""
     order = len(coefs)
-    sub_header(w, 32 + order - 1, 0)
+    sub_header(w, 32 + order - 1, waste)
+    x = [v >> waste for v in x]
     for v in x[:order]:
-        w.s(v, bps)
+        w.s(v, bps - waste)
     w.u(prec - 1, 4)
     w.s(shift, 5)
     for c in coefs:
@@ -152,20 +156,50 @@ def sub_lpc(w, x, bps: int, coefs, prec: int, shift: int, method: int, porder: i
     residual(w, lpc_residual(x, coefs, shift), len(x), order, method, porder, params)
 
 
-def frame(number: int, bs: int, channel_assign: int, bits: int, write_subframes, marks=None) -> bytes:
-    """9.1 + 9.3: header (44.1 kHz, fixed block size, block size as an 8- or 16-bit field),
-    write_subframes(w), zero padding, CRC-16.  marks: "pad_bits", "pad_pos", "hdr_bytes"."""
+def block_size_code(bs: int) -> int:
+    """9.1.1: the table code of a block size that has one (1: 192, 2..5: 576 * 2^n, 8..15:
+    256 * 2^n), else 6 / 7 (the size follows the coded number as an 8- / 16-bit field)."""
+    if bs == 192:
+        return 1
+    for n in range(4):
+        if bs == 576 << n:
+            return 2 + n
+    for n in range(8):
+        if bs == 256 << n:
+            return 8 + n
+    return 6 if bs <= 256 else 7
+
+
+# 9.1.2: the sample rates of codes 1..11 (0: from STREAMINFO; 12: kHz in 8 bits, 13: Hz in 16 bits,
+# 14: tens of Hz in 16 bits, each after the block-size field)
+RATE_OF_CODE = {1: 88200, 2: 176400, 3: 192000, 4: 8000, 5: 16000, 6: 22050, 7: 24000, 8: 32000, 9: 44100, 10: 48000,
+                11: 96000}
+
+
+def frame(number: int, bs: int, channel_assign: int, bits: int, write_subframes, marks=None, *, table_bs: bool = False,
+          rate_code: int = 9, rate_field: int = 0, bits_code=None, variable: bool = False) -> bytes:
+    """9.1 + 9.3: header, write_subframes(w), zero padding, CRC-16.  By default 44.1 kHz, fixed
+    block size, the block size as an 8- or 16-bit field.  table_bs: the block size's table code
+    where it has one; rate_code 0..14, rate_field the value of the field codes 12..14 carry;
+    bits_code: the bit-depth code (0: from STREAMINFO) instead of the one of `bits`; variable: the
+    blocking-strategy bit set, `number` then being the frame's first sample number (36 bits).
+    marks: "pad_bits", "pad_pos", "hdr_bytes"."""
+    bsc = block_size_code(bs) if table_bs else (6 if bs <= 256 else 7)
+    assert 0 <= rate_code <= 14 and 0 <= number < (1 << 36)
     w = BitWriter()
     w.u(0x7FFC, 15)
-    w.u(0, 1)
-    w.u(6 if bs <= 256 else 7, 4)
-    w.u(9, 4)
+    w.u(1 if variable else 0, 1)
+    w.u(bsc, 4)
+    w.u(rate_code, 4)
     w.u(channel_assign, 4)
-    w.u(BITS_CODE[bits], 3)
+    w.u(BITS_CODE[bits] if bits_code is None else bits_code, 3)
     w.u(0, 1)
     for b in utf8_number(number):
         w.u(b, 8)
-    w.u(bs - 1, 8 if bs <= 256 else 16)
+    if bsc in (6, 7):
+        w.u(bs - 1, 8 if bsc == 6 else 16)
+    if rate_code >= 12:
+        w.u(rate_field, 8 if rate_code == 12 else 16)
     w.u(crc8(w.bytes()), 8)
     hdr = w.pos // 8
     write_subframes(w)

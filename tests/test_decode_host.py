@@ -88,6 +88,7 @@ def test_hand_built_frames_decode(exe, tmp_path):
     for h in dc.hand_built():
         res, got = run_host(exe, tmp_path, [h["frame"]], h["channels"], h["bits"], 44100)
         assert res["status"] == [0] and res["block"] == [h["block"]] and res["number"] == [h["number"]], h["name"]
+        assert got == h["pcm"], h["name"]  # the samples the frame was written from
         assert got == dc.oracle_pcm(h["frame"], h["channels"], h["bits"], 44100, h["number"]), h["name"]
 
 

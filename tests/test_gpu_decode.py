@@ -167,6 +167,7 @@ def test_hand_built_frames():
         with _decoder(h["channels"], h["bits"], max_frames=4) as d:
             got, res = d.decode_frames(h["frame"], [len(h["frame"])])
         assert res[0].status == 0 and res[0].number == h["number"] and res[0].block_size == h["block"], h["name"]
+        assert got == h["pcm"], h["name"]  # the samples the frame was written from
         assert got == want, h["name"]
 
 
