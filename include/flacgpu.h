@@ -542,6 +542,73 @@ int flacgpu_decode_streams_device(flacgpu_ctx *ctx, const uint8_t *d_data, uint3
 int flacgpu_decode_files(flacgpu_ctx *ctx, uint32_t n_files, const void *const *flac, const size_t *len,
                          uint8_t *const *pcm_out, const size_t *pcm_cap, uint64_t *n_samples, int *md5_ok,
                          int *status);
+/* The sample positions of n_streams (<= 65535) streams that flacgpu_flac_index_streams_device has
+ * indexed (same d_data, table_first, table_caps, stream_bits, stream_rates; the two tables and
+ * d_index_results as that call left them): d_frame_first_sample[table_first[s] + i] = the
+ * interchannel samples before frame i of stream s, d_stream_samples[s] = the stream's total (both
+ * device memory; the first is laid out like the frame tables).  A frame's block size is what its
+ * header states, read from at most 16 bytes at its offset with no regard to the context's channel
+ * count, depth or block size; positions are the exclusive sum of the block sizes, never the coded
+ * frame or sample number.  A stream whose index result is not OK gets total 0 and none of its
+ * entries written.  The table is the caller's to keep: a batch that stays resident is indexed and
+ * scanned once and serves any number of flacgpu_decode_windows_device calls.  Asynchronous on
+ * hip_stream, no host synchronisation (but when the context's scratch has to grow): the frame
+ * counts are read on the device, the grids are sized from table_caps; independent of
+ * max_frames_per_call.  Timed as FLACGPU_K_SCAN. */
+int flacgpu_flac_positions_streams_device(flacgpu_ctx *ctx, const uint8_t *d_data, uint32_t n_streams,
+                                          const uint64_t *table_first, const uint64_t *table_caps,
+                                          const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                          const flacgpu_index_result *d_index_results,
+                                          const uint32_t *stream_bits, const uint32_t *stream_rates,
+                                          uint64_t *d_frame_first_sample, uint64_t *d_stream_samples, void *hip_stream);
+/* Decode n_windows (<= 65535, more: FLACGPU_ERR_INVALID_INPUT) sample windows of indexed streams
+ * without decoding the rest: window w is samples [window_start[w], + window_count[w]) of stream
+ * window_stream[w] (< n_streams, else FLACGPU_ERR_INVALID_INPUT), clipped to the stream's total; a
+ * window that starts at or past the end or has count 0 is OK with 0 samples and 0 frames.  Its
+ * bytes go to d_pcm_out + pcm_offsets[w] (any alignment) and are exactly those the whole decode
+ * of the stream puts at [start * per, (start + n_samples) * per), per = channels * bytes per
+ * sample.  Windows may share a stream and overlap.  Only the frames that hold a window's samples
+ * (found by binary search of the positions) are parsed past their header and reconstructed, whole,
+ * into scratch the context owns, in chunks of max_frames_per_call that run on from one window
+ * into the next; one copy pass then delivers each window's bytes.  So a frame this context cannot
+ * decode harms no window that does not cover it.  d_results[w] (device memory): BAD_INDEX where
+ * the stream's index result is not OK, BAD_FRAME where a covering frame has a non-zero decode
+ * status (first_bad_frame counted in the stream), TOO_SMALL where n_samples * per > pcm_caps[w];
+ * each of the three delivers 0 samples and writes nothing, and nothing is ever written outside
+ * [pcm_offsets[w], + n_samples * per).  The window and pcm arrays and table_first are host memory.
+ * The call waits for hip_stream ONCE, to read the covers; everything after that is only queued.
+ * The cover is timed as FLACGPU_K_SCAN, parse and reconstruct as in every decode, the copy is not. */
+enum { FLACGPU_WINDOW_OK = 0, FLACGPU_WINDOW_BAD_INDEX = 1, FLACGPU_WINDOW_BAD_FRAME = 2, FLACGPU_WINDOW_TOO_SMALL = 3 };
+typedef struct {                 /* 32 bytes, device memory */
+    uint64_t n_samples;          /* interchannel samples delivered */
+    uint64_t first_frame;        /* first covering frame, counted in its stream */
+    uint32_t n_frames;           /* covering frames decoded */
+    uint32_t status;             /* FLACGPU_WINDOW_* */
+    uint32_t first_bad_frame;    /* BAD_FRAME: counted in its stream; else 0xFFFFFFFF */
+    uint32_t first_bad_status;   /* FLACGPU_DEC_* of that frame */
+} flacgpu_window_result;
+int flacgpu_decode_windows_device(flacgpu_ctx *ctx, const uint8_t *d_data,
+                                  uint32_t n_streams, const uint64_t *table_first,
+                                  const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                  const flacgpu_index_result *d_index_results,
+                                  const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
+                                  uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
+                                  const uint64_t *window_count,
+                                  uint8_t *d_pcm_out, const uint64_t *pcm_offsets, const uint64_t *pcm_caps,
+                                  flacgpu_window_result *d_results, void *hip_stream);
+/* Windows of whole files in host memory: window w is samples [window_start[w], + window_count[w])
+ * of file window_file[w] (< n_files), delivered to pcm_out[w] (capacity pcm_cap[w]) with
+ * n_samples[w].  Metadata is parsed on the host as in flacgpu_decode_files; the good files' frames
+ * are uploaded into one device buffer, indexed and scanned there, and only the windows' bytes and
+ * results come back.  status[w]: 0; the code flacgpu_decode_file gives for a file with bad
+ * metadata, another channel count or depth; FLACGPU_ERR_INVALID_INPUT where the device index
+ * refuses the file (there is no second try through the host index) or a covering frame is
+ * damaged; FLACGPU_ERR_OUTPUT_TOO_SMALL.  No MD5: a window has none.  The return value is for the
+ * call's own errors only. */
+int flacgpu_decode_files_windows(flacgpu_ctx *ctx, uint32_t n_files, const void *const *flac, const size_t *len,
+                                 uint32_t n_windows, const uint32_t *window_file, const uint64_t *window_start,
+                                 const uint64_t *window_count, uint8_t *const *pcm_out, const size_t *pcm_cap,
+                                 uint64_t *n_samples, int *status);
 
 /* ---- Instrumentation ---------------------------------------------------- */
 /* Kernel ids for flacgpu_kernel_time: frame analysis (4096-sample frames /

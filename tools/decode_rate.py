@@ -23,6 +23,16 @@ alternated, best of 3 each after one warm call each, the MD5 engine the batch ch
 bytes in HBM (HIP events, warm-up, the median).
 
     python tools/decode_rate.py --legs files --files-out profiles/decode_files_rate.json
+
+The windows leg (--windows-out) takes the same 64 files of 256 frames and one window of 65536
+samples per file, starting at a sample that is no multiple of the block size:
+flacgpu_decode_windows_device from tables and positions that stay resident against
+flacgpu_decode_streams_device on the same bytes (HIP events, the two alternated, the median), the
+positions call alone, flacgpu_decode_files_windows against flacgpu_decode_files end to end (wall
+clock, alternated, best of 3 each after one warm call each), and a call of windows that cover
+whole streams with its timed kernels, whose difference bounds the copy pass.
+
+    python tools/decode_rate.py --legs windows --windows-out profiles/decode_windows_rate.json
 """
 import argparse
 import ctypes
@@ -353,6 +363,173 @@ def files_rate(n_files: int, frames_each: int, warmup: int, repeats: int) -> dic
     return res
 
 
+def windows_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: int) -> dict:
+    import numpy as np
+    import torch
+
+    import flacgpu
+    import synth
+
+    ch, bits, rate, _ = PRESETS["c2"]
+    per = ch * (bits // 8)
+    dev = torch.device("cuda", 0)
+    unit = synth.synth_pcm(64 * 4096, ch, bits, rate)
+    n_each = frames_each * 4096
+    pcm = (unit * ((frames_each + 63) // 64))[: n_each * per]
+    start = (n_each // 3 // 4096) * 4096 + 1234  # not a multiple of the block size
+    assert start % 4096 and start + window <= n_each
+    want = pcm[start * per:(start + window) * per]
+    L = flacgpu.load_library()
+    with flacgpu.Encoder(ch, bits, rate, device=0, max_frames=n_files * frames_each) as enc:
+        flacs = enc.encode_files([pcm] * n_files)
+        first = flacgpu.flac_index(flacs[0])[1]
+        # ---- resident: the files' frames in one HBM buffer, indexed and scanned once ----
+        bodies = [f[first:] for f in flacs]
+        offs, at = [], 0
+        for b in bodies:
+            offs.append(at)
+            at += (len(b) + 63) & ~63
+        host = np.zeros(at + 16, dtype=np.uint8)
+        for o, b in zip(offs, bodies):
+            host[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        d_buf = torch.from_numpy(host).to(dev)
+        lens = [len(b) for b in bodies]
+        caps = [n // 8 + 1 for n in lens]
+        tfirst = [int(v) for v in np.cumsum([0] + caps)[:-1]]
+        d_off = torch.zeros(sum(caps), dtype=torch.int64, device=dev)
+        d_fb = torch.zeros(sum(caps), dtype=torch.int32, device=dev)
+        d_pos = torch.zeros(sum(caps), dtype=torch.int64, device=dev)
+        d_tot = torch.zeros(n_files, dtype=torch.int64, device=dev)
+        d_ir = torch.zeros(16 * n_files, dtype=torch.uint8, device=dev)
+        d_wres = torch.zeros(32 * n_files, dtype=torch.uint8, device=dev)
+        d_sres = torch.zeros(32 * n_files, dtype=torch.uint8, device=dev)
+        d_win = torch.zeros(n_files * window * per, dtype=torch.uint8, device=dev)
+        d_all = torch.zeros(n_files * len(pcm), dtype=torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        sbits, srates = [bits] * n_files, [rate] * n_files
+        enc.flac_index_streams_device(d_buf.data_ptr(), offs, lens, tfirst, caps, d_off.data_ptr(), d_fb.data_ptr(),
+                                      d_ir.data_ptr(), stream_bits=sbits, stream_rates=srates, stream=st)
+
+        def positions():
+            enc.flac_positions_streams_device(d_buf.data_ptr(), tfirst, caps, d_off.data_ptr(), d_fb.data_ptr(),
+                                              d_ir.data_ptr(), d_pos.data_ptr(), d_tot.data_ptr(), stream_bits=sbits,
+                                              stream_rates=srates, stream=st)
+
+        crops = [(i, start, window) for i in range(n_files)]
+        crop_offs, crop_caps = [i * window * per for i in range(n_files)], [window * per] * n_files
+        wholes = [(i, 0, n_each) for i in range(n_files)]
+        whole_offs, whole_caps = [i * len(pcm) for i in range(n_files)], [len(pcm)] * n_files
+
+        def windows(wins, w_offs, w_caps, d_out):
+            enc.decode_windows_device(d_buf.data_ptr(), tfirst, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(),
+                                      d_pos.data_ptr(), d_tot.data_ptr(), wins, d_out.data_ptr(), w_offs, w_caps,
+                                      d_wres.data_ptr(), stream=st)
+
+        def streams():
+            enc.decode_streams_device(d_buf.data_ptr(), offs, lens, d_all.data_ptr(), whole_offs, whole_caps,
+                                      d_sres.data_ptr(), stream_bits=sbits, stream_rates=srates, stream=st)
+
+        def event_ms(fn):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            return a.elapsed_time(b)
+
+        def summary(ms):
+            return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
+
+        def window_results():
+            raw = d_wres.cpu().numpy().tobytes()
+            return [(r.status, r.n_samples) for r in (flacgpu.WindowResult * n_files).from_buffer_copy(raw)]
+
+        for _ in range(warmup):
+            positions()
+            windows(crops, crop_offs, crop_caps, d_win)
+            streams()
+        enc.sync_check(st)
+        assert window_results() == [(0, window)] * n_files
+        got = d_win.cpu().numpy().tobytes()
+        assert all(got[o:o + len(want)] == want for o in crop_offs), "a window differs from the PCM it was cut from"
+        ms_pos = [event_ms(positions) for _ in range(repeats)]
+        ms_win, ms_all = [], []
+        for _ in range(repeats):  # the two alternated
+            ms_win.append(event_ms(lambda: windows(crops, crop_offs, crop_caps, d_win)))
+            ms_all.append(event_ms(streams))
+        res = {"files": n_files, "frames_per_file": frames_each, "channels": ch, "bits": bits, "window_samples": window,
+               "window_start": start, "flac_bytes": sum(lens), "pcm_bytes": n_files * len(pcm),
+               "window_bytes": n_files * window * per,
+               "positions": summary(ms_pos), "decode_windows_device": summary(ms_win), "decode_streams_device": summary(ms_all)}
+        res["decode_windows_device"]["x_decode_streams_device"] = res["decode_streams_device"]["ms_median"] / res["decode_windows_device"]["ms_median"]
+        # the copy: windows that cover whole streams do everything decode_streams_device does but the
+        # index, plus the copy pass; events around the call, and the timed kernels of the same call
+        # in a pass of their own.  The call less its timed kernels is an upper bound of the copy (it
+        # holds the one wait, the uploads, the small kernels and the gaps between launches too).
+        windows(wholes, whole_offs, whole_caps, d_all)
+        enc.sync_check(st)
+        assert window_results() == [(0, n_each)] * n_files
+        assert d_all[:len(pcm)].cpu().numpy().tobytes() == pcm and d_all[-len(pcm):].cpu().numpy().tobytes() == pcm
+        ms_whole = [event_ms(lambda: windows(wholes, whole_offs, whole_caps, d_all)) for _ in range(repeats)]
+        enc.set_timing(True)
+        enc.reset_timing()
+        for _ in range(repeats):
+            windows(wholes, whole_offs, whole_caps, d_all)
+        enc.sync_check(st)
+        kernels = {name: enc.kernel_time(k)[1] / repeats for name, k in
+                   (("scan_ms", flacgpu.K_SCAN), ("parse_ms", flacgpu.K_DEC_PARSE), ("recon_ms", flacgpu.K_DEC_RECON))}
+        enc.set_timing(False)
+        res["whole_stream_windows"] = dict(summary(ms_whole), **kernels)
+        copy_ms = statistics.median(ms_whole) - sum(kernels.values())
+        res["whole_stream_windows"]["copy_ms_upper_bound"] = copy_ms
+        res["whole_stream_windows"]["copy_gb_per_s_at_least"] = 2 * n_files * len(pcm) / copy_ms / 1e6  # read + write
+
+        # ---- end to end from host memory: the windows against the whole files, alternated ----
+        P = ctypes.c_void_p
+        srcs = [ctypes.create_string_buffer(f, len(f)) for f in flacs]
+        outs = [ctypes.create_string_buffer(len(pcm)) for _ in flacs]
+        wouts = [ctypes.create_string_buffer(window * per) for _ in flacs]
+        a_src = (P * n_files)(*[ctypes.addressof(b) for b in srcs])
+        a_out = (P * n_files)(*[ctypes.addressof(b) for b in outs])
+        a_wout = (P * n_files)(*[ctypes.addressof(b) for b in wouts])
+        a_len = (ctypes.c_size_t * n_files)(*[len(f) for f in flacs])
+        a_cap = (ctypes.c_size_t * n_files)(*[len(pcm)] * n_files)
+        a_wcap = (ctypes.c_size_t * n_files)(*[window * per] * n_files)
+        w_file = (ctypes.c_uint32 * n_files)(*range(n_files))
+        w_start = (ctypes.c_uint64 * n_files)(*[start] * n_files)
+        w_count = (ctypes.c_uint64 * n_files)(*[window] * n_files)
+        ns = (ctypes.c_uint64 * n_files)()
+        ok = (ctypes.c_int * n_files)()
+        status = (ctypes.c_int * n_files)()
+
+        def files_windows():
+            t = time.perf_counter()
+            rc = L.flacgpu_decode_files_windows(enc.ctx, n_files, a_src, a_len, n_files, w_file, w_start, w_count, a_wout,
+                                                a_wcap, ns, status)
+            dt = time.perf_counter() - t
+            assert rc == 0 and list(status) == [0] * n_files and list(ns) == [window] * n_files
+            return dt
+
+        def files_whole():
+            t = time.perf_counter()
+            rc = L.flacgpu_decode_files(enc.ctx, n_files, a_src, a_len, a_out, a_cap, ns, ok, status)
+            dt = time.perf_counter() - t
+            assert rc == 0 and list(status) == [0] * n_files and list(ok) == [1] * n_files
+            return dt
+
+        files_windows()  # one warm call each: the allocations
+        files_whole()
+        assert all(o.raw == want for o in wouts) and all(o.raw == pcm for o in outs)
+        t_win, t_all = [], []
+        for _ in range(3):
+            t_win.append(files_windows())
+            t_all.append(files_whole())
+        res["decode_files_windows"] = {"seconds_best_of_3": min(t_win), "seconds": t_win}
+        res["decode_files"] = {"seconds_best_of_3": min(t_all), "seconds": t_all}
+        res["decode_files_windows"]["x_decode_files"] = min(t_all) / min(t_win)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dec_rate.json"))
@@ -360,11 +537,21 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--legs", choices=("all", "decode", "index", "files"), default="all")
+    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows"), default="all")
+    ap.add_argument("--windows-out", default=os.path.join(ROOT, "profiles", "decode_windows_rate.json"))
+    ap.add_argument("--window", type=int, default=65536)
     ap.add_argument("--files-out", default=os.path.join(ROOT, "profiles", "decode_files_rate.json"))
     ap.add_argument("--files", type=int, default=64)
     ap.add_argument("--index-out", default=os.path.join(ROOT, "profiles", "index_rate.json"))
     a = ap.parse_args()
+    if a.legs in ("all", "windows"):
+        wr = {"c2": windows_rate(a.files, a.frames // a.files, a.window, a.warmup, a.repeats)}
+        print(json.dumps({"windows": wr}), flush=True)
+        with open(a.windows_out, "w") as f:
+            json.dump(wr, f, indent=1)
+            f.write("\n")
+        if a.legs == "windows":
+            return
     if a.legs in ("all", "files"):
         fr = {"c2": files_rate(a.files, a.frames // a.files, a.warmup, a.repeats)}
         print(json.dumps({"files": fr}), flush=True)

@@ -135,6 +135,12 @@ namespace streams {
 struct Segment;
 struct StreamResult;
 }
+namespace window {
+struct PosStream;
+struct WindowArg;
+struct Cover;
+struct WindowResult;
+}
 
 // shared by the translation units that include this header, not exported from libflacgpu.so
 #define FG_LOCAL __attribute__((visibility("hidden")))
@@ -166,6 +172,19 @@ hipError_t launch_seg_fold(const streams::Segment *segs, uint32_t n_segs, const 
                            streams::StreamResult *res, hipStream_t st);
 hipError_t launch_streams_md5_lens(const streams::StreamResult *res, uint32_t per, uint64_t *lens, uint32_t n, hipStream_t st);
 hipError_t launch_streams_md5_mask(const streams::StreamResult *res, uint8_t *digests, uint32_t n, hipStream_t st);
+// fg_window.hip
+hipError_t launch_positions(const uint8_t *data, const window::PosStream *d_streams, uint32_t n_streams, uint64_t max_cap,
+                            const uint64_t *f_off, const uint32_t *f_bytes, const idx::IndexResult *ires, uint64_t *pos,
+                            uint64_t *totals, hipStream_t st);
+hipError_t launch_window_cover(const window::WindowArg *args, const idx::IndexResult *ires, const uint64_t *pos,
+                               const uint64_t *totals, uint32_t per, window::Cover *recs, uint32_t n, hipStream_t st);
+hipError_t launch_window_init(const window::Cover *recs, streams::StreamResult *res, uint64_t *carried, uint32_t n,
+                              hipStream_t st);
+hipError_t launch_window_copy(const window::Cover *recs, const streams::StreamResult *res, const uint8_t *scratch,
+                              const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off, uint32_t per, uint32_t n,
+                              uint64_t max_bytes, hipStream_t st);
+hipError_t launch_window_results(const window::Cover *recs, const streams::StreamResult *res, window::WindowResult *out,
+                                 uint32_t n, hipStream_t st);
 // fg_misc.hip
 hipError_t launch_md5_streams(const uint8_t *base, const uint64_t *offs, const uint64_t *lens, const uint8_t *fin,
                               uint32_t n, Md5State *states, uint8_t *digests, hipStream_t st, int kernel, int prio);

@@ -215,4 +215,74 @@ int flacgpu_decode_files(flacgpu_ctx *ctx, uint32_t n_files, const void *const *
     return FLACGPU_OK;
 }
 
+// The files whose metadata and stream parameters are good go through the device in one batch
+// (fg_dec_host.cpp decode_files_windows_resident) with the windows that name them; a window of
+// another file gets that file's status.
+int flacgpu_decode_files_windows(flacgpu_ctx *ctx, uint32_t n_files, const void *const *flac, const size_t *len,
+                                 uint32_t n_windows, const uint32_t *window_file, const uint64_t *window_start,
+                                 const uint64_t *window_count, uint8_t *const *pcm_out, const size_t *pcm_cap,
+                                 uint64_t *n_samples, int *status) {
+    if (!ctx || n_windows > 65535u || (n_files && (!flac || !len)) ||
+        (n_windows && (!window_file || !window_start || !window_count || !pcm_out || !pcm_cap || !n_samples || !status)))
+        return FLACGPU_ERR_INVALID_INPUT;
+    for (uint32_t w = 0; w < n_windows; w++)
+        if (window_file[w] >= n_files || (pcm_cap[w] && !pcm_out[w])) return FLACGPU_ERR_INVALID_INPUT;
+    if (n_windows == 0) return FLACGPU_OK;
+    flacgpu_config cfg;
+    int rc = flacgpu_get_config(ctx, &cfg);
+    if (rc) return rc;
+    constexpr uint32_t kUnused = 0xFFFFFFFFu;
+    std::vector<int> file_status(n_files, FLACGPU_OK);
+    std::vector<uint32_t> slot(n_files, kUnused), bits, rates;  // slot: the file's place in the batch
+    std::vector<const uint8_t *> ptr;
+    std::vector<size_t> lens;
+    for (uint32_t i = 0; i < n_files; i++) {
+        flacgpu_streaminfo si;
+        size_t first = 0;
+        if (!flac[i]) {
+            file_status[i] = FLACGPU_ERR_INVALID_INPUT;
+            continue;
+        }
+        const uint8_t *p = (const uint8_t *)flac[i];
+        file_status[i] = parse_metadata(p, len[i], &si, &first);
+        if (file_status[i]) continue;
+        if (si.channels != cfg.channels || si.bit_depth != cfg.bits_per_sample) {
+            file_status[i] = FLACGPU_ERR_INVALID_INPUT;
+            continue;
+        }
+        slot[i] = (uint32_t)ptr.size();
+        bits.push_back(si.bit_depth);
+        rates.push_back(si.sample_rate);
+        ptr.push_back(p + first);
+        lens.push_back(len[i] - first);
+    }
+    std::vector<uint32_t> which, w_slot;  // the batch's windows: window index, its file's slot
+    std::vector<uint64_t> w_start, w_count, w_cap;
+    std::vector<uint8_t *> w_out;
+    for (uint32_t w = 0; w < n_windows; w++) {
+        n_samples[w] = 0;
+        status[w] = file_status[window_file[w]];
+        if (status[w]) continue;
+        which.push_back(w);
+        w_slot.push_back(slot[window_file[w]]);
+        w_start.push_back(window_start[w]);
+        w_count.push_back(window_count[w]);
+        w_cap.push_back(pcm_cap[w]);
+        w_out.push_back(pcm_out[w]);
+    }
+    const uint32_t nw = (uint32_t)which.size();
+    if (nw == 0) return FLACGPU_OK;
+    std::vector<uint64_t> ns(nw, 0);
+    std::vector<int> st(nw, 0);
+    rc = decode_files_windows_resident(ctx, (uint32_t)ptr.size(), ptr.data(), lens.data(), bits.data(), rates.data(), nw,
+                                       w_slot.data(), w_start.data(), w_count.data(), w_out.data(), w_cap.data(), ns.data(),
+                                       st.data());
+    if (rc) return rc;
+    for (uint32_t k = 0; k < nw; k++) {
+        n_samples[which[k]] = ns[k];
+        status[which[k]] = st[k];
+    }
+    return FLACGPU_OK;
+}
+
 }  // extern "C"

@@ -2,7 +2,9 @@
 // (fg_dec.hpp, fg_dec.hip) and the device frame index (fg_index.hpp, fg_index.hip) over device
 // memory, the host-buffer decode, and the device side of the whole-file decode; and their
 // many-streams forms: the index of n streams in one call, decode chunks that span streams
-// (fg_streams.hpp, fg_dec_streams.hip), and the device side of flacgpu_decode_files.  The
+// (fg_streams.hpp, fg_dec_streams.hip), and the device side of flacgpu_decode_files; and the
+// sample-window decode (fg_window.hpp, fg_window.hip): the positions of indexed streams, windows
+// over resident tables, and the device side of flacgpu_decode_files_windows.  The
 // host-only side (metadata, the host index, flacgpu_decode_file / _files) is fg_dec_api.cpp.
 #include <hip/hip_runtime.h>
 
@@ -16,9 +18,14 @@
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
 #include "fg_streams.hpp"
+#include "fg_window.hpp"
 
 using namespace fg;
 
+static_assert(sizeof(window::WindowResult) == sizeof(flacgpu_window_result), "window result layout");
+static_assert(FLACGPU_WINDOW_BAD_INDEX == (int)window::WIN_BAD_INDEX && FLACGPU_WINDOW_BAD_FRAME == (int)window::WIN_BAD_FRAME &&
+                  FLACGPU_WINDOW_TOO_SMALL == (int)window::WIN_TOO_SMALL,
+              "window status codes");
 static_assert(sizeof(dec::Result) == sizeof(flacgpu_decode_result), "decode result layout");
 static_assert(sizeof(idx::IndexResult) == sizeof(flacgpu_index_result), "index result layout");
 static_assert(sizeof(streams::StreamResult) == sizeof(flacgpu_stream_result), "stream result layout");
@@ -43,16 +50,22 @@ struct DecScratch {
 // cap; and the frame table and result of the whole-file decode, which indexes the file it uploaded.
 // The many-streams decode adds the packed frame table with the per-stream arrays and segment table
 // of a call (packed), and the per-file results and digests of flacgpu_decode_files (files).
+// The window decode adds the stream table of a positions call (pos), the windows of a call as the
+// caller states them with their cover records (win_in), what the chunk loop over the covering
+// frames needs (win), those frames' PCM (win_pcm), and the delivered bytes and results of
+// flacgpu_decode_files_windows (win_out).
 struct IdxScratch {
     uint8_t *buf = nullptr, *table = nullptr, *packed = nullptr, *files = nullptr;
     uint64_t cap = 0, table_cap = 0, packed_cap = 0, files_cap = 0;
+    uint8_t *pos = nullptr, *win_in = nullptr, *win = nullptr, *win_pcm = nullptr, *win_out = nullptr;
+    uint64_t pos_cap = 0, win_in_cap = 0, win_cap = 0, win_pcm_cap = 0, win_out_cap = 0;
 };
 
 void fg::dec_release(flacgpu_ctx *c) {
     if (DecScratch *d = c->dec)
         for (uint8_t *b : {d->buf, d->d_frames, d->d_pcm}) hipFree(b);
     if (IdxScratch *x = c->idx)
-        for (uint8_t *b : {x->buf, x->table, x->packed, x->files}) hipFree(b);
+        for (uint8_t *b : {x->buf, x->table, x->packed, x->files, x->pos, x->win_in, x->win, x->win_pcm, x->win_out}) hipFree(b);
     delete c->dec;
     delete c->idx;
     c->dec = nullptr;
@@ -365,6 +378,149 @@ int streams_decode(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const Stre
     return FLACGPU_OK;
 }
 
+// The sample positions of n indexed streams (0 < n <= kIdxMaxStreams), only queued: one table of
+// n PosStream goes to the device; the grids are sized from the caps, the frame counts are read
+// from d_res on the device.
+int positions_core(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const uint64_t *table_first, const uint64_t *table_caps,
+                   const uint64_t *d_off, const uint32_t *d_bytes, const idx::IndexResult *d_res, const uint32_t *bits,
+                   const uint32_t *rates, uint64_t *d_pos, uint64_t *d_totals, hipStream_t st) {
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
+    std::vector<window::PosStream> tab;
+    try {
+        tab.resize(n);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    uint64_t max_cap = 0;
+    for (uint32_t s = 0; s < n; s++) {
+        tab[s] = {table_first[s], table_caps[s], bits ? bits[s] : 16u, rates ? rates[s] : 0u};
+        max_cap = std::max(max_cap, table_caps[s]);
+    }
+    HIPCHK(grow(x->pos, x->pos_cap, (uint64_t)n * sizeof(window::PosStream), &st));  // an earlier call may still use the old one
+    HIPCHK(hipMemcpyAsync(x->pos, tab.data(), (uint64_t)n * sizeof(window::PosStream), hipMemcpyHostToDevice, st));
+    Timed t(c, FLACGPU_K_SCAN, st);
+    HIPCHK(launch_positions(d_data, (const window::PosStream *)x->pos, n, max_cap, d_off, d_bytes, d_res, d_pos, d_totals, st));
+    return FLACGPU_OK;
+}
+
+// The windows of a call between its two halves: as uploaded, and their cover records on both sides.
+struct WindowsCall {
+    uint32_t n = 0;
+    window::Cover *d_recs = nullptr;
+    std::vector<window::Cover> recs;
+};
+
+// The first half of a window decode: the windows go to the device, k_window_cover finds their
+// covering frames, and the host waits for st ONCE to read the records.  caps[w]: the bytes of
+// window w's destination.
+int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexResult *d_ires, const uint64_t *d_pos,
+                  const uint64_t *d_totals, uint32_t n, const uint32_t *window_stream, const uint64_t *window_start,
+                  const uint64_t *window_count, const uint64_t *caps, WindowsCall &wc, hipStream_t st) {
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
+    std::vector<window::WindowArg> args;
+    try {
+        args.resize(n);
+        wc.recs.resize(n);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    for (uint32_t w = 0; w < n; w++)
+        args[w] = {window_start[w], window_count[w], caps[w], table_first[window_stream[w]], window_stream[w], 0u};
+    window::WindowArg *d_args = nullptr;
+    auto carve = [&](uint8_t *base) {
+        Carve v{base};
+        v.take(n, d_args);
+        return v.take(n, wc.d_recs);
+    };
+    HIPCHK(grow(x->win_in, x->win_in_cap, carve(nullptr), &st));  // an earlier call may still use the old one
+    carve(x->win_in);
+    wc.n = n;
+    HIPCHK(hipMemcpyAsync(d_args, args.data(), (uint64_t)n * sizeof(window::WindowArg), hipMemcpyHostToDevice, st));
+    {
+        Timed t(c, FLACGPU_K_SCAN, st);
+        HIPCHK(launch_window_cover(d_args, d_ires, d_pos, d_totals, c->g.C * (c->g.bits / 8u), wc.d_recs, n, st));
+    }
+    HIPCHK(hipMemcpyAsync(wc.recs.data(), wc.d_recs, (uint64_t)n * sizeof(window::Cover), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    return FLACGPU_OK;
+}
+
+// The second half, only queued.  Every window plays the role a stream plays in streams_decode: its
+// covering frames are its frames, cut with all the others' into chunks of max_frames; its PCM
+// region is span * per bytes of the context's window scratch (bases 16-byte aligned); its result is
+// a scratch StreamResult.  After the last chunk k_window_copy moves each clean window's bytes to
+// d_pcm_out + out_offsets[w], and k_window_results writes d_results.
+int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_first, const uint64_t *d_foff,
+                   const uint32_t *d_fbytes, const WindowsCall &wc, const uint32_t *window_stream, uint8_t *d_pcm_out,
+                   const uint64_t *out_offsets, window::WindowResult *d_results, hipStream_t st) {
+    DecScratch *d = c->dec;
+    IdxScratch *x = c->idx;
+    const uint32_t n = wc.n;
+    const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u);
+    std::vector<uint64_t> frames, host;
+    std::vector<streams::Segment> segs;
+    std::vector<uint32_t> chunk_seg;
+    uint64_t whole = 0, max_bytes = 0;  // whole: the end of the last region, the capacity k_dec_recon checks
+    try {
+        frames.assign(n, 0);
+        host.assign(4u * (uint64_t)n, 0);
+        for (uint32_t w = 0; w < n; w++) {
+            const window::Cover &r = wc.recs[w];
+            const bool decode = r.status == window::WIN_OK && r.n_frames > 0;
+            host[w] = whole;
+            host[2u * (uint64_t)n + w] = table_first[window_stream[w]] + r.first_frame;
+            host[3u * (uint64_t)n + w] = out_offsets[w];
+            if (!decode) continue;
+            if (r.span > (1ull << 40) || r.n_samples > r.span) return FLACGPU_ERR_INVALID_INPUT;  // no stream's positions
+            frames[w] = r.n_frames;
+            host[n + w] = r.span * per;
+            whole += (r.span * per + 15u) & ~(uint64_t)15u;
+            if (whole > (1ull << 47)) return FLACGPU_ERR_OUT_OF_MEMORY;
+            max_bytes = std::max(max_bytes, r.n_samples * per);
+        }
+        streams::cut_segments(frames, c->max_frames, segs, chunk_seg);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    const uint32_t n_chunks = chunk_seg.empty() ? 0u : (uint32_t)chunk_seg.size() - 1u;
+    const uint64_t n_packed = (uint64_t)n_chunks * c->max_frames;
+    uint64_t *p_off = nullptr, *meta = nullptr, *carried = nullptr;
+    uint32_t *p_bytes = nullptr;
+    streams::Segment *d_segs = nullptr;
+    streams::StreamResult *sres = nullptr;
+    auto carve = [&](uint8_t *base) {
+        Carve v{base};
+        v.take(n_packed, p_off);
+        v.take(4u * (uint64_t)n, meta);  // scratch base, scratch cap, table first, destination: one upload
+        v.take(n, carried, sres);
+        v.take(segs.size(), d_segs);
+        return v.take(n_packed, p_bytes);
+    };
+    HIPCHK(grow(x->win, x->win_cap, carve(nullptr), &st));
+    carve(x->win);
+    HIPCHK(grow(x->win_pcm, x->win_pcm_cap, whole + 16u, &st));
+    uint64_t *d_base = meta, *d_cap = meta + n, *d_first = meta + 2u * (uint64_t)n, *d_dst = meta + 3u * (uint64_t)n;
+    HIPCHK(hipMemcpyAsync(meta, host.data(), host.size() * 8u, hipMemcpyHostToDevice, st));
+    if (!segs.empty())
+        HIPCHK(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(streams::Segment), hipMemcpyHostToDevice, st));
+    HIPCHK(launch_window_init(wc.d_recs, sres, carried, n, st));
+    HIPCHK(launch_streams_gather(d_segs, (uint32_t)segs.size(), d_first, d_foff, d_fbytes, p_off, p_bytes, st));
+    for (uint32_t k = 0; k < n_chunks; k++) {
+        const uint32_t s0 = chunk_seg[k], s1 = chunk_seg[k + 1u];
+        const uint32_t nf = segs[s1 - 1u].first + segs[s1 - 1u].count;
+        const ChunkStreams cs{d_segs + s0, s1 - s0, d_base, d_cap, carried, sres};
+        const int rc = dec_core(c, d_data, p_off + (uint64_t)k * c->max_frames, p_bytes + (uint64_t)k * c->max_frames, nf,
+                                nullptr, x->win_pcm, whole, nullptr, false, (flacgpu_decode_result *)d->d_results, nullptr,
+                                st, &cs);
+        if (rc) return rc;
+    }
+    HIPCHK(launch_window_copy(wc.d_recs, sres, x->win_pcm, d_base, d_pcm_out, d_dst, (uint32_t)per, n, max_bytes, st));
+    HIPCHK(launch_window_results(wc.d_recs, sres, d_results, n, st));
+    return FLACGPU_OK;
+}
+
 // One chunk of a host-buffer decode on the context's stream: the n <= max_frames consecutive
 // frames of the table (d_foff, d_fbytes) into d_frames are decoded into the zeroed staging PCM (a
 // damaged frame leaves zeros), their results copied to `results`, their PCM to pcm_out + *written;
@@ -491,6 +647,49 @@ int flacgpu_decode_streams_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_
     if (rc) return rc;
     return streams_decode(c, d_data, n_streams, tb, ires, d_pcm_out, pcm_offsets, pcm_caps, (streams::StreamResult *)d_results,
                           d_md5, st);
+}
+
+int flacgpu_flac_positions_streams_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams,
+                                          const uint64_t *table_first, const uint64_t *table_caps,
+                                          const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                          const flacgpu_index_result *d_index_results, const uint32_t *stream_bits,
+                                          const uint32_t *stream_rates, uint64_t *d_frame_first_sample,
+                                          uint64_t *d_stream_samples, void *hip_stream) {
+    if (!c || !d_data || !table_first || !table_caps || !d_frame_offsets || !d_frame_bytes || !d_index_results ||
+        !d_frame_first_sample || !d_stream_samples || n_streams > idx::kIdxMaxStreams)
+        return FLACGPU_ERR_INVALID_INPUT;
+    if (n_streams == 0) return FLACGPU_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return positions_core(c, d_data, n_streams, table_first, table_caps, d_frame_offsets, d_frame_bytes,
+                          (const idx::IndexResult *)d_index_results, stream_bits, stream_rates, d_frame_first_sample,
+                          d_stream_samples, pick_stream(c, hip_stream));
+}
+
+int flacgpu_decode_windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
+                                  const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                  const flacgpu_index_result *d_index_results, const uint64_t *d_frame_first_sample,
+                                  const uint64_t *d_stream_samples, uint32_t n_windows, const uint32_t *window_stream,
+                                  const uint64_t *window_start, const uint64_t *window_count, uint8_t *d_pcm_out,
+                                  const uint64_t *pcm_offsets, const uint64_t *pcm_caps, flacgpu_window_result *d_results,
+                                  void *hip_stream) {
+    if (!c || !d_data || !table_first || !d_frame_offsets || !d_frame_bytes || !d_index_results || !d_frame_first_sample ||
+        !d_stream_samples || n_windows > 65535u)
+        return FLACGPU_ERR_INVALID_INPUT;
+    if (n_windows && (!window_stream || !window_start || !window_count || !d_pcm_out || !pcm_offsets || !pcm_caps || !d_results))
+        return FLACGPU_ERR_INVALID_INPUT;
+    for (uint32_t w = 0; w < n_windows; w++)
+        if (window_stream[w] >= n_streams || pcm_offsets[w] + pcm_caps[w] < pcm_offsets[w]) return FLACGPU_ERR_INVALID_INPUT;
+    if (n_windows == 0) return FLACGPU_OK;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = dec_scratch(c);
+    if (rc) return rc;
+    hipStream_t st = pick_stream(c, hip_stream);
+    WindowsCall wc;
+    rc = windows_cover(c, table_first, (const idx::IndexResult *)d_index_results, d_frame_first_sample, d_stream_samples,
+                       n_windows, window_stream, window_start, window_count, pcm_caps, wc, st);
+    if (rc) return rc;
+    return windows_decode(c, d_data, table_first, d_frame_offsets, d_frame_bytes, wc, window_stream, d_pcm_out, pcm_offsets,
+                          (window::WindowResult *)d_results, st);
 }
 
 // every chunk's frames and frame table are uploaded, its results land at results + f0
@@ -681,5 +880,105 @@ int fg::decode_files_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *
         if (rc) return rc;
         for (size_t k = 0; k < hi.size(); k++) std::copy(dg.begin() + 16 * k, dg.begin() + 16 * (k + 1), digests + 16u * hi[k]);
     }
+    return FLACGPU_OK;
+}
+
+// The device side of flacgpu_decode_files_windows.  The files' frames go into one device buffer as
+// in decode_files_resident and are indexed in one call; the positions and the windows run on those
+// tables, the delivered bytes land back to back in device memory, and only they and the windows'
+// results come back.  status[w]: 0, FLACGPU_ERR_INVALID_INPUT (the device index refuses the file,
+// or a covering frame is damaged) or FLACGPU_ERR_OUTPUT_TOO_SMALL.
+int fg::decode_files_windows_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *p, const size_t *len,
+                                      const uint32_t *bits, const uint32_t *rates, uint32_t n_windows,
+                                      const uint32_t *window_file, const uint64_t *window_start, const uint64_t *window_count,
+                                      uint8_t *const *pcm_out, const uint64_t *pcm_cap, uint64_t *n_samples, int *status) {
+    if (n_windows == 0) return FLACGPU_OK;
+    if (n == 0 || n > idx::kIdxMaxStreams || n_windows > 65535u) return FLACGPU_ERR_INVALID_INPUT;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = dec_scratch(c);
+    if (rc) return rc;
+    DecScratch *d = c->dec;
+    hipStream_t st = c->stream;
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
+    const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u);
+    std::vector<uint64_t> offs, lens, first, caps, out_offs;
+    std::vector<window::WindowResult> res;
+    try {
+        offs.resize(n);
+        lens.resize(n);
+        first.resize(n);
+        caps.resize(n);
+        out_offs.resize(n_windows);
+        res.resize(n_windows);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    uint64_t total = 0, entries = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (len[i] > 0xFFFFFFFFull) return FLACGPU_ERR_INVALID_INPUT;
+        offs[i] = total;
+        lens[i] = len[i];
+        total += (len[i] + 63u) & ~(uint64_t)63u;
+        first[i] = entries;
+        caps[i] = len[i] / 8u + 1u;  // a frame is at least 9 bytes
+        entries += caps[i];
+    }
+    HIPCHK(grow(d->d_frames, d->frames_cap, total + 16u, &st));
+    for (uint32_t i = 0; i < n; i++)
+        if (len[i]) HIPCHK(hipMemcpyAsync(d->d_frames + offs[i], p[i], len[i], hipMemcpyHostToDevice, st));
+    uint64_t *f_off = nullptr, *f_pos = nullptr, *d_totals = nullptr;
+    uint32_t *f_bytes = nullptr;
+    idx::IndexResult *d_ires = nullptr;
+    auto table = [&](uint8_t *base) {
+        Carve v{base};
+        v.take(entries, f_off, f_pos);
+        v.take(n, d_totals, d_ires);
+        return v.take(entries, f_bytes);
+    };
+    HIPCHK(grow(x->table, x->table_cap, table(nullptr), &st));
+    table(x->table);
+    rc = index_streams_core(c, d->d_frames, n, offs.data(), lens.data(), bits, rates, first.data(), caps.data(), f_off, f_bytes,
+                            d_ires, st);
+    if (rc) return rc;
+    rc = positions_core(c, d->d_frames, n, first.data(), caps.data(), f_off, f_bytes, d_ires, bits, rates, f_pos, d_totals, st);
+    if (rc) return rc;
+    WindowsCall wc;
+    rc = windows_cover(c, first.data(), d_ires, f_pos, d_totals, n_windows, window_file, window_start, window_count, pcm_cap, wc,
+                       st);
+    if (rc) return rc;
+    uint64_t out_total = 0;
+    for (uint32_t w = 0; w < n_windows; w++) {
+        const window::Cover &r = wc.recs[w];
+        out_offs[w] = out_total;
+        if (r.status != window::WIN_OK) continue;
+        if (r.n_samples > r.span) return FLACGPU_ERR_INTERNAL;
+        out_total += (r.n_samples * per + 15u) & ~(uint64_t)15u;
+    }
+    uint8_t *d_out = nullptr;
+    window::WindowResult *d_wres = nullptr;
+    auto carve = [&](uint8_t *base) {
+        Carve v{base};
+        v.take(n_windows, d_wres);
+        return v.take(out_total + 16u, d_out);
+    };
+    HIPCHK(grow(x->win_out, x->win_out_cap, carve(nullptr), &st));
+    carve(x->win_out);
+    rc = windows_decode(c, d->d_frames, first.data(), f_off, f_bytes, wc, window_file, d_out, out_offs.data(), d_wres, st);
+    if (rc) return rc;
+    HIPCHK(hipMemcpyAsync(res.data(), d_wres, (uint64_t)n_windows * sizeof(window::WindowResult), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    for (uint32_t w = 0; w < n_windows; w++) {
+        n_samples[w] = 0;
+        if (res[w].status == window::WIN_TOO_SMALL) status[w] = FLACGPU_ERR_OUTPUT_TOO_SMALL;
+        else if (res[w].status != window::WIN_OK) status[w] = FLACGPU_ERR_INVALID_INPUT;
+        else {
+            status[w] = FLACGPU_OK;
+            n_samples[w] = res[w].n_samples;
+            const uint64_t bytes = res[w].n_samples * per;
+            if (bytes) HIPCHK(hipMemcpyAsync(pcm_out[w], d_out + out_offs[w], bytes, hipMemcpyDeviceToHost, st));
+        }
+    }
+    HIPCHK(hipStreamSynchronize(st));
     return FLACGPU_OK;
 }

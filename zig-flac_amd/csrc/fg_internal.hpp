@@ -49,4 +49,12 @@ int decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uint32_
 int decode_files_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *p, const size_t *len, const uint32_t *bits,
                           const uint32_t *rates, uint8_t *const *pcm_out, const size_t *pcm_cap, uint64_t *n_samples,
                           uint8_t *digests, uint8_t *take_single);
+// fg_dec_host.cpp, the device side of flacgpu_decode_files_windows: n > 0 bare runs of frames
+// uploaded into one buffer, indexed, their sample positions scanned, and window w (samples
+// [window_start[w], + window_count[w]) of run window_file[w] < n) decoded to pcm_out[w]; status[w]
+// and n_samples[w] for every window.  No host index, no MD5.
+int decode_files_windows_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *p, const size_t *len, const uint32_t *bits,
+                                  const uint32_t *rates, uint32_t n_windows, const uint32_t *window_file,
+                                  const uint64_t *window_start, const uint64_t *window_count, uint8_t *const *pcm_out,
+                                  const uint64_t *pcm_cap, uint64_t *n_samples, int *status);
 }  // namespace fg

@@ -359,6 +359,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_flac_index_streams_device": (I32, [P, P, U32, P, P, P, P, P, P, P, P, P, P]),
         "flacgpu_decode_streams_device": (I32, [P, P, U32, P, P, P, P, P, P, P, P, P, P]),
         "flacgpu_decode_files": (I32, [P, U32, P, P, P, P, P, P, P]),
+        "flacgpu_flac_positions_streams_device": (I32, [P, P, U32, P, P, P, P, P, P, P, P, P, P]),
+        "flacgpu_decode_windows_device": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, P, P, P, P, P]),
+        "flacgpu_decode_files_windows": (I32, [P, U32, P, P, U32, P, P, P, P, P, P, P]),
     }
     # an older build named by FLACGPU_LIB (same-box A/B runs, tools/ab.sh) may predate later entry
     # points: those stay unbound there; the in-tree library must export every one
@@ -395,6 +398,7 @@ def exported_symbols() -> list:
         "flacgpu_decode_frames_device", "flacgpu_verify_plan_device", "flacgpu_decode_frames", "flacgpu_flac_index",
         "flacgpu_decode_file", "flacgpu_flac_index_device",
         "flacgpu_flac_index_streams_device", "flacgpu_decode_streams_device", "flacgpu_decode_files",
+        "flacgpu_flac_positions_streams_device", "flacgpu_decode_windows_device", "flacgpu_decode_files_windows",
     ]
 
 
@@ -500,6 +504,15 @@ class StreamResult(ctypes.Structure):
                 ("first_bad_status", ctypes.c_uint32)]
 
 
+WINDOW_OK, WINDOW_BAD_INDEX, WINDOW_BAD_FRAME, WINDOW_TOO_SMALL = range(4)  # flacgpu_window_result.status
+
+
+class WindowResult(ctypes.Structure):
+    """flacgpu_window_result: one window of flacgpu_decode_windows_device (device memory, 32 bytes)."""
+    _fields_ = [("n_samples", ctypes.c_uint64), ("first_frame", ctypes.c_uint64), ("n_frames", ctypes.c_uint32),
+                ("status", ctypes.c_uint32), ("first_bad_frame", ctypes.c_uint32), ("first_bad_status", ctypes.c_uint32)]
+
+
 def _u64s(v: Sequence[int]):
     return (ctypes.c_uint64 * max(len(v), 1))(*v)
 
@@ -563,6 +576,54 @@ class _DecodeOps:
             self.ctx, d_data, len(offsets), _u64s(offsets), _u64s(lengths), _u32s(stream_bits), _u32s(stream_rates),
             d_pcm_out, _u64s(pcm_offsets), _u64s(pcm_caps), d_results, d_md5 or None, _stream(stream)),
             "decode_streams_device")
+
+    def flac_positions_streams_device(self, d_data: int, table_first: Sequence[int], table_caps: Sequence[int],
+                                      d_frame_offsets: int, d_frame_bytes: int, d_index_results: int,
+                                      d_frame_first_sample: int, d_stream_samples: int,
+                                      stream_bits: Optional[Sequence[int]] = None,
+                                      stream_rates: Optional[Sequence[int]] = None, stream: Optional[int] = None) -> None:
+        """flacgpu_flac_positions_streams_device: the sample positions of len(table_first) indexed streams
+        into d_frame_first_sample (laid out like the frame tables) and their totals into d_stream_samples."""
+        _check(self.lib.flacgpu_flac_positions_streams_device(
+            self.ctx, d_data, len(table_first), _u64s(table_first), _u64s(table_caps), d_frame_offsets, d_frame_bytes,
+            d_index_results, _u32s(stream_bits), _u32s(stream_rates), d_frame_first_sample, d_stream_samples,
+            _stream(stream)), "flac_positions_streams_device")
+
+    def decode_windows_device(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int, d_frame_bytes: int,
+                              d_index_results: int, d_frame_first_sample: int, d_stream_samples: int,
+                              windows: Sequence, d_pcm_out: int, pcm_offsets: Sequence[int], pcm_caps: Sequence[int],
+                              d_results: int, stream: Optional[int] = None) -> None:
+        """flacgpu_decode_windows_device: windows = [(stream, start, count)] over resident tables and
+        positions; window w's bytes to d_pcm_out + pcm_offsets[w], d_results: WindowResult per window."""
+        _check(self.lib.flacgpu_decode_windows_device(
+            self.ctx, d_data, len(table_first), _u64s(table_first), d_frame_offsets, d_frame_bytes, d_index_results,
+            d_frame_first_sample, d_stream_samples, len(windows), _u32s([w[0] for w in windows]),
+            _u64s([w[1] for w in windows]), _u64s([w[2] for w in windows]), d_pcm_out, _u64s(pcm_offsets),
+            _u64s(pcm_caps), d_results, _stream(stream)), "decode_windows_device")
+
+    def decode_files_windows(self, flacs: Sequence[bytes], windows: Sequence, guard: int = 0,
+                             pcm_caps: Optional[Sequence[int]] = None):
+        """flacgpu_decode_files_windows: windows = [(file, start, count)] of whole FLAC files ->
+        [(status, PCM bytes, guard bytes)] per window.  guard: that many extra bytes after every
+        capacity, returned as the third member; pcm_caps: each window's capacity (default: count samples)."""
+        n, nw = len(flacs), len(windows)
+        per = self.channels * self.bytes_per_sample
+        if pcm_caps is None:
+            pcm_caps = [w[2] * per for w in windows]
+        srcs = [ctypes.create_string_buffer(bytes(f), max(len(f), 1)) for f in flacs]
+        outs = [ctypes.create_string_buffer(b"\xA5" * (c + guard + 1), c + guard + 1) for c in pcm_caps]
+        P = ctypes.c_void_p
+        a_src = (P * max(n, 1))(*[ctypes.addressof(b) for b in srcs])
+        a_len = (ctypes.c_size_t * max(n, 1))(*[len(f) for f in flacs])
+        a_out = (P * max(nw, 1))(*[ctypes.addressof(b) for b in outs])
+        a_cap = (ctypes.c_size_t * max(nw, 1))(*pcm_caps)
+        ns = (ctypes.c_uint64 * max(nw, 1))()
+        st = (ctypes.c_int * max(nw, 1))()
+        _check(self.lib.flacgpu_decode_files_windows(
+            self.ctx, n, a_src, a_len, nw, _u32s([w[0] for w in windows]), _u64s([w[1] for w in windows]),
+            _u64s([w[2] for w in windows]), a_out, a_cap, ns, st), "decode_files_windows")
+        return [(int(st[w]), outs[w].raw[: min(ns[w] * per, pcm_caps[w])], outs[w].raw[pcm_caps[w]: pcm_caps[w] + guard])
+                for w in range(nw)]
 
     def decode_files(self, flacs: Sequence[bytes], pcm_caps: Optional[Sequence[int]] = None, guard: int = 0):
         """flacgpu_decode_files: whole FLAC files in one call -> [(status, PCM bytes, md5_ok)] per
