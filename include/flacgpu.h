@@ -596,6 +596,39 @@ int flacgpu_decode_windows_device(flacgpu_ctx *ctx, const uint8_t *d_data,
                                   const uint64_t *window_count,
                                   uint8_t *d_pcm_out, const uint64_t *pcm_offsets, const uint64_t *pcm_caps,
                                   flacgpu_window_result *d_results, void *hip_stream);
+/* The same windows delivered as tensor elements instead of PCM bytes.  A source sample is the
+ * bits / 8 bytes the decode writes (signed, little-endian, 8-bit included), sign-extended to
+ * int32 x; its element is
+ *   FLACGPU_SAMPLE_I32   x, unscaled
+ *   FLACGPU_SAMPLE_F32   (float)x * 2^-(bits-1): the conversion rounds to nearest-even (inexact only
+ *                        for 32-bit samples with |x| >= 2^24), the scale is exact; in [-1, 1]
+ *   FLACGPU_SAMPLE_F16   that value rounded to nearest-even, subnormal results kept
+ *   FLACGPU_SAMPLE_BF16  that value rounded to nearest-even
+ * With C channels, n samples delivered after clipping and count = window_count[w], sample t of
+ * channel c is element t * C + c from d_out + out_offsets[w] * element size (interleaved), or
+ * c * count + t with FLACGPU_DELIVER_PLANAR: the plane stride is the stated count, whatever n turns
+ * out to be.  With FLACGPU_DELIVER_PAD the elements of t in [n, count) are written as zero in every
+ * channel -- also where n is 0 -- so every OK window fills exactly C * count elements; without it
+ * they are not touched.  out_offsets and out_caps are in ELEMENTS.  TOO_SMALL where C * count
+ * (PLANAR or PAD) or else C * n exceeds out_caps[w], decided before anything is decoded and with
+ * no product formed, so count = 2^64 - 1 under PLANAR or PAD is TOO_SMALL.  n_samples of a result
+ * counts decoded samples; padding is never counted.  A window that is not OK writes nothing, PAD or
+ * not.  An unknown sample_format, unknown flag bits, d_out not aligned to the element size, or
+ * out_offsets[w] + out_caps[w] passing 64 bits: FLACGPU_ERR_INVALID_INPUT before any device work.
+ * Everything else -- the one wait, the chunks, BAD_INDEX and BAD_FRAME, windows that share streams
+ * and overlap, what is timed -- is as in flacgpu_decode_windows_device. */
+enum { FLACGPU_SAMPLE_I32 = 0, FLACGPU_SAMPLE_F32 = 1, FLACGPU_SAMPLE_F16 = 2, FLACGPU_SAMPLE_BF16 = 3 };
+enum { FLACGPU_DELIVER_PLANAR = 1, FLACGPU_DELIVER_PAD = 2 };
+int flacgpu_decode_windows_device_as(flacgpu_ctx *ctx, const uint8_t *d_data,
+                                     uint32_t n_streams, const uint64_t *table_first,
+                                     const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                     const flacgpu_index_result *d_index_results,
+                                     const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
+                                     uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
+                                     const uint64_t *window_count,
+                                     uint32_t sample_format, uint32_t flags,
+                                     void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
+                                     flacgpu_window_result *d_results, void *hip_stream);
 /* Windows of whole files in host memory: window w is samples [window_start[w], + window_count[w])
  * of file window_file[w] (< n_files), delivered to pcm_out[w] (capacity pcm_cap[w]) with
  * n_samples[w].  Metadata is parsed on the host as in flacgpu_decode_files; the good files' frames

@@ -33,6 +33,15 @@ clock, alternated, best of 3 each after one warm call each), and a call of windo
 whole streams with its timed kernels, whose difference bounds the copy pass.
 
     python tools/decode_rate.py --legs windows --windows-out profiles/decode_windows_rate.json
+
+The deliver leg (--deliver-out; opt-in, not part of `all`) takes the windows leg's files and
+windows: flacgpu_decode_windows_device_as (planar, padded; f32, and again bf16) against what a
+caller of the byte call does to get the identical tensor -- flacgpu_decode_windows_device, then
+view(int16) -> reshape -> to(float32) -> scale -> transpose -> contiguous() in torch -- alternated
+(HIP events, the median), and windows that cover whole streams through both calls with their timed
+kernels, whose differences bound the delivery pass and the copy pass.
+
+    python tools/decode_rate.py --legs deliver --deliver-out profiles/decode_deliver_rate.json
 """
 import argparse
 import ctypes
@@ -530,6 +539,142 @@ def windows_rate(n_files: int, frames_each: int, window: int, warmup: int, repea
     return res
 
 
+def deliver_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: int) -> dict:
+    import numpy as np
+    import torch
+
+    import flacgpu
+    import synth
+
+    ch, bits, rate, _ = PRESETS["c2"]
+    per = ch * (bits // 8)
+    dev = torch.device("cuda", 0)
+    unit = synth.synth_pcm(64 * 4096, ch, bits, rate)
+    n_each = frames_each * 4096
+    pcm = (unit * ((frames_each + 63) // 64))[: n_each * per]
+    start = (n_each // 3 // 4096) * 4096 + 1234  # not a multiple of the block size
+    assert start % 4096 and start + window <= n_each
+    with flacgpu.Encoder(ch, bits, rate, device=0, max_frames=n_files * frames_each) as enc:
+        flacs = enc.encode_files([pcm] * n_files)
+        first = flacgpu.flac_index(flacs[0])[1]
+        bodies = [f[first:] for f in flacs]
+        offs, at = [], 0
+        for b in bodies:
+            offs.append(at)
+            at += (len(b) + 63) & ~63
+        host = np.zeros(at + 16, dtype=np.uint8)
+        for o, b in zip(offs, bodies):
+            host[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        d_buf = torch.from_numpy(host).to(dev)
+        lens = [len(b) for b in bodies]
+        caps = [n // 8 + 1 for n in lens]
+        tfirst = [int(v) for v in np.cumsum([0] + caps)[:-1]]
+        d_off = torch.zeros(sum(caps), dtype=torch.int64, device=dev)
+        d_fb = torch.zeros(sum(caps), dtype=torch.int32, device=dev)
+        d_pos = torch.zeros(sum(caps), dtype=torch.int64, device=dev)
+        d_tot = torch.zeros(n_files, dtype=torch.int64, device=dev)
+        d_ir = torch.zeros(16 * n_files, dtype=torch.uint8, device=dev)
+        d_wres = torch.zeros(32 * n_files, dtype=torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        sbits, srates = [bits] * n_files, [rate] * n_files
+        enc.flac_index_streams_device(d_buf.data_ptr(), offs, lens, tfirst, caps, d_off.data_ptr(), d_fb.data_ptr(),
+                                      d_ir.data_ptr(), stream_bits=sbits, stream_rates=srates, stream=st)
+        enc.flac_positions_streams_device(d_buf.data_ptr(), tfirst, caps, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(),
+                                          d_pos.data_ptr(), d_tot.data_ptr(), stream_bits=sbits, stream_rates=srates, stream=st)
+        tables = (d_buf.data_ptr(), tfirst, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(), d_pos.data_ptr(), d_tot.data_ptr())
+        planar_pad = flacgpu.DELIVER_PLANAR | flacgpu.DELIVER_PAD
+
+        def deliver(wins, fmt, x):
+            count = wins[0][2]
+            enc.decode_windows_device_as(*tables, wins, fmt, planar_pad, x.data_ptr(), [i * ch * count for i in range(len(wins))],
+                                         [ch * count] * len(wins), d_wres.data_ptr(), stream=st)
+
+        def copy(wins, d_out):
+            count = wins[0][2]
+            enc.decode_windows_device(*tables, wins, d_out.data_ptr(), [i * count * per for i in range(len(wins))],
+                                      [count * per] * len(wins), d_wres.data_ptr(), stream=st)
+
+        def today(wins, d_out, dtype):
+            """What a caller of the byte call does for the same [window, channel, time] tensor."""
+            copy(wins, d_out)
+            x = d_out.view(torch.int16).view(len(wins), wins[0][2], ch).to(torch.float32) * (2.0 ** -(bits - 1))
+            return x.to(dtype).transpose(1, 2).contiguous()
+
+        def event_ms(fn):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            return a.elapsed_time(b)
+
+        def summary(ms):
+            return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
+
+        def all_ok(n):
+            raw = d_wres.cpu().numpy().tobytes()
+            return [(r.status, r.n_samples) for r in (flacgpu.WindowResult * n_files).from_buffer_copy(raw)] == [(0, n)] * n_files
+
+        crops = [(i, start, window) for i in range(n_files)]
+        d_win = torch.zeros(n_files * window * per, dtype=torch.uint8, device=dev)
+        x32 = torch.zeros((n_files, ch, window), dtype=torch.float32, device=dev)
+        x16 = torch.zeros((n_files, ch, window), dtype=torch.bfloat16, device=dev)
+        legs = {"as_f32": lambda: deliver(crops, flacgpu.SAMPLE_F32, x32),
+                "torch_f32": lambda: today(crops, d_win, torch.float32),
+                "as_bf16": lambda: deliver(crops, flacgpu.SAMPLE_BF16, x16),
+                "torch_bf16": lambda: today(crops, d_win, torch.bfloat16)}
+        for _ in range(warmup):
+            for fn in legs.values():
+                fn()
+        enc.sync_check(st)
+        assert all_ok(window)
+        assert torch.equal(x32, today(crops, d_win, torch.float32)), "the delivered f32 tensor differs from the torch sequence's"
+        assert torch.equal(x16, today(crops, d_win, torch.bfloat16)), "the delivered bf16 tensor differs from the torch sequence's"
+        ms = {k: [] for k in legs}
+        for _ in range(repeats):  # alternated
+            for k, fn in legs.items():
+                ms[k].append(event_ms(fn))
+        res = {"files": n_files, "frames_per_file": frames_each, "channels": ch, "bits": bits, "window_samples": window,
+               "window_start": start, "window_bytes": n_files * window * per, "layout": "planar, padded"}
+        for k in legs:
+            res[k] = summary(ms[k])
+        for f in ("f32", "bf16"):
+            res["as_" + f]["x_torch"] = res["torch_" + f]["ms_median"] / res["as_" + f]["ms_median"]
+
+        # the delivery pass: windows that cover whole streams, events around the call and the timed
+        # kernels of the same call in a pass of their own; the call less its timed kernels is an upper
+        # bound of the pass (it holds the one wait, the uploads, the small kernels and the gaps too).
+        # The byte call the same way, for its copy pass, in the same run.
+        wholes = [(i, 0, n_each) for i in range(n_files)]
+        d_all = torch.zeros(n_files * len(pcm), dtype=torch.uint8, device=dev)
+        xall = torch.zeros((n_files, ch, n_each), dtype=torch.float32, device=dev)
+
+        def bound(fn):
+            fn()
+            enc.sync_check(st)
+            assert all_ok(n_each)
+            whole = [event_ms(fn) for _ in range(repeats)]
+            enc.set_timing(True)
+            enc.reset_timing()
+            for _ in range(repeats):
+                fn()
+            enc.sync_check(st)
+            kernels = {name: enc.kernel_time(k)[1] / repeats for name, k in
+                       (("scan_ms", flacgpu.K_SCAN), ("parse_ms", flacgpu.K_DEC_PARSE), ("recon_ms", flacgpu.K_DEC_RECON))}
+            enc.set_timing(False)
+            return dict(summary(whole), **kernels), statistics.median(whole) - sum(kernels.values())
+
+        res["whole_stream_as_f32"], deliver_ms = bound(lambda: deliver(wholes, flacgpu.SAMPLE_F32, xall))
+        res["whole_stream_as_f32"]["deliver_ms_upper_bound"] = deliver_ms
+        res["whole_stream_as_f32"]["deliver_gb_per_s_at_least"] = 3 * n_files * len(pcm) / deliver_ms / 1e6  # read + write twice as wide
+        want = torch.from_numpy(np.frombuffer(pcm, dtype=np.int16).reshape(n_each, ch).T.astype(np.float32) * np.float32(2.0 ** -15))
+        assert torch.equal(xall[0].cpu(), want) and torch.equal(xall[-1].cpu(), want)
+        res["whole_stream_bytes"], copy_ms = bound(lambda: copy(wholes, d_all))
+        res["whole_stream_bytes"]["copy_ms_upper_bound"] = copy_ms
+        res["pcm_bytes"] = n_files * len(pcm)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dec_rate.json"))
@@ -537,13 +682,21 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows"), default="all")
+    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver"), default="all")
+    ap.add_argument("--deliver-out", default=os.path.join(ROOT, "profiles", "decode_deliver_rate.json"))
     ap.add_argument("--windows-out", default=os.path.join(ROOT, "profiles", "decode_windows_rate.json"))
     ap.add_argument("--window", type=int, default=65536)
     ap.add_argument("--files-out", default=os.path.join(ROOT, "profiles", "decode_files_rate.json"))
     ap.add_argument("--files", type=int, default=64)
     ap.add_argument("--index-out", default=os.path.join(ROOT, "profiles", "index_rate.json"))
     a = ap.parse_args()
+    if a.legs == "deliver":  # opt-in: `all` leaves it out
+        dr = {"c2": deliver_rate(a.files, a.frames // a.files, a.window, a.warmup, a.repeats)}
+        print(json.dumps({"deliver": dr}), flush=True)
+        with open(a.deliver_out, "w") as f:
+            json.dump(dr, f, indent=1)
+            f.write("\n")
+        return
     if a.legs in ("all", "windows"):
         wr = {"c2": windows_rate(a.files, a.frames // a.files, a.window, a.warmup, a.repeats)}
         print(json.dumps({"windows": wr}), flush=True)

@@ -141,6 +141,9 @@ struct WindowArg;
 struct Cover;
 struct WindowResult;
 }
+namespace deliver {
+struct Delivery;
+}
 
 // shared by the translation units that include this header, not exported from libflacgpu.so
 #define FG_LOCAL __attribute__((visibility("hidden")))
@@ -177,12 +180,16 @@ hipError_t launch_positions(const uint8_t *data, const window::PosStream *d_stre
                             const uint64_t *f_off, const uint32_t *f_bytes, const idx::IndexResult *ires, uint64_t *pos,
                             uint64_t *totals, hipStream_t st);
 hipError_t launch_window_cover(const window::WindowArg *args, const idx::IndexResult *ires, const uint64_t *pos,
-                               const uint64_t *totals, uint32_t per, window::Cover *recs, uint32_t n, hipStream_t st);
+                               const uint64_t *totals, uint32_t unit, uint32_t flags, window::Cover *recs, uint32_t n,
+                               hipStream_t st);
 hipError_t launch_window_init(const window::Cover *recs, streams::StreamResult *res, uint64_t *carried, uint32_t n,
                               hipStream_t st);
 hipError_t launch_window_copy(const window::Cover *recs, const streams::StreamResult *res, const uint8_t *scratch,
                               const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off, uint32_t per, uint32_t n,
                               uint64_t max_bytes, hipStream_t st);
+hipError_t launch_window_deliver(const window::Cover *recs, const streams::StreamResult *res, const window::WindowArg *args,
+                                 const uint8_t *scratch, const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off,
+                                 const deliver::Delivery &dv, uint32_t n, uint64_t max_samples, hipStream_t st);
 hipError_t launch_window_results(const window::Cover *recs, const streams::StreamResult *res, window::WindowResult *out,
                                  uint32_t n, hipStream_t st);
 // fg_misc.hip

@@ -4,8 +4,9 @@
 // many-streams forms: the index of n streams in one call, decode chunks that span streams
 // (fg_streams.hpp, fg_dec_streams.hip), and the device side of flacgpu_decode_files; and the
 // sample-window decode (fg_window.hpp, fg_window.hip): the positions of indexed streams, windows
-// over resident tables, and the device side of flacgpu_decode_files_windows.  The
-// host-only side (metadata, the host index, flacgpu_decode_file / _files) is fg_dec_api.cpp.
+// over resident tables -- as PCM bytes or as tensor elements (fg_deliver.hpp) -- and the device
+// side of flacgpu_decode_files_windows.  The host-only side (metadata, the host index,
+// flacgpu_decode_file / _files) is fg_dec_api.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include "../../include/flacgpu.h"
 #include "fg_ctx.hpp"
 #include "fg_dec.hpp"
+#include "fg_deliver.hpp"
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
 #include "fg_streams.hpp"
@@ -26,6 +28,10 @@ static_assert(sizeof(window::WindowResult) == sizeof(flacgpu_window_result), "wi
 static_assert(FLACGPU_WINDOW_BAD_INDEX == (int)window::WIN_BAD_INDEX && FLACGPU_WINDOW_BAD_FRAME == (int)window::WIN_BAD_FRAME &&
                   FLACGPU_WINDOW_TOO_SMALL == (int)window::WIN_TOO_SMALL,
               "window status codes");
+static_assert(FLACGPU_SAMPLE_I32 == (int)deliver::SAMPLE_I32 && FLACGPU_SAMPLE_F32 == (int)deliver::SAMPLE_F32 &&
+                  FLACGPU_SAMPLE_F16 == (int)deliver::SAMPLE_F16 && FLACGPU_SAMPLE_BF16 == (int)deliver::SAMPLE_BF16 &&
+                  FLACGPU_DELIVER_PLANAR == (int)deliver::DELIVER_PLANAR && FLACGPU_DELIVER_PAD == (int)deliver::DELIVER_PAD,
+              "sample formats and delivery flags");
 static_assert(sizeof(dec::Result) == sizeof(flacgpu_decode_result), "decode result layout");
 static_assert(sizeof(idx::IndexResult) == sizeof(flacgpu_index_result), "index result layout");
 static_assert(sizeof(streams::StreamResult) == sizeof(flacgpu_stream_result), "stream result layout");
@@ -407,16 +413,18 @@ int positions_core(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const uint
 // The windows of a call between its two halves: as uploaded, and their cover records on both sides.
 struct WindowsCall {
     uint32_t n = 0;
+    window::WindowArg *d_args = nullptr;
     window::Cover *d_recs = nullptr;
     std::vector<window::Cover> recs;
 };
 
 // The first half of a window decode: the windows go to the device, k_window_cover finds their
 // covering frames, and the host waits for st ONCE to read the records.  caps[w]: the bytes of
-// window w's destination.
+// window w's destination, or its elements where dv converts; TOO_SMALL is deliver::too_small's.
 int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexResult *d_ires, const uint64_t *d_pos,
                   const uint64_t *d_totals, uint32_t n, const uint32_t *window_stream, const uint64_t *window_start,
-                  const uint64_t *window_count, const uint64_t *caps, WindowsCall &wc, hipStream_t st) {
+                  const uint64_t *window_count, const uint64_t *caps, const deliver::Delivery &dv, WindowsCall &wc,
+                  hipStream_t st) {
     IdxScratch *x = idx_scratch(c);
     if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
     std::vector<window::WindowArg> args;
@@ -428,19 +436,19 @@ int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexR
     }
     for (uint32_t w = 0; w < n; w++)
         args[w] = {window_start[w], window_count[w], caps[w], table_first[window_stream[w]], window_stream[w], 0u};
-    window::WindowArg *d_args = nullptr;
     auto carve = [&](uint8_t *base) {
         Carve v{base};
-        v.take(n, d_args);
+        v.take(n, wc.d_args);
         return v.take(n, wc.d_recs);
     };
     HIPCHK(grow(x->win_in, x->win_in_cap, carve(nullptr), &st));  // an earlier call may still use the old one
     carve(x->win_in);
     wc.n = n;
-    HIPCHK(hipMemcpyAsync(d_args, args.data(), (uint64_t)n * sizeof(window::WindowArg), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(wc.d_args, args.data(), (uint64_t)n * sizeof(window::WindowArg), hipMemcpyHostToDevice, st));
     {
         Timed t(c, FLACGPU_K_SCAN, st);
-        HIPCHK(launch_window_cover(d_args, d_ires, d_pos, d_totals, c->g.C * (c->g.bits / 8u), wc.d_recs, n, st));
+        const uint32_t unit = dv.format == deliver::SAMPLE_BYTES ? dv.channels * dv.sample_bytes : dv.channels;
+        HIPCHK(launch_window_cover(wc.d_args, d_ires, d_pos, d_totals, unit, dv.flags, wc.d_recs, n, st));
     }
     HIPCHK(hipMemcpyAsync(wc.recs.data(), wc.d_recs, (uint64_t)n * sizeof(window::Cover), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -451,10 +459,12 @@ int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexR
 // covering frames are its frames, cut with all the others' into chunks of max_frames; its PCM
 // region is span * per bytes of the context's window scratch (bases 16-byte aligned); its result is
 // a scratch StreamResult.  After the last chunk k_window_copy moves each clean window's bytes to
-// d_pcm_out + out_offsets[w], and k_window_results writes d_results.
+// d_pcm_out + out_offsets[w] -- or, where dv converts, k_window_deliver writes its elements from
+// element out_offsets[w] of d_pcm_out on -- and k_window_results writes d_results.
 int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_first, const uint64_t *d_foff,
-                   const uint32_t *d_fbytes, const WindowsCall &wc, const uint32_t *window_stream, uint8_t *d_pcm_out,
-                   const uint64_t *out_offsets, window::WindowResult *d_results, hipStream_t st) {
+                   const uint32_t *d_fbytes, const WindowsCall &wc, const uint32_t *window_stream,
+                   const uint64_t *window_count, const deliver::Delivery &dv, uint8_t *d_pcm_out, const uint64_t *out_offsets,
+                   window::WindowResult *d_results, hipStream_t st) {
     DecScratch *d = c->dec;
     IdxScratch *x = c->idx;
     const uint32_t n = wc.n;
@@ -462,7 +472,9 @@ int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_
     std::vector<uint64_t> frames, host;
     std::vector<streams::Segment> segs;
     std::vector<uint32_t> chunk_seg;
+    const bool convert = dv.format != deliver::SAMPLE_BYTES;
     uint64_t whole = 0, max_bytes = 0;  // whole: the end of the last region, the capacity k_dec_recon checks
+    uint64_t max_written = 0;           // convert: the most samples a window writes, its padding included
     try {
         frames.assign(n, 0);
         host.assign(4u * (uint64_t)n, 0);
@@ -472,6 +484,8 @@ int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_
             host[w] = whole;
             host[2u * (uint64_t)n + w] = table_first[window_stream[w]] + r.first_frame;
             host[3u * (uint64_t)n + w] = out_offsets[w];
+            if (convert && r.status == window::WIN_OK)
+                max_written = std::max(max_written, deliver::written_samples(r.n_samples, window_count[w], dv.flags));
             if (!decode) continue;
             if (r.span > (1ull << 40) || r.n_samples > r.span) return FLACGPU_ERR_INVALID_INPUT;  // no stream's positions
             frames[w] = r.n_frames;
@@ -516,7 +530,10 @@ int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_
                                 st, &cs);
         if (rc) return rc;
     }
-    HIPCHK(launch_window_copy(wc.d_recs, sres, x->win_pcm, d_base, d_pcm_out, d_dst, (uint32_t)per, n, max_bytes, st));
+    if (convert)
+        HIPCHK(launch_window_deliver(wc.d_recs, sres, wc.d_args, x->win_pcm, d_base, d_pcm_out, d_dst, dv, n, max_written, st));
+    else
+        HIPCHK(launch_window_copy(wc.d_recs, sres, x->win_pcm, d_base, d_pcm_out, d_dst, (uint32_t)per, n, max_bytes, st));
     HIPCHK(launch_window_results(wc.d_recs, sres, d_results, n, st));
     return FLACGPU_OK;
 }
@@ -665,6 +682,39 @@ int flacgpu_flac_positions_streams_device(flacgpu_ctx *c, const uint8_t *d_data,
                           d_stream_samples, pick_stream(c, hip_stream));
 }
 
+namespace {
+
+// flacgpu_decode_windows_device (format SAMPLE_BYTES, no flags: offsets and caps in bytes) and
+// flacgpu_decode_windows_device_as (offsets and caps in elements) behind their own checks
+int windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
+                   const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes, const flacgpu_index_result *d_index_results,
+                   const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples, uint32_t n_windows,
+                   const uint32_t *window_stream, const uint64_t *window_start, const uint64_t *window_count,
+                   uint32_t sample_format, uint32_t flags, void *d_out, const uint64_t *offsets, const uint64_t *caps,
+                   flacgpu_window_result *d_results, void *hip_stream) {
+    if (!c || !d_data || !table_first || !d_frame_offsets || !d_frame_bytes || !d_index_results || !d_frame_first_sample ||
+        !d_stream_samples || n_windows > 65535u)
+        return FLACGPU_ERR_INVALID_INPUT;
+    if (n_windows && (!window_stream || !window_start || !window_count || !d_out || !offsets || !caps || !d_results))
+        return FLACGPU_ERR_INVALID_INPUT;
+    for (uint32_t w = 0; w < n_windows; w++)
+        if (window_stream[w] >= n_streams || offsets[w] + caps[w] < offsets[w]) return FLACGPU_ERR_INVALID_INPUT;
+    if (n_windows == 0) return FLACGPU_OK;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = dec_scratch(c);
+    if (rc) return rc;
+    hipStream_t st = pick_stream(c, hip_stream);
+    const deliver::Delivery dv{sample_format, flags, c->g.C, c->g.bits / 8u};
+    WindowsCall wc;
+    rc = windows_cover(c, table_first, (const idx::IndexResult *)d_index_results, d_frame_first_sample, d_stream_samples,
+                       n_windows, window_stream, window_start, window_count, caps, dv, wc, st);
+    if (rc) return rc;
+    return windows_decode(c, d_data, table_first, d_frame_offsets, d_frame_bytes, wc, window_stream, window_count, dv,
+                          (uint8_t *)d_out, offsets, (window::WindowResult *)d_results, st);
+}
+
+}  // namespace
+
 int flacgpu_decode_windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
                                   const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
                                   const flacgpu_index_result *d_index_results, const uint64_t *d_frame_first_sample,
@@ -672,24 +722,24 @@ int flacgpu_decode_windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_
                                   const uint64_t *window_start, const uint64_t *window_count, uint8_t *d_pcm_out,
                                   const uint64_t *pcm_offsets, const uint64_t *pcm_caps, flacgpu_window_result *d_results,
                                   void *hip_stream) {
-    if (!c || !d_data || !table_first || !d_frame_offsets || !d_frame_bytes || !d_index_results || !d_frame_first_sample ||
-        !d_stream_samples || n_windows > 65535u)
+    return windows_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results,
+                          d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
+                          deliver::SAMPLE_BYTES, 0u, d_pcm_out, pcm_offsets, pcm_caps, d_results, hip_stream);
+}
+
+int flacgpu_decode_windows_device_as(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
+                                     const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                     const flacgpu_index_result *d_index_results, const uint64_t *d_frame_first_sample,
+                                     const uint64_t *d_stream_samples, uint32_t n_windows, const uint32_t *window_stream,
+                                     const uint64_t *window_start, const uint64_t *window_count, uint32_t sample_format,
+                                     uint32_t flags, void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
+                                     flacgpu_window_result *d_results, void *hip_stream) {
+    if (!c || sample_format >= deliver::SAMPLE_FORMATS || (flags & ~deliver::DELIVER_FLAGS) ||
+        ((uintptr_t)d_out & (deliver::elem_size(sample_format) - 1u)))
         return FLACGPU_ERR_INVALID_INPUT;
-    if (n_windows && (!window_stream || !window_start || !window_count || !d_pcm_out || !pcm_offsets || !pcm_caps || !d_results))
-        return FLACGPU_ERR_INVALID_INPUT;
-    for (uint32_t w = 0; w < n_windows; w++)
-        if (window_stream[w] >= n_streams || pcm_offsets[w] + pcm_caps[w] < pcm_offsets[w]) return FLACGPU_ERR_INVALID_INPUT;
-    if (n_windows == 0) return FLACGPU_OK;
-    HIPCHK(hipSetDevice(c->device));
-    int rc = dec_scratch(c);
-    if (rc) return rc;
-    hipStream_t st = pick_stream(c, hip_stream);
-    WindowsCall wc;
-    rc = windows_cover(c, table_first, (const idx::IndexResult *)d_index_results, d_frame_first_sample, d_stream_samples,
-                       n_windows, window_stream, window_start, window_count, pcm_caps, wc, st);
-    if (rc) return rc;
-    return windows_decode(c, d_data, table_first, d_frame_offsets, d_frame_bytes, wc, window_stream, d_pcm_out, pcm_offsets,
-                          (window::WindowResult *)d_results, st);
+    return windows_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results,
+                          d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
+                          sample_format, flags, d_out, out_offsets, out_caps, d_results, hip_stream);
 }
 
 // every chunk's frames and frame table are uploaded, its results land at results + f0
@@ -943,9 +993,10 @@ int fg::decode_files_windows_resident(flacgpu_ctx *c, uint32_t n, const uint8_t 
     if (rc) return rc;
     rc = positions_core(c, d->d_frames, n, first.data(), caps.data(), f_off, f_bytes, d_ires, bits, rates, f_pos, d_totals, st);
     if (rc) return rc;
+    const deliver::Delivery bytes{deliver::SAMPLE_BYTES, 0u, c->g.C, c->g.bits / 8u};
     WindowsCall wc;
-    rc = windows_cover(c, first.data(), d_ires, f_pos, d_totals, n_windows, window_file, window_start, window_count, pcm_cap, wc,
-                       st);
+    rc = windows_cover(c, first.data(), d_ires, f_pos, d_totals, n_windows, window_file, window_start, window_count, pcm_cap,
+                       bytes, wc, st);
     if (rc) return rc;
     uint64_t out_total = 0;
     for (uint32_t w = 0; w < n_windows; w++) {
@@ -964,7 +1015,8 @@ int fg::decode_files_windows_resident(flacgpu_ctx *c, uint32_t n, const uint8_t 
     };
     HIPCHK(grow(x->win_out, x->win_out_cap, carve(nullptr), &st));
     carve(x->win_out);
-    rc = windows_decode(c, d->d_frames, first.data(), f_off, f_bytes, wc, window_file, d_out, out_offs.data(), d_wres, st);
+    rc = windows_decode(c, d->d_frames, first.data(), f_off, f_bytes, wc, window_file, window_count, bytes, d_out,
+                        out_offs.data(), d_wres, st);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(res.data(), d_wres, (uint64_t)n_windows * sizeof(window::WindowResult), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));

@@ -1,0 +1,131 @@
+// fg_deliver.hpp -- the scalar rules of delivering decoded sample windows as tensor elements,
+// shared by the device kernel (k_window_deliver, fg_window.hip), the host layer (fg_dec_host.cpp)
+// and the stand-alone host program of the tests (tests/cpp/deliver_host_main.cpp).  Compiles under
+// hipcc and plain g++.
+//
+// A SOURCE SAMPLE is the B = bits / 8 bytes at a byte address of any alignment: signed two's
+// complement, little-endian, sign-extended to i32 -- what every decode call here writes to PCM,
+// 8-bit included.  An ELEMENT is that sample in one of four formats (SAMPLE_*).  A window of
+// `count` stated samples, n of them delivered after clipping, of C channels goes to a region of
+// elements: sample t, channel c at t * C + c (interleaved) or c * count + t (DELIVER_PLANAR);
+// with DELIVER_PAD the elements of t in [n, count) are written as zero.  A ROW is a run of
+// consecutive destination elements (one plane, or the whole interleaved region); its ROW PLAN cuts
+// it into the elements before the first 16-byte boundary, whole 16-byte units and the elements
+// after them: the element-granular counterpart of window::copy_plan.
+#pragma once
+#include <stdint.h>
+
+#include "fg_crc.hpp"  // FG_HD
+
+namespace fg {
+namespace deliver {
+
+enum : uint32_t { SAMPLE_I32 = 0, SAMPLE_F32 = 1, SAMPLE_F16 = 2, SAMPLE_BF16 = 3, SAMPLE_FORMATS = 4 };  // = FLACGPU_SAMPLE_*
+enum : uint32_t { DELIVER_PLANAR = 1, DELIVER_PAD = 2, DELIVER_FLAGS = 3 };                               // = FLACGPU_DELIVER_*
+constexpr uint32_t SAMPLE_BYTES = 0xFFFFFFFFu;  // not an element format: the byte copy of flacgpu_decode_windows_device
+
+// How a window call delivers: `format` SAMPLE_BYTES copies the PCM bytes (k_window_copy, flags 0);
+// any other format converts (k_window_deliver).
+struct Delivery {
+    uint32_t format, flags, channels, sample_bytes;
+};
+
+FG_HD uint32_t elem_size(uint32_t format) { return format <= SAMPLE_F32 ? 4u : 2u; }
+
+// the B bytes at p, any alignment, as a sign-extended little-endian integer
+FG_HD int32_t load_sample(const uint8_t *p, uint32_t B) {
+    uint32_t v = 0;
+    for (uint32_t i = 0; i < B; i++) v |= (uint32_t)p[i] << (8u * i);
+    const uint32_t sh = 32u - 8u * B;
+    return (int32_t)(v << sh) >> sh;
+}
+
+// The same sample out of little-endian 32-bit words: the B bytes at byte offset `off` of `words`.
+// Only the words that hold one of those bytes are read.
+FG_HD int32_t sample_in_words(const uint32_t *words, uint32_t off, uint32_t B) {
+    const uint32_t i = off >> 2, r = off & 3u;
+    uint64_t v = words[i];
+    if (r + B > 4u) v |= (uint64_t)words[i + 1u] << 32;
+    const uint32_t sh = 32u - 8u * B;
+    return (int32_t)((uint32_t)(v >> (8u * r)) << sh) >> sh;
+}
+
+// (float)x * 2^-(bits-1) as its bit pattern.  The conversion rounds to nearest-even (inexact only
+// for 32-bit samples with |x| >= 2^24); the scale is a power of two and a normal f32, so the
+// product is exact.  The value lies in [-1, 1].
+FG_HD uint32_t f32_bits(int32_t x, uint32_t bits) {
+    union {
+        float f;
+        uint32_t u;
+    } s, v;
+    s.u = (127u - (bits - 1u)) << 23;
+    v.f = (float)x * s.f;
+    return v.u;
+}
+
+// f32 -> bf16, round to nearest-even, by integer arithmetic on the bit pattern (no NaN can occur)
+FG_HD uint16_t bf16_bits(uint32_t f) { return (uint16_t)((f + 0x7FFFu + ((f >> 16) & 1u)) >> 16); }
+
+// f32 -> f16, round to nearest-even, subnormal results kept, by integer arithmetic on the bit
+// pattern; for |value| <= 1 (no overflow, no NaN).
+FG_HD uint16_t f16_bits(uint32_t f) {
+    const uint32_t sign = (f >> 16) & 0x8000u, a = f & 0x7FFFFFFFu, e = a >> 23;
+    if (e >= 113u) {  // >= 2^-14, a normal f16: a rounding that carries goes into the exponent field, as it should
+        uint32_t r = a - (112u << 23);
+        r += 0xFFFu + ((r >> 13) & 1u);
+        return (uint16_t)(sign | (r >> 13));
+    }
+    if (e < 102u) return (uint16_t)sign;  // < 2^-25: rounds to zero
+    // a subnormal f16, in units of 2^-24: m * 2^(e - 150) = m >> (126 - e)
+    const uint32_t m = (a & 0x7FFFFFu) | 0x800000u, s = 126u - e;  // 14 <= s <= 24
+    uint32_t q = m >> s;
+    const uint32_t rem = m & ((1u << s) - 1u), half = 1u << (s - 1u);
+    if (rem > half || (rem == half && (q & 1u))) q++;
+    return (uint16_t)(sign | q);  // q = 0x400 is the smallest normal
+}
+
+// the element of sample x (of `bits` bits) in `format`: 32 bits, or 16 in the low half
+FG_HD uint32_t element(int32_t x, uint32_t bits, uint32_t format) {
+    if (format == SAMPLE_I32) return (uint32_t)x;
+    const uint32_t f = f32_bits(x, bits);
+    if (format == SAMPLE_F32) return f;
+    return format == SAMPLE_F16 ? f16_bits(f) : bf16_bits(f);
+}
+
+// The capacity rule.  A window that delivers n of its `count` stated samples needs count * unit of
+// its capacity under PLANAR or PAD (the layout is the stated one), else n * unit; unit = channels
+// for a capacity in elements, channels * bytes per sample for one in bytes.  No product is formed,
+// so count = 2^64 - 1 is too small and does not wrap; count = 0 needs nothing.
+FG_HD bool too_small(uint64_t n, uint64_t count, uint32_t flags, uint64_t cap, uint32_t unit) {
+    return ((flags & (DELIVER_PLANAR | DELIVER_PAD)) ? count : n) > cap / unit;
+}
+
+// The samples a clean window writes: all `count` under PAD, else the n delivered.
+FG_HD uint64_t written_samples(uint64_t n, uint64_t count, uint32_t flags) { return (flags & DELIVER_PAD) ? count : n; }
+
+// A row of n elements of esz (2 or 4) bytes at dst_addr (a multiple of esz): `head` elements up to
+// the first 16-byte boundary (all of them where the row ends before it), `units` whole 16-byte
+// units, `tail` elements after the last.
+struct RowPlan {
+    uint32_t head, tail;
+    uint64_t units;
+};
+FG_HD RowPlan row_plan(uint64_t dst_addr, uint64_t n, uint32_t esz) {
+    RowPlan p;
+    const uint64_t to_boundary = ((16u - (dst_addr & 15u)) & 15u) / esz, per_unit = 16u / esz;
+    p.head = (uint32_t)(to_boundary < n ? to_boundary : n);
+    p.units = (n - p.head) / per_unit;
+    p.tail = (uint32_t)((n - p.head) % per_unit);
+    return p;
+}
+
+// ---- the tile of k_window_deliver --------------------------------------------------------------
+// A workgroup takes kTileBytes / per consecutive samples of one window (per = channels * bytes per
+// sample <= 32, so at least 128): their source bytes go to LDS as the aligned 8-byte words that
+// hold them, at most kTileWords.
+constexpr uint32_t kTileBytes = 4096;
+constexpr uint32_t kTileWords = (kTileBytes + 7u + 7u) / 8u;
+FG_HD uint32_t tile_samples(uint32_t per) { return kTileBytes / per; }
+
+}  // namespace deliver
+}  // namespace fg

@@ -9,6 +9,9 @@
 //                     chunk loop in which a window is what a stream is in fg_dec_streams.hip
 //   k_window_copy     per window (blockIdx.y), after the last chunk: the delivered bytes from the
 //                     window's decoded covering frames to the caller's region
+//   k_window_deliver  in place of k_window_copy for flacgpu_decode_windows_device_as: the delivered
+//                     samples converted to tensor elements (fg_deliver.hpp), interleaved or planar,
+//                     the rest of a padded window zeroed
 //   k_window_results  per window: its flacgpu_window_result
 //
 // Every index is bounded by what the index left and the host sized: a frame i of stream s is
@@ -16,6 +19,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fg_common.hpp"
+#include "fg_deliver.hpp"
 #include "fg_index.hpp"
 #include "fg_streams.hpp"
 #include "fg_window.hpp"
@@ -76,7 +80,8 @@ __global__ void __launch_bounds__(256) k_pos_scan(const PosStream *streams, cons
 }
 
 __global__ void __launch_bounds__(256) k_window_cover(const WindowArg *args, const idx::IndexResult *ires, const uint64_t *pos,
-                                                       const uint64_t *totals, uint32_t per, Cover *recs, uint32_t n) {
+                                                       const uint64_t *totals, uint32_t unit, uint32_t flags, Cover *recs,
+                                                       uint32_t n) {
     const uint32_t w = blockIdx.x * 256u + threadIdx.x;
     if (w >= n) return;
     const WindowArg a = args[w];
@@ -87,7 +92,8 @@ __global__ void __launch_bounds__(256) k_window_cover(const WindowArg *args, con
         c.status = WIN_BAD_INDEX;
     } else {
         c = cover(pos + a.table_first, r.n_frames, totals[a.stream], a.start, a.count);
-        if (c.n_samples > a.cap / per) c.status = WIN_TOO_SMALL;  // n_samples * per > cap, with no product to overflow
+        // the byte copy: unit = per, no flags, so n_samples * per > cap with no product to overflow
+        if (deliver::too_small(c.n_samples, a.count, flags, a.cap, unit)) c.status = WIN_TOO_SMALL;
     }
     recs[w] = c;
 }
@@ -139,6 +145,90 @@ __global__ void __launch_bounds__(256) k_window_copy(const Cover *recs, const st
     }
 }
 
+// One element of a tile: source element si of the tile's `have` (sample-major, channel-minor, as
+// they lie in the LDS words from byte `lead` on), or zero past them (the padding).
+__device__ __forceinline__ uint32_t tile_element(const uint32_t *words, uint32_t lead, uint32_t si, uint32_t have,
+                                                 const deliver::Delivery &dv) {
+    if (si >= have) return 0u;
+    return deliver::element(deliver::sample_in_words(words, lead + si * dv.sample_bytes, dv.sample_bytes), 8u * dv.sample_bytes,
+                            dv.format);
+}
+
+__device__ __forceinline__ void store_element(uint8_t *row, uint64_t e, uint32_t esz, uint32_t v) {
+    if (esz == 4u) ((uint32_t *)row)[e] = v;
+    else ((uint16_t *)row)[e] = (uint16_t)v;
+}
+
+// In place of k_window_copy: window w (blockIdx.y) as elements of dv.format to out + dst_off[w]
+// elements.  A workgroup takes tiles of tile_samples(per) consecutive samples: the aligned 8-byte
+// words of the scratch that hold a tile's source bytes go to LDS (no word past the one that holds
+// the window's last byte is read; a tile of padding alone reads nothing), then every row of the
+// tile -- a plane's part, or the interleaved tile -- is written by its row plan: whole 16-byte
+// units built from LDS, one thread a unit, and the head and tail elements one at a time.  A window
+// that is not clean writes nothing; one with no samples still writes its padding.
+__global__ void __launch_bounds__(256) k_window_deliver(const Cover *recs, const streams::StreamResult *res, const WindowArg *args,
+                                                         const uint8_t *scratch, const uint64_t *src_base, uint8_t *out,
+                                                         const uint64_t *dst_off, deliver::Delivery dv) {
+    __shared__ uint64_t s_src[deliver::kTileWords];
+    const uint32_t w = blockIdx.y, tid = threadIdx.x;
+    const Cover c = recs[w];
+    if (!window_clean(c, res[w])) return;
+    const uint64_t count = args[w].count, n = c.n_samples;
+    const uint64_t total = deliver::written_samples(n, count, dv.flags);
+    if (total == 0) return;
+    const uint32_t C = dv.channels, per = C * dv.sample_bytes, esz = deliver::elem_size(dv.format), per_unit = 16u / esz;
+    const uint32_t T = deliver::tile_samples(per);
+    const bool planar = (dv.flags & deliver::DELIVER_PLANAR) != 0;
+    const uint8_t *src = scratch + src_base[w] + c.skip * per;
+    uint8_t *dst = out + dst_off[w] * esz;
+    const uint64_t n_tiles = (total + T - 1u) / T;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint64_t t0 = tile * T;
+        const uint32_t ns = (uint32_t)(total - t0 < T ? total - t0 : T);             // samples written
+        const uint32_t nsrc = t0 < n ? (uint32_t)(n - t0 < T ? n - t0 : T) : 0u;     // of them decoded ones
+        uint32_t lead = 0;
+        if (nsrc) {
+            const uintptr_t a = (uintptr_t)(src + t0 * per), a0 = a & ~(uintptr_t)7;
+            lead = (uint32_t)(a - a0);
+            const uint32_t n_words = (lead + nsrc * per + 7u) / 8u;  // <= kTileWords
+            for (uint32_t i = tid; i < n_words; i += 256u) s_src[i] = ((const uint64_t *)a0)[i];
+        }
+        __syncthreads();
+        const uint32_t *words = (const uint32_t *)s_src;
+        const uint32_t have = nsrc * C;
+        const uint32_t rows = planar ? C : 1u, row_elems = planar ? ns : ns * C;
+        const uint32_t max_units = row_elems / per_unit, slots = max_units + 2u;  // a row's units, its head, its tail
+        for (uint32_t item = tid; item < rows * slots; item += 256u) {
+            const uint32_t r = item / slots, k = item - r * slots;
+            uint8_t *row = dst + (planar ? (uint64_t)r * count + t0 : t0 * C) * esz;
+            const deliver::RowPlan p = deliver::row_plan((uint64_t)(uintptr_t)row, row_elems, esz);
+            const uint32_t mul = planar ? C : 1u, add = planar ? r : 0u;  // row element e is source element e * mul + add
+            if (k < max_units) {
+                if (k >= p.units) continue;
+                const uint32_t e0 = p.head + k * per_unit;
+                uint32_t q[4];
+                if (esz == 4u) {
+#pragma unroll
+                    for (uint32_t j = 0; j < 4u; j++) q[j] = tile_element(words, lead, (e0 + j) * mul + add, have, dv);
+                } else {
+#pragma unroll
+                    for (uint32_t j = 0; j < 4u; j++)
+                        q[j] = tile_element(words, lead, (e0 + 2u * j) * mul + add, have, dv) |
+                               (tile_element(words, lead, (e0 + 2u * j + 1u) * mul + add, have, dv) << 16);
+                }
+                *(uint4 *)(row + (uint64_t)e0 * esz) = make_uint4(q[0], q[1], q[2], q[3]);
+            } else if (k == max_units) {
+                for (uint32_t e = 0; e < p.head; e++) store_element(row, e, esz, tile_element(words, lead, e * mul + add, have, dv));
+            } else {
+                const uint32_t e1 = p.head + (uint32_t)p.units * per_unit;
+                for (uint32_t e = e1; e < e1 + p.tail; e++)
+                    store_element(row, e, esz, tile_element(words, lead, e * mul + add, have, dv));
+            }
+        }
+        __syncthreads();  // s_src is written again by the next tile
+    }
+}
+
 __global__ void __launch_bounds__(256) k_window_results(const Cover *recs, const streams::StreamResult *res, WindowResult *out,
                                                          uint32_t n) {
     const uint32_t w = blockIdx.x * 256u + threadIdx.x;
@@ -179,10 +269,11 @@ hipError_t launch_positions(const uint8_t *data, const PosStream *d_streams, uin
     return hipGetLastError();
 }
 
+// unit, flags: the capacity rule's (deliver::too_small); the byte copy passes per and 0
 hipError_t launch_window_cover(const WindowArg *args, const idx::IndexResult *ires, const uint64_t *pos, const uint64_t *totals,
-                               uint32_t per, Cover *recs, uint32_t n, hipStream_t st) {
+                               uint32_t unit, uint32_t flags, Cover *recs, uint32_t n, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_window_cover, dim3((n + 255u) / 256u), dim3(256), 0, st, args, ires, pos, totals, per, recs, n);
+    hipLaunchKernelGGL(k_window_cover, dim3((n + 255u) / 256u), dim3(256), 0, st, args, ires, pos, totals, unit, flags, recs, n);
     return hipGetLastError();
 }
 
@@ -200,6 +291,18 @@ hipError_t launch_window_copy(const Cover *recs, const streams::StreamResult *re
     const uint64_t blocks = (max_bytes / 16u + 255u) / 256u;
     const uint32_t gx = (uint32_t)(blocks < 1u ? 1u : (blocks > 256u ? 256u : blocks));
     hipLaunchKernelGGL(k_window_copy, dim3(gx, n), dim3(256), 0, st, recs, res, scratch, src_base, out, dst_off, per);
+    return hipGetLastError();
+}
+
+// n <= 65535 (gridDim.y); max_samples: the most any window writes, padding included, which sizes gridDim.x
+hipError_t launch_window_deliver(const Cover *recs, const streams::StreamResult *res, const WindowArg *args,
+                                 const uint8_t *scratch, const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off,
+                                 const deliver::Delivery &dv, uint32_t n, uint64_t max_samples, hipStream_t st) {
+    if (n == 0 || max_samples == 0) return hipSuccess;
+    const uint32_t T = deliver::tile_samples(dv.channels * dv.sample_bytes);
+    const uint64_t tiles = (max_samples + T - 1u) / T;
+    const uint32_t gx = (uint32_t)(tiles > 1024u ? 1024u : tiles);
+    hipLaunchKernelGGL(k_window_deliver, dim3(gx, n), dim3(256), 0, st, recs, res, args, scratch, src_base, out, dst_off, dv);
     return hipGetLastError();
 }
 

@@ -362,6 +362,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_flac_positions_streams_device": (I32, [P, P, U32, P, P, P, P, P, P, P, P, P, P]),
         "flacgpu_decode_windows_device": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, P, P, P, P, P]),
         "flacgpu_decode_files_windows": (I32, [P, U32, P, P, U32, P, P, P, P, P, P, P]),
+        "flacgpu_decode_windows_device_as": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, U32, P, P, P, P, P]),
     }
     # an older build named by FLACGPU_LIB (same-box A/B runs, tools/ab.sh) may predate later entry
     # points: those stay unbound there; the in-tree library must export every one
@@ -399,6 +400,7 @@ def exported_symbols() -> list:
         "flacgpu_decode_file", "flacgpu_flac_index_device",
         "flacgpu_flac_index_streams_device", "flacgpu_decode_streams_device", "flacgpu_decode_files",
         "flacgpu_flac_positions_streams_device", "flacgpu_decode_windows_device", "flacgpu_decode_files_windows",
+        "flacgpu_decode_windows_device_as",
     ]
 
 
@@ -513,6 +515,11 @@ class WindowResult(ctypes.Structure):
                 ("status", ctypes.c_uint32), ("first_bad_frame", ctypes.c_uint32), ("first_bad_status", ctypes.c_uint32)]
 
 
+SAMPLE_I32, SAMPLE_F32, SAMPLE_F16, SAMPLE_BF16 = range(4)  # FLACGPU_SAMPLE_*: the element formats of a delivery
+ELEMENT_BYTES = {SAMPLE_I32: 4, SAMPLE_F32: 4, SAMPLE_F16: 2, SAMPLE_BF16: 2}  # their element sizes
+DELIVER_PLANAR, DELIVER_PAD = 1, 2  # FLACGPU_DELIVER_*
+
+
 def _u64s(v: Sequence[int]):
     return (ctypes.c_uint64 * max(len(v), 1))(*v)
 
@@ -600,6 +607,20 @@ class _DecodeOps:
             d_frame_first_sample, d_stream_samples, len(windows), _u32s([w[0] for w in windows]),
             _u64s([w[1] for w in windows]), _u64s([w[2] for w in windows]), d_pcm_out, _u64s(pcm_offsets),
             _u64s(pcm_caps), d_results, _stream(stream)), "decode_windows_device")
+
+    def decode_windows_device_as(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int, d_frame_bytes: int,
+                                 d_index_results: int, d_frame_first_sample: int, d_stream_samples: int,
+                                 windows: Sequence, sample_format: int, flags: int, d_out: int,
+                                 out_offsets: Sequence[int], out_caps: Sequence[int], d_results: int,
+                                 stream: Optional[int] = None) -> None:
+        """flacgpu_decode_windows_device_as: the windows of decode_windows_device as elements of
+        sample_format (SAMPLE_*), laid out by flags (DELIVER_*); window w's elements from element
+        out_offsets[w] of d_out on, out_caps in elements too."""
+        _check(self.lib.flacgpu_decode_windows_device_as(
+            self.ctx, d_data, len(table_first), _u64s(table_first), d_frame_offsets, d_frame_bytes, d_index_results,
+            d_frame_first_sample, d_stream_samples, len(windows), _u32s([w[0] for w in windows]),
+            _u64s([w[1] for w in windows]), _u64s([w[2] for w in windows]), sample_format, flags, d_out,
+            _u64s(out_offsets), _u64s(out_caps), d_results, _stream(stream)), "decode_windows_device_as")
 
     def decode_files_windows(self, flacs: Sequence[bytes], windows: Sequence, guard: int = 0,
                              pcm_caps: Optional[Sequence[int]] = None):
