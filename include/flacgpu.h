@@ -412,6 +412,23 @@ int flacgpu_encode_files(flacgpu_ctx *ctx, uint32_t n_files, const void *const *
  * (Config.default for the WAV's channels and bit depth). */
 int flacgpu_wav_to_flac(int device, const void *wav, size_t wav_len, uint8_t *out, size_t out_cap, size_t *out_len);
 
+/* A decode-only context (no reference counterpart: the reference has no decoder).  flacgpu_open's
+ * block_size limit, 4096, is the encoder's; RFC 9639's streamable subset allows frames of up to
+ * 16384 samples, and encoders other than this one write them (4608 is a table code).  A context
+ * opened here decodes frames of `channels` x `bits_per_sample` of up to max_block samples:
+ * 1..FLACGPU_DECODER_MAX_BLOCK, and at most FLACGPU_DECODER_MAX_BLOCK_32 at 32 bits per sample, whose
+ * 64-bit sample planes of larger frames do not fit a compute unit's LDS; anything else, and a bad
+ * channel count, depth or rate, is FLACGPU_ERR_INVALID_CONFIG.  It allocates no encode buffers and is
+ * closed by flacgpu_close.  Every entry point of the "Decode and verify" section below but
+ * flacgpu_verify_plan_device works on it, and so do flacgpu_sync_check, flacgpu_get_config (block_size
+ * = max_block, the encode options zero), the timing calls and the streaming MD5 (host engine).  Every entry point that
+ * encodes, and flacgpu_plan_create* (so nothing that needs a plan can be reached), returns
+ * FLACGPU_ERR_INVALID_CONFIG.  max_frames_per_call as in flacgpu_open. */
+#define FLACGPU_DECODER_MAX_BLOCK 16384
+#define FLACGPU_DECODER_MAX_BLOCK_32 8192
+int flacgpu_open_decoder(int device, uint32_t sample_rate, uint8_t channels, uint8_t bits_per_sample,
+                         uint32_t max_block, uint32_t max_frames_per_call, flacgpu_ctx **out);
+
 /* ---- Decode and verify (no reference counterpart: the reference's readme lists a decoder as
  *      queued).  Frames are decoded where the encode entry points leave them; DESIGN.md
  *      "Decode and verify". ------------------------------------------------------------------ */
@@ -439,7 +456,7 @@ typedef struct {                             /* 32 bytes */
  * a difference gives MISMATCH.  A frame with a non-zero status writes no PCM.  d_results[f] and
  * *d_bad_count (frames with a non-zero status) are device memory.  Asynchronous on hip_stream.
  * The decode scratch of a context is allocated by its first decode call.  Blocks larger than
- * the context's block_size are RANGE. */
+ * the context's block_size (flacgpu_open_decoder: max_block) are RANGE. */
 int flacgpu_decode_frames_device(flacgpu_ctx *ctx, const uint8_t *d_frames, const uint64_t *d_frame_offsets,
                                  const uint32_t *d_frame_bytes, uint64_t n_frames, const uint64_t *d_pcm_offsets,
                                  uint8_t *d_pcm_out, uint64_t pcm_cap, const uint8_t *d_pcm_expect,

@@ -42,6 +42,15 @@ view(int16) -> reshape -> to(float32) -> scale -> transpose -> contiguous() in t
 kernels, whose differences bound the delivery pass and the copy pass.
 
     python tools/decode_rate.py --legs deliver --deliver-out profiles/decode_deliver_rate.json
+
+The bigblock leg (--bigblock-out; opt-in, not part of `all`) takes one 16-bit stereo PCM buffer of
+2^20 samples, encoded by the CPU oracle encoder at blocks 4096, 4608 and 16384 (--blocks), as
+--streams streams of one device buffer through flacgpu_decode_streams_device -- the 4096 row on a
+flacgpu_open context, the others on a decode-only one: HIP events around the call, warm-up, the
+median, and the parse and reconstruct kernel times in a pass of their own.  FLACGPU_LIB names
+another build of the library for the same row of an earlier commit.
+
+    python tools/decode_rate.py --legs bigblock --bigblock-out profiles/decode_bigblock_rate.json
 """
 import argparse
 import ctypes
@@ -675,6 +684,72 @@ def deliver_rate(n_files: int, frames_each: int, window: int, warmup: int, repea
     return res
 
 
+def bigblock_rate(blocks, n_streams: int, warmup: int, repeats: int) -> dict:
+    import numpy as np
+    import torch
+
+    import flacgpu
+    import oracle_ref
+    import synth
+
+    ch, bits, rate = 2, 16, 44100
+    per = ch * (bits // 8)
+    dev = torch.device("cuda", 0)
+    n = 1 << 20
+    pcm = synth.synth_pcm(n, ch, bits, rate)
+    res = {"channels": ch, "bits": bits, "streams": n_streams, "samples_per_stream": n, "library": flacgpu.LIB_PATH, "rows": {}}
+    for block in blocks:
+        body, sizes, _ = oracle_ref.encode_stream(pcm, ch, bits, rate, block)
+        frames = len(sizes)
+        offs, at = [], 0
+        for _ in range(n_streams):
+            offs.append(at)
+            at += (len(body) + 63) & ~63
+        host = np.zeros(at + 16, dtype=np.uint8)
+        for o in offs:
+            host[o:o + len(body)] = np.frombuffer(body, dtype=np.uint8)
+        d_buf = torch.from_numpy(host).to(dev)
+        d_all = torch.zeros(n_streams * len(pcm), dtype=torch.uint8, device=dev)
+        d_sres = torch.zeros(32 * n_streams, dtype=torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        lens, pcm_offs, caps = [len(body)] * n_streams, [i * len(pcm) for i in range(n_streams)], [len(pcm)] * n_streams
+        with flacgpu.Decoder(ch, bits, rate, device=0, max_frames=n_streams * frames, block_size=block) as d:
+            def run():
+                d.decode_streams_device(d_buf.data_ptr(), offs, lens, d_all.data_ptr(), pcm_offs, caps, d_sres.data_ptr(),
+                                        stream_bits=[bits] * n_streams, stream_rates=[rate] * n_streams, stream=st)
+
+            for _ in range(warmup):
+                run()
+            d.sync_check(st)
+            sres = (flacgpu.StreamResult * n_streams).from_buffer_copy(d_sres.cpu().numpy().tobytes())
+            assert [(r.n_frames, r.n_samples, r.bad_frames) for r in sres] == [(frames, n, 0)] * n_streams
+            got = d_all.cpu().numpy().tobytes()
+            assert got[:len(pcm)] == pcm and got[-len(pcm):] == pcm, "decoded PCM differs from the input"
+            ms = []
+            for _ in range(repeats):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                run()
+                b.record()
+                b.synchronize()
+                ms.append(a.elapsed_time(b))
+            d.set_timing(True)
+            d.reset_timing()
+            for _ in range(repeats):
+                run()
+            d.sync_check(st)
+            kernels = {name: d.kernel_time(k)[1] / repeats for name, k in
+                       (("index_ms", flacgpu.K_INDEX), ("parse_ms", flacgpu.K_DEC_PARSE), ("recon_ms", flacgpu.K_DEC_RECON))}
+            d.set_timing(False)
+        med = statistics.median(ms)
+        total = n_streams * n
+        res["rows"][str(block)] = dict({"frames": n_streams * frames, "flac_bytes": n_streams * len(body), "ms_median": med,
+                                        "ms_min": min(ms), "ms_max": max(ms), "ms": ms, "msamples_per_s": total / med / 1e3,
+                                        "recon_ns_per_sample": kernels["recon_ms"] * 1e6 / total,
+                                        "parse_ns_per_sample": kernels["parse_ms"] * 1e6 / total}, **kernels)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dec_rate.json"))
@@ -682,7 +757,10 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver"), default="all")
+    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock"), default="all")
+    ap.add_argument("--bigblock-out", default=os.path.join(ROOT, "profiles", "decode_bigblock_rate.json"))
+    ap.add_argument("--blocks", default="4096,4608,16384")
+    ap.add_argument("--streams", type=int, default=16)
     ap.add_argument("--deliver-out", default=os.path.join(ROOT, "profiles", "decode_deliver_rate.json"))
     ap.add_argument("--windows-out", default=os.path.join(ROOT, "profiles", "decode_windows_rate.json"))
     ap.add_argument("--window", type=int, default=65536)
@@ -690,6 +768,13 @@ def main():
     ap.add_argument("--files", type=int, default=64)
     ap.add_argument("--index-out", default=os.path.join(ROOT, "profiles", "index_rate.json"))
     a = ap.parse_args()
+    if a.legs == "bigblock":  # opt-in: `all` leaves it out
+        br = bigblock_rate([int(b) for b in a.blocks.split(",")], a.streams, a.warmup, a.repeats)
+        print(json.dumps({"bigblock": br}), flush=True)
+        with open(a.bigblock_out, "w") as f:
+            json.dump(br, f, indent=1)
+            f.write("\n")
+        return
     if a.legs == "deliver":  # opt-in: `all` leaves it out
         dr = {"c2": deliver_rate(a.files, a.frames // a.files, a.window, a.warmup, a.repeats)}
         print(json.dumps({"deliver": dr}), flush=True)

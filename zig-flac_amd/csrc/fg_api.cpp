@@ -420,6 +420,7 @@ int fg::ctx_download_chunk(flacgpu_ctx *c, uint8_t *out, uint64_t total) {
 }
 
 uint32_t fg::ctx_max_frames(const flacgpu_ctx *c) { return c->max_frames; }
+bool fg::ctx_decode_only(const flacgpu_ctx *c) { return c->decode_only; }
 bool fg::ctx_plain(const flacgpu_ctx *c) { return !c->records_on && !c->timing && c->ovl_chunks <= 1 && !c->g.fused; }
 fg::CtxDevice fg::ctx_device(const flacgpu_ctx *c) {
     return {c->device, (void *)c->stream, c->d_out, c->d_fbytes, c->d_total, c->out_cap, c->g.C, c->g.B,
@@ -566,6 +567,45 @@ int flacgpu_open(int device, const flacgpu_config *cfg, uint32_t max_frames_per_
         hipMemcpy(c->d_crc_join, pj.data(), pj.size() * 2, hipMemcpyHostToDevice) || hipMemset(c->d_err, 0, 16) || hipMemset(c->d_ctr, 0, 4u * kCtrSet * kOvlMaxChunks) ||
         hipMemset(c->d_stamps, 0, 32 * 8))
         return fail(FLACGPU_ERR_DEVICE);
+    flacgpu_md5_init(c);
+    *out = c;
+    return FLACGPU_OK;
+}
+
+// A context that only decodes: the device and stream checks of flacgpu_open, its own stream, and
+// nothing else -- the decoder allocates its scratch on first use (fg_dec_host.cpp), sized by
+// cfg.block_size = max_block.  The limits are dec_geometry's: what k_dec_recon's planes hold.
+int flacgpu_open_decoder(int device, uint32_t sample_rate, uint8_t channels, uint8_t bits_per_sample, uint32_t max_block,
+                         uint32_t max_frames_per_call, flacgpu_ctx **out) {
+    if (!out) return FLACGPU_ERR_INVALID_INPUT;
+    *out = nullptr;
+    if (sample_rate >= (1u << 20)) return FLACGPU_ERR_INVALID_CONFIG;  // u20, as flacgpu_open
+    if (!dec_geometry(channels, bits_per_sample, max_block).ok) return FLACGPU_ERR_INVALID_CONFIG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FLACGPU_ERR_DEVICE;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return FLACGPU_ERR_DEVICE;
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return FLACGPU_ERR_DEVICE;  // code objects are gfx950-only
+    HIPCHK(hipSetDevice(device));
+    auto *c = new (std::nothrow) flacgpu_ctx();
+    if (!c) return FLACGPU_ERR_OUT_OF_MEMORY;
+    c->device = device;
+    c->decode_only = true;
+    c->cfg.sample_rate = sample_rate;
+    c->cfg.block_size = (uint16_t)max_block;  // <= FLACGPU_DECODER_MAX_BLOCK
+    c->cfg.channels = channels;
+    c->cfg.bits_per_sample = bits_per_sample;
+    c->max_frames = max_frames_per_call ? max_frames_per_call : 32768u;
+    c->k = knobs_from_env();
+    c->g.C = channels;
+    c->g.bits = bits_per_sample;
+    c->g.B = bits_per_sample / 8u;
+    // the batched MD5 of decoded streams: the kernel enc_geometry picks for this depth
+    c->g.md5_kernel = c->k.md5_kernel_set ? c->k.md5_kernel : (c->g.B == 4u ? 2 : 1);
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
+        flacgpu_close(c);
+        return FLACGPU_ERR_DEVICE;
+    }
     flacgpu_md5_init(c);
     *out = c;
     return FLACGPU_OK;
@@ -828,6 +868,7 @@ int flacgpu_encode_frames(flacgpu_ctx *c, const void *pcm, uint32_t bytes_per_sa
                           uint64_t first_frame_number, uint8_t *out, size_t out_cap, size_t *out_len,
                           uint32_t *frame_bytes) {
     if (!c || (!pcm && n_samples) || !out_len) return FLACGPU_ERR_INVALID_INPUT;
+    FG_ENCODER_ONLY(c);
     if (bytes_per_sample != c->g.B) return FLACGPU_ERR_INVALID_INPUT;
     HIPCHK(hipSetDevice(c->device));
     *out_len = 0;
@@ -870,7 +911,9 @@ int flacgpu_encode_frames(flacgpu_ctx *c, const void *pcm, uint32_t bytes_per_sa
 
 int flacgpu_encode_frame_planar(flacgpu_ctx *c, const int32_t *const planes[8], uint32_t n, uint64_t frame_number,
                                 uint8_t *out, size_t out_cap, uint32_t *frame_bytes) {
-    if (!c || !planes || !out || n == 0 || n > c->cfg.block_size) return FLACGPU_ERR_INVALID_INPUT;
+    if (!c) return FLACGPU_ERR_INVALID_INPUT;
+    FG_ENCODER_ONLY(c);
+    if (!planes || !out || n == 0 || n > c->cfg.block_size) return FLACGPU_ERR_INVALID_INPUT;
     for (uint32_t ch = 0; ch < c->g.C; ch++)
         if (!planes[ch]) return FLACGPU_ERR_INVALID_INPUT;
     // Encoder.samples[ch][0..n] -> the little-endian interleaved layout the kernels stage
@@ -892,6 +935,7 @@ int flacgpu_encode_frame_planar(flacgpu_ctx *c, const int32_t *const planes[8], 
 // ---- streaming MD5 --------------------------------------------------------
 int flacgpu_md5_set_engine(flacgpu_ctx *c, int engine) {
     if (!c || (engine != FLACGPU_MD5_HOST && engine != FLACGPU_MD5_DEVICE)) return FLACGPU_ERR_INVALID_INPUT;
+    if (engine == FLACGPU_MD5_DEVICE) FG_ENCODER_ONLY(c);  // the device engine's state is an encode buffer
     c->md5_engine = engine;
     return flacgpu_md5_init(c);
 }
@@ -1162,8 +1206,10 @@ int flacgpu_plan_md5_engine(const flacgpu_plan *p) {
 int flacgpu_plan_create_segments(flacgpu_ctx *c, uint32_t n_streams, const uint64_t *offs, const uint64_t *samples,
                                  uint32_t bytes_per_sample, const uint64_t *first_frame_numbers,
                                  const uint8_t *final_segment, flacgpu_plan **out) {
-    if (!c || !out || (n_streams && (!offs || !samples)) || bytes_per_sample != c->g.B) return FLACGPU_ERR_INVALID_INPUT;
+    if (!c || !out) return FLACGPU_ERR_INVALID_INPUT;
     *out = nullptr;
+    FG_ENCODER_ONLY(c);  // no plan exists on a decode-only context, so nothing that takes one runs on it
+    if ((n_streams && (!offs || !samples)) || bytes_per_sample != c->g.B) return FLACGPU_ERR_INVALID_INPUT;
     HIPCHK(hipSetDevice(c->device));
     const uint32_t bs = c->cfg.block_size;
     const uint64_t fbytes_in = (uint64_t)c->g.C * c->g.B;
@@ -1284,7 +1330,9 @@ int flacgpu_encode_plan_device_ex(flacgpu_ctx *c, const flacgpu_plan *p, const v
                                   uint64_t out_cap, uint32_t *d_frame_bytes, uint64_t *d_frame_offsets,
                                   uint64_t *d_total, flacgpu_md5_state *d_md5_state, uint8_t *d_md5, void *hip_stream,
                                   void *md5_stream) {
-    if (!c || !p || p->ctx != c || !d_pcm || !d_out || !d_frame_bytes || !d_frame_offsets || !d_total)
+    if (!c) return FLACGPU_ERR_INVALID_INPUT;
+    FG_ENCODER_ONLY(c);
+    if (!p || p->ctx != c || !d_pcm || !d_out || !d_frame_bytes || !d_frame_offsets || !d_total)
         return FLACGPU_ERR_INVALID_INPUT;
     // a stream that continues past this segment has no digest yet: its state must be carried
     if (p->d_md5_fin && d_md5 && !d_md5_state) return FLACGPU_ERR_INVALID_INPUT;
@@ -1351,6 +1399,7 @@ int flacgpu_sync_check(flacgpu_ctx *c, void *hip_stream) {
     if (!c) return FLACGPU_ERR_INVALID_INPUT;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(pick_stream(c, hip_stream)));
+    if (c->decode_only) return FLACGPU_OK;  // the error word is the encode kernels': decode statuses are per frame
     return check_device_error(c);
 }
 
@@ -1383,6 +1432,7 @@ int flacgpu_reset_timing(flacgpu_ctx *c) {
 int flacgpu_set_overlap(flacgpu_ctx *c, uint32_t ranges, uint32_t ana_per_cu, uint32_t pack_per_cu,
                         uint32_t min_frames) {
     if (!c || ranges > kOvlMaxChunks || min_frames == 0) return FLACGPU_ERR_INVALID_INPUT;
+    FG_ENCODER_ONLY(c);
     // the overlapped schedule measured slower: diagnostic builds only
     if (!FG_DIAG && ranges > 1) return FLACGPU_ERR_INVALID_CONFIG;
     c->ovl_chunks = ranges;
@@ -1394,6 +1444,7 @@ int flacgpu_set_overlap(flacgpu_ctx *c, uint32_t ranges, uint32_t ana_per_cu, ui
 
 int flacgpu_set_records(flacgpu_ctx *c, int enable) {
     if (!c) return FLACGPU_ERR_INVALID_INPUT;
+    FG_ENCODER_ONLY(c);
     HIPCHK(hipSetDevice(c->device));
     if (enable && !c->d_records) HIPCHK(hipMalloc(&c->d_records, (uint64_t)c->max_frames * sizeof(FrameRec)));
     if (enable) HIPCHK(hipMemset(c->d_records, 0, (uint64_t)c->max_frames * sizeof(FrameRec)));
@@ -1412,6 +1463,7 @@ int flacgpu_get_records(flacgpu_ctx *c, flacgpu_frame_record *out, uint64_t max_
 // Diagnostic build only (-DFG_STAMPS): per-phase shader-clock sums of the encode kernel.
 int flacgpu_debug_stamps(flacgpu_ctx *c, uint64_t *out32, int reset) {
     if (!c || !out32) return FLACGPU_ERR_INVALID_INPUT;
+    FG_ENCODER_ONLY(c);
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpy(out32, c->d_stamps, 32 * 8, hipMemcpyDeviceToHost));
     if (reset) HIPCHK(hipMemset(c->d_stamps, 0, 32 * 8));

@@ -263,6 +263,7 @@ int flacgpu_encode_frames_sharded(flacgpu_ctx *ctx, flacgpu_comm *m, const void 
     if (out_len) *out_len = 0;
     int local = FLACGPU_OK;
     if (!ctx || (!pcm && n_samples) || (m->rank == 0 && !out_len)) local = FLACGPU_ERR_INVALID_INPUT;
+    else if (fg::ctx_decode_only(ctx)) local = FLACGPU_ERR_INVALID_CONFIG;  // agreed on with the other ranks below
     fg::CtxDevice d{};
     if (!local) {
         d = fg::ctx_device(ctx);

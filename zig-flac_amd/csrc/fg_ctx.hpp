@@ -28,6 +28,10 @@ struct flacgpu_ctx {
     int device = 0;
     flacgpu_config cfg{};
     uint32_t max_frames = 0;
+    // flacgpu_open_decoder: cfg holds the stream and block_size = max_block (the encode options zero),
+    // g only C, B, bits and md5_kernel; of everything below only `stream`, the event pool, the timing
+    // and host MD5 state and the decoder scratch exist.  Every encode entry point refuses it.
+    bool decode_only = false;
     fg::Knobs k;    // the environment's knobs when the context was opened
     fg::EncGeom g;  // kernel variants, thread counts, LDS and image sizes: enc_geometry(cfg, k)
 
@@ -217,6 +221,12 @@ struct FG_LOCAL Timed {
 };
 
 FG_LOCAL inline int hip_err(hipError_t e) { return e == hipSuccess ? FLACGPU_OK : (e == hipErrorOutOfMemory ? FLACGPU_ERR_OUT_OF_MEMORY : FLACGPU_ERR_DEVICE); }
+
+// first statement of every entry point that encodes or needs an encode buffer, after its NULL checks
+#define FG_ENCODER_ONLY(c)                                        \
+    do {                                                          \
+        if ((c)->decode_only) return FLACGPU_ERR_INVALID_CONFIG;  \
+    } while (0)
 
 #define HIPCHK(x)                               \
     do {                                        \

@@ -5,14 +5,16 @@
 //                 nature: every Rice code's length depends on its bits); leaves one DecSub per
 //                 subframe, the block size and the provisional status.
 //   k_dec_recon   persistent grid over frames (atomic ticket), one wave64 per subframe: lane s
-//                 decodes segment s (64 samples) into LDS, the wave restores the samples (FIXED:
+//                 decodes segment s (seg_len(block size) = 64, 128 or 256 samples) into LDS, the
+//                 wave restores the samples (FIXED:
 //                 nested running sums by wave scans; LPC: the serial chain on one lane, history
 //                 in registers), then the workgroup undoes the stereo decorrelation, checks the
 //                 CRC-16 and the sample range, and writes / compares the interleaved PCM in
 //                 16-byte units from LDS.
 //
 // Hostile bytes: every bitstream read goes through the bounded BitReader; every LDS / PCM write
-// is indexed by i < block_size <= the context's block size (<= 4096).
+// is indexed by i < block_size <= the context's block size, for which dec_geometry (fg_geom.hpp)
+// sized the planes (<= 16384; <= 8192 with 64-bit planes).
 #include <hip/hip_runtime.h>
 
 #include <mutex>
@@ -20,6 +22,7 @@
 
 #include "fg_common.hpp"
 #include "fg_dec.hpp"
+#include "fg_geom.hpp"
 
 namespace fg {
 
@@ -27,14 +30,22 @@ using namespace dec;
 
 namespace {
 
-constexpr uint32_t kPlane = kMaxBlock + kMaxBlock / 64;  // one subframe's samples, one pad word per 64
-// sample i of a plane: lane s's 64 consecutive samples start one bank further than lane s-1's, so
-// both the per-lane walks (stride 65) and the consecutive accesses are free of bank conflicts
-__device__ __forceinline__ uint32_t phys(uint32_t i) { return i + (i >> 6); }
+// Two instantiations of everything below: BIG = false for a context whose frames have at most 4096
+// samples -- the segment shift 6 and the plane stride kPlane are compile-time constants, the code
+// such a context ran before larger frames existed -- and BIG = true, where the shift is the
+// frame's (seg_shift(bs): 6, 7 or 8) and the stride the context's (DecGeom::plane_words).
+constexpr uint32_t kPlane = 4096 + 4096 / 64;  // one subframe's samples, one pad word per segment
+// sample i of a plane, S = the frame's segment shift: lane s's L = 2^S consecutive samples start
+// one bank further than lane s-1's (stride L + 1 words, odd), so the per-lane walks of the 64 lanes
+// touch 64 different banks, as they did with L = 64.  i + (i >> 6) for every L would start the lanes
+// 65 L / 64 words apart: 130 or 260, even.  (Reasoned from the 64 banks of 4 bytes; not measured.)
+// The largest index, bs - 1 + ((bs - 1) >> S) with bs <= B = 4096 << (S - 6), is below B + 64 <= B + B / 64.
+__device__ __forceinline__ uint32_t phys(uint32_t i, uint32_t S) { return i + (i >> S); }
 
 enum : uint32_t { FLAG_RANGE = 1, FLAG_SUB = 2, FLAG_TRUNC = 4 };
 
 // ---------------------------------------------------------------------------------------------
+template <bool BIG>
 __global__ void __launch_bounds__(64) k_dec_parse(Args a) {
     const uint32_t f = blockIdx.x * 64u + threadIdx.x;
     if (f == 0) {
@@ -44,8 +55,9 @@ __global__ void __launch_bounds__(64) k_dec_parse(Args a) {
     if (f >= a.n_frames) return;
     FrameHdr h;
     uint32_t body = 0;
-    const uint32_t st = parse_frame(a.frames + a.frame_off[f], a.frame_bytes[f], a.rate, a.channels, a.bits, a.block, h,
-                                    a.subs + (size_t)f * a.channels, body);
+    // BIG = false: a.block <= 4096 (launch_dec_parse), so no frame with longer segments is walked
+    const uint32_t st = parse_frame_upto<BIG ? 8u : 6u>(a.frames + a.frame_off[f], a.frame_bytes[f], a.rate, a.channels, a.bits,
+                                                        a.block, h, a.subs + (size_t)f * a.channels, body);
     Result r;
     r.status = st;
     r.block_size = h.block_size;
@@ -75,7 +87,8 @@ __device__ __forceinline__ U wave_incl_scan(U x, uint32_t lane) {
 // The shift makes it a serial chain; the last M samples stay in registers (a ring indexed at
 // compile time), the taps past `order` are zero.  i64 accumulation as in the verifier decoder.
 template <typename T, int M>
-__device__ __forceinline__ void lpc_chain(T *pl, uint32_t bs, uint32_t order, const int32_t (&cf)[M], uint32_t shift) {
+__device__ __forceinline__ void lpc_chain(T *pl, uint32_t bs, uint32_t order, const int32_t (&cf)[M], uint32_t shift,
+                                          uint32_t S) {
     using U = typename std::make_unsigned<T>::type;
     T h[M];
 #pragma unroll
@@ -85,7 +98,7 @@ __device__ __forceinline__ void lpc_chain(T *pl, uint32_t bs, uint32_t order, co
         // before it has used them)
         T r[M];
 #pragma unroll
-        for (int u = 0; u < M; u++) r[u] = base + (uint32_t)u < bs ? pl[phys(base + (uint32_t)u)] : (T)0;
+        for (int u = 0; u < M; u++) r[u] = base + (uint32_t)u < bs ? pl[phys(base + (uint32_t)u, S)] : (T)0;
 #pragma unroll
         for (int u = 0; u < M; u++) {
             const uint32_t i = base + (uint32_t)u;
@@ -97,7 +110,7 @@ __device__ __forceinline__ void lpc_chain(T *pl, uint32_t bs, uint32_t order, co
                     for (int j = 0; j < M; j++)
                         acc += (uint64_t)(int64_t)cf[j] * (uint64_t)(int64_t)h[(u - 1 - j + 2 * M) % M];
                     x = (T)((U)x + (U)((int64_t)acc >> shift));
-                    pl[phys(i)] = x;
+                    pl[phys(i, S)] = x;
                 }
                 h[u] = x;
             }
@@ -105,8 +118,9 @@ __device__ __forceinline__ void lpc_chain(T *pl, uint32_t bs, uint32_t order, co
     }
 }
 
-template <typename T, int M>
-__device__ __noinline__ void lpc_restore(T *pl, const uint8_t *p, uint32_t len, const DecSub &d, uint32_t bs) {
+template <typename T, int M, bool BIG>
+__device__ __noinline__ void lpc_restore(T *pl, const uint8_t *p, uint32_t len, const DecSub &d, uint32_t bs, uint32_t sh) {
+    const uint32_t S = BIG ? sh : 6u;
     int32_t cf[M];
 #pragma unroll
     for (int j = 0; j < M; j++) {
@@ -116,32 +130,35 @@ __device__ __noinline__ void lpc_restore(T *pl, const uint8_t *p, uint32_t len, 
             cf[j] = (int32_t)br_s(b, d.prec);
         }
     }
-    lpc_chain<T, M>(pl, bs, d.order, cf, d.shift);
+    lpc_chain<T, M>(pl, bs, d.order, cf, d.shift, S);
 }
 
-// One wave restores one subframe into its plane (samples after the waste shift).
-template <typename T>
-__device__ void restore_subframe(T *pl, const uint8_t *p, uint32_t len, const DecSub &d, uint32_t bs, uint32_t lane,
-                                 uint32_t *flags) {
+// One wave restores one subframe into its plane (samples after the waste shift).  Lane s owns
+// segment s: samples [L s, L s + L), L = 2^S = seg_len(bs).
+template <typename T, bool BIG>
+__device__ void restore_subframe(T *pl, const uint8_t *p, uint32_t len, const DecSub &d, uint32_t bs, uint32_t sh,
+                                 uint32_t lane, uint32_t *flags) {
     using U = typename std::make_unsigned<T>::type;
     const uint32_t sbps = d.sbps, order = d.order;
+    const uint32_t S = BIG ? sh : 6u, L = 1u << S;
+    if (!BIG) __builtin_assume(bs <= 4096u);  // decode_segment's seg_len(bs) folds to 64
     if (d.type == SUB_CONSTANT) {
         BitReader b = br_make(p, len, d.warm_pos);
         const T v = (T)br_s(b, sbps);
-        for (uint32_t i = lane; i < bs; i += 64u) pl[phys(i)] = v;
+        for (uint32_t i = lane; i < bs; i += 64u) pl[phys(i, S)] = v;
     } else if (d.type == SUB_VERBATIM) {
-        for (uint32_t j = 0; j < 64u; j++) {
-            const uint32_t i = 64u * lane + j;
+        for (uint32_t j = 0; j < L; j++) {
+            const uint32_t i = L * lane + j;
             if (i < bs) {
                 BitReader b = br_make(p, len, d.warm_pos + i * sbps);
-                pl[phys(i)] = (T)br_s(b, sbps);
+                pl[phys(i, S)] = (T)br_s(b, sbps);
             }
         }
     } else {
         // residuals: lane s decodes segment s, then the continuity check against segment s + 1
         uint32_t err = 0;
         const uint32_t end = decode_segment(p, len, d, bs, lane, err, [&](uint32_t i, int64_t v) {
-            if (i < bs) pl[phys(i)] = (T)v;
+            if (i < bs) pl[phys(i, S)] = (T)v;
         });
         const uint32_t next = lane < 63u ? d.seg_pos[lane + 1u] : d.end_pos;
         if (end != next) atomicOr(flags, FLAG_SUB);
@@ -149,13 +166,13 @@ __device__ void restore_subframe(T *pl, const uint8_t *p, uint32_t len, const De
         if (d.type == SUB_LPC) {
             if (lane < order) {
                 BitReader b = br_make(p, len, d.warm_pos + lane * sbps);
-                pl[phys(lane)] = (T)br_s(b, sbps);
+                pl[phys(lane, S)] = (T)br_s(b, sbps);
             }
             __threadfence_block();
             if (lane == 0) {
-                if (order <= 8u) lpc_restore<T, 8>(pl, p, len, d, bs);
-                else if (order <= 12u) lpc_restore<T, 12>(pl, p, len, d, bs);
-                else lpc_restore<T, 32>(pl, p, len, d, bs);
+                if (order <= 8u) lpc_restore<T, 8, BIG>(pl, p, len, d, bs, S);
+                else if (order <= 12u) lpc_restore<T, 12, BIG>(pl, p, len, d, bs, S);
+                else lpc_restore<T, 32, BIG>(pl, p, len, d, bs, S);
             }
         } else if (order > 0) {
             // FIXED order k: k nested running sums (RFC 9639 9.2.5: the predictors are the k-th
@@ -176,37 +193,37 @@ __device__ void restore_subframe(T *pl, const uint8_t *p, uint32_t len, const De
             for (uint32_t lvl = order; lvl >= 1u; lvl--) {
                 const U ini = lvl == 1u ? init[0] : lvl == 2u ? init[1] : lvl == 3u ? init[2] : init[3];
                 U tot = 0;
-                for (uint32_t j = 0; j < 64u; j++) {
-                    const uint32_t i = 64u * lane + j;
-                    if (i >= order && i < bs) tot += (U)pl[phys(i)];
+                for (uint32_t j = 0; j < L; j++) {
+                    const uint32_t i = L * lane + j;
+                    if (i >= order && i < bs) tot += (U)pl[phys(i, S)];
                 }
                 U run = wave_incl_scan<U>(tot, lane) - tot + ini;
-                for (uint32_t j = 0; j < 64u; j++) {
-                    const uint32_t i = 64u * lane + j;
+                for (uint32_t j = 0; j < L; j++) {
+                    const uint32_t i = L * lane + j;
                     if (i >= order && i < bs) {
-                        run += (U)pl[phys(i)];
-                        pl[phys(i)] = (T)run;
+                        run += (U)pl[phys(i, S)];
+                        pl[phys(i, S)] = (T)run;
                     }
                 }
             }
             if (lane == 0)
                 for (uint32_t m = 0; m < 4u; m++)
-                    if (m < order) pl[phys(order - 1u - m)] = (T)w[m];
+                    if (m < order) pl[phys(order - 1u - m, S)] = (T)w[m];
         }
     }
     __threadfence_block();
     if (d.waste)  // 9.2.2: the wasted bits come back as zeros
-        for (uint32_t i = lane; i < bs; i += 64u) pl[phys(i)] = (T)((U)pl[phys(i)] << d.waste);
+        for (uint32_t i = lane; i < bs; i += 64u) pl[phys(i, S)] = (T)((U)pl[phys(i, S)] << d.waste);
 }
 
 // The interleaved little-endian PCM of the frame region [base, base + nb), in 16-byte units of the
 // absolute address: written (CMP = false) or compared with what is there (CMP = true: the first
 // differing interleaved sample goes to *first_bad by atomicMin).  Channels c0 .. c0 + wc - 1 are in
-// `planes`; a unit that is not whole (the region's edges, or channels of another round) goes byte
-// by byte.
+// `planes` (`plane` elements apart, the frame's segment shift S); a unit that is not whole (the
+// region's edges, or channels of another round) goes byte by byte.
 template <typename T, bool CMP>
-__device__ void emit(const T *planes, uint32_t C, uint32_t c0, uint32_t wc, uint32_t bps, uint32_t nb, uint8_t *base,
-                     uint32_t tid, uint32_t nt, uint32_t *first_bad) {
+__device__ void emit(const T *planes, uint32_t plane, uint32_t S, uint32_t C, uint32_t c0, uint32_t wc, uint32_t bps,
+                     uint32_t nb, uint8_t *base, uint32_t tid, uint32_t nt, uint32_t *first_bad) {
     const uintptr_t A = (uintptr_t)base, U0 = A & ~(uintptr_t)15;
     const uint32_t units = (uint32_t)((A + nb - U0 + 15u) >> 4);
     for (uint32_t u = tid; u < units; u += nt) {
@@ -218,7 +235,7 @@ __device__ void emit(const T *planes, uint32_t C, uint32_t c0, uint32_t wc, uint
         uint32_t mask = 0;
         for (; (int32_t)(e * bps) < hi; e++) {
             if (c >= c0 && c < c0 + wc) {
-                const uint64_t v = (uint64_t)(int64_t)planes[(c - c0) * kPlane + phys(i)];
+                const uint64_t v = (uint64_t)(int64_t)planes[(c - c0) * plane + phys(i, S)];
                 for (uint32_t o = 0; o < bps; o++) {
                     const int32_t b = (int32_t)(e * bps + o);
                     if (b >= lo && b < hi) {
@@ -259,11 +276,14 @@ __device__ void emit(const T *planes, uint32_t C, uint32_t c0, uint32_t wc, uint
 }
 
 // W waves = W subframes at a time; a frame of more channels than W takes several rounds.
-template <typename T>
-__global__ void __launch_bounds__(512) k_dec_recon(Args a, uint32_t W) {
+// plane_words: DecGeom's (BIG = false: kPlane, a constant here).
+template <typename T, bool BIG>
+__global__ void __launch_bounds__(512) k_dec_recon(Args a, uint32_t W, uint32_t plane_words) {
     extern __shared__ __align__(16) uint8_t smem[];
     T *planes = (T *)smem;
     __shared__ uint32_t s_f, s_flags, s_crc, s_bad;
+    static_assert(4 * sizeof(uint32_t) == kDecStaticLds, "dec_geometry's LDS budget leaves room for these");
+    const uint32_t plane = BIG ? plane_words : kPlane;
     const uint32_t tid = threadIdx.x, nt = blockDim.x, lane = tid & 63u, wv = tid >> 6;
     const uint32_t C = a.channels, bps = a.bps;
     for (;;) {
@@ -281,6 +301,7 @@ __global__ void __launch_bounds__(512) k_dec_recon(Args a, uint32_t W) {
         uint32_t st = R->status, first_bad = 0;
         const uint8_t *p = a.frames + a.frame_off[f];
         const uint32_t len = a.frame_bytes[f], bs = R->block_size, chc = R->channel_assign, body = a.body[f];
+        const uint32_t S = BIG ? seg_shift(bs) : 6u;  // st == 0: bs <= a.block, which the planes were sized for
         if (st == 0) {
             // CRC-16 over the body: thread t folds the t-th of nt equal pieces (the first ones
             // start before the frame: leading zeros leave an init-0 CRC at 0) byte by byte, then
@@ -324,19 +345,20 @@ __global__ void __launch_bounds__(512) k_dec_recon(Args a, uint32_t W) {
                     __syncthreads();
                     if (wv < wc) {
                         const uint32_t c = c0 + wv;
-                        restore_subframe<T>(planes + wv * kPlane, p, len, a.subs[(size_t)f * C + c], bs, lane, &s_flags);
+                        restore_subframe<T, BIG>(planes + wv * plane, p, len, a.subs[(size_t)f * C + c], bs, S, lane, &s_flags);
                     }
                     __syncthreads();
                     if (C == 2u && chc >= 8u) {  // 9.1.3: left/side, side/right, mid/side
                         using U = typename std::make_unsigned<T>::type;
                         for (uint32_t i = tid; i < bs; i += nt) {
-                            const U x = (U)planes[phys(i)], s = (U)planes[kPlane + phys(i)];
-                            if (chc == 8u) planes[kPlane + phys(i)] = (T)(x - s);
-                            else if (chc == 9u) planes[phys(i)] = (T)(x + s);
+                            const uint32_t q = phys(i, S);
+                            const U x = (U)planes[q], s = (U)planes[plane + q];
+                            if (chc == 8u) planes[plane + q] = (T)(x - s);
+                            else if (chc == 9u) planes[q] = (T)(x + s);
                             else {
                                 const U mid = x * 2u + (s & 1u);
-                                planes[phys(i)] = (T)(mid + s) >> 1;
-                                planes[kPlane + phys(i)] = (T)(mid - s) >> 1;
+                                planes[q] = (T)(mid + s) >> 1;
+                                planes[plane + q] = (T)(mid - s) >> 1;
                             }
                         }
                         __syncthreads();
@@ -345,15 +367,16 @@ __global__ void __launch_bounds__(512) k_dec_recon(Args a, uint32_t W) {
                         uint32_t bad = 0;
                         for (uint32_t e = tid; e < wc * bs; e += nt) {
                             const uint32_t w = e / bs, i = e - w * bs;
-                            if (!sample_in_range((int64_t)planes[w * kPlane + phys(i)], a.bits)) bad = 1;
+                            if (!sample_in_range((int64_t)planes[w * plane + phys(i, S)], a.bits)) bad = 1;
                         }
                         if (bad) atomicOr(&s_flags, FLAG_RANGE);
                         __syncthreads();
                     }
                     if (pass + 1u == npass && s_flags == 0) {
-                        if (a.out) emit<T, false>(planes, C, c0, wc, bps, nb, a.out + off, tid, nt, nullptr);
+                        if (a.out) emit<T, false>(planes, plane, S, C, c0, wc, bps, nb, a.out + off, tid, nt, nullptr);
                         if (a.expect)
-                            emit<T, true>(planes, C, c0, wc, bps, nb, const_cast<uint8_t *>(a.expect) + off, tid, nt, &s_bad);
+                            emit<T, true>(planes, plane, S, C, c0, wc, bps, nb, const_cast<uint8_t *>(a.expect) + off, tid, nt,
+                                          &s_bad);
                     }
                 }
                 __syncthreads();
@@ -376,28 +399,36 @@ __global__ void __launch_bounds__(512) k_dec_recon(Args a, uint32_t W) {
 }
 
 template <typename KernelT>
-hipError_t launch_recon(KernelT k, const Args &a, uint32_t W, uint32_t lds, hipStream_t st) {
+hipError_t launch_recon(KernelT k, const Args &a, const DecGeom &g, hipStream_t st) {
     struct Occ {
         const void *fn;
-        uint32_t W;
+        uint32_t W, lds;
         int device, grid;
     };
-    static Occ cache[32];
+    static Occ cache[64];
     static int n_cache = 0;
     static std::mutex mu;
+    const uint32_t W = g.W, lds = g.lds;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     int grid = 0;
+    uint32_t asked = 0;  // the most dynamic LDS this kernel has been allowed on this device
     {
         std::lock_guard<std::mutex> lock(mu);
         for (int i = 0; i < n_cache; i++)
-            if (cache[i].fn == (const void *)k && cache[i].W == W && cache[i].device == dev) grid = cache[i].grid;
+            if (cache[i].fn == (const void *)k && cache[i].device == dev) {
+                if (cache[i].W == W && cache[i].lds == lds) grid = cache[i].grid;
+                if (cache[i].lds > asked) asked = cache[i].lds;
+            }
     }
     if (!grid) {
-        // (the kernel's few static words count against the 160 KiB too: ask for what the planes need)
-        e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+        // (the kernel's few static words count against the 160 KiB too: ask for what the planes need;
+        // never for less than an earlier geometry of the same kernel was given)
+        if (lds > asked) {
+            e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
         int cus = 0, nb = 0;
         e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
         if (e != hipSuccess) return e;
@@ -405,10 +436,10 @@ hipError_t launch_recon(KernelT k, const Args &a, uint32_t W, uint32_t lds, hipS
         if (e != hipSuccess) return e;
         grid = (nb > 0 ? nb : 1) * (cus > 0 ? cus : 256);
         std::lock_guard<std::mutex> lock(mu);
-        if (n_cache < 32) cache[n_cache++] = {(const void *)k, W, dev, grid};
+        if (n_cache < 64) cache[n_cache++] = {(const void *)k, W, lds, dev, grid};
     }
-    const uint32_t g = a.n_frames < (uint32_t)grid ? a.n_frames : (uint32_t)grid;
-    hipLaunchKernelGGL(k, dim3(g), dim3(64u * W), lds, st, a, W);
+    const uint32_t ng = a.n_frames < (uint32_t)grid ? a.n_frames : (uint32_t)grid;
+    hipLaunchKernelGGL(k, dim3(ng), dim3(64u * W), lds, st, a, W, g.plane_words);
     return hipGetLastError();
 }
 
@@ -416,21 +447,26 @@ hipError_t launch_recon(KernelT k, const Args &a, uint32_t W, uint32_t lds, hipS
 
 hipError_t launch_dec_parse(const Args &a, hipStream_t st) {
     if (a.n_frames == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_dec_parse, dim3((a.n_frames + 63u) / 64u), dim3(64), 0, st, a);
+    if (a.block <= 4096u) hipLaunchKernelGGL(k_dec_parse<false>, dim3((a.n_frames + 63u) / 64u), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_dec_parse<true>, dim3((a.n_frames + 63u) / 64u), dim3(64), 0, st, a);
     return hipGetLastError();
 }
 
-// 8/16/24-bit: i32 planes, every channel's wave at once (8 x 16.25 KiB = 130 KiB of LDS at most).
-// 32-bit: i64 planes (the 33-bit side channel, and the 64-bit sums of the verifier decoder), at
-// most four waves at a time (4 x 32.5 KiB).
+// Waves, plane size and LDS are dec_geometry's (fg_geom.hpp) for the context's channels, depth and
+// block size: i32 planes at 8/16/24 bits, i64 planes at 32 (the 33-bit side channel, and the 64-bit
+// sums of the verifier decoder).  A context of blocks up to 4096 runs the BIG = false kernels.
 hipError_t launch_dec_recon(const Args &a, hipStream_t st) {
     if (a.n_frames == 0) return hipSuccess;
-    if (a.bits == 32u) {
-        const uint32_t W = a.channels < 4u ? a.channels : 4u;
-        return launch_recon(k_dec_recon<int64_t>, a, W, W * kPlane * (uint32_t)sizeof(int64_t), st);
+    const DecGeom g = dec_geometry(a.channels, a.bits, a.block);
+    if (!g.ok) return hipErrorInvalidValue;  // no context is opened with such a block size
+    if (a.block <= 4096u) {
+        static_assert(kPlane == 4096 + 4096 / 64, "dec_geometry's plane of a block of at most 4096");
+        if (g.plane_words != kPlane) return hipErrorInvalidValue;
+        return a.bits == 32u ? launch_recon(k_dec_recon<int64_t, false>, a, g, st)
+                             : launch_recon(k_dec_recon<int32_t, false>, a, g, st);
     }
-    const uint32_t W = a.channels;
-    return launch_recon(k_dec_recon<int32_t>, a, W, W * kPlane * (uint32_t)sizeof(int32_t), st);
+    return a.bits == 32u ? launch_recon(k_dec_recon<int64_t, true>, a, g, st)
+                         : launch_recon(k_dec_recon<int32_t, true>, a, g, st);
 }
 
 // verify: the expected PCM offset, frame number and sample count of every frame, from a plan's frame table

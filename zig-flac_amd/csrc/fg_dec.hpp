@@ -9,9 +9,10 @@
 //
 // Two stages.  The WALK (walk_subframe) goes through a subframe once, sequentially, doing no
 // arithmetic on the residual values: it checks every rule of the layout and leaves a DecSub
-// descriptor that says where each 64-sample segment's residuals start.  The SEGMENT DECODE
-// (decode_segment) then turns one segment's codes into residuals, independently of every other
-// segment -- on the device, one lane per segment.
+// descriptor that says where each segment's residuals start: a frame is cut into kSegs = 64
+// segments of seg_len(block size) = 64, 128 or 256 samples.  The SEGMENT DECODE (decode_segment)
+// then turns one segment's codes into residuals, independently of every other segment -- on the
+// device, one lane per segment.
 #pragma once
 #include <stdint.h>
 
@@ -27,8 +28,14 @@ enum : uint32_t {
 };
 
 constexpr uint32_t kMaxFrameBytes = 1u << 28;  // bit positions stay below 2^31; longer "frames" are cut here
-constexpr uint32_t kSegs = 64;                 // 64-sample segments of a block of at most 4096
-constexpr uint32_t kMaxBlock = 4096;
+constexpr uint32_t kSegs = 64;                 // segments of a frame, whatever its block size
+constexpr uint32_t kMaxBlock = 16384;          // RFC 9639's streamable subset; 64-bit planes (32-bit samples): 8192
+
+// Samples of one segment of a frame of bs samples: 64 up to 4096 samples (the only length there
+// was when no frame was larger, so those frames' descriptors are what they always were), 128 up to
+// 8192, 256 up to 16384 = kMaxBlock.  A function of the frame alone, not of the context.
+FG_HD uint32_t seg_shift(uint32_t bs) { return bs <= 4096u ? 6u : (bs <= 8192u ? 7u : 8u); }
+FG_HD uint32_t seg_len(uint32_t bs) { return 1u << seg_shift(bs); }
 
 // ---- bounded bit reader over one frame's bytes [p, p + nbits / 8) ----------------------------
 // A read past the end returns zeros for the missing bits, leaves pos at the end and sets the
@@ -238,15 +245,18 @@ struct DecSub {
     uint32_t warm_pos;   // bit position of the warm-up samples (CONSTANT: the value, VERBATIM: sample 0)
     uint32_t coef_pos;   // LPC: bit position of the first coefficient
     uint32_t end_pos;    // bit position after the subframe's last bit
-    uint32_t seg_pos[kSegs];  // where segment s's first residual (sample max(64 s, order)) starts
+    uint32_t seg_pos[kSegs];  // where segment s's first residual (sample max(seg_len s, order)) starts
     uint8_t seg_par[kSegs];
     uint8_t type, order, waste, sbps;  // sbps: bits of a sample of this subframe after the waste shift
     uint8_t method, porder, prec, shift;
 };
 static_assert(sizeof(DecSub) == 340, "DecSub layout");
 
-// 9.2.7: the coded residual, walked without decoding a value
-FG_HD uint32_t walk_residual(BitReader &b, uint32_t bs, uint32_t order, DecSub &d) {
+// 9.2.7: the coded residual, walked without decoding a value; SH = seg_shift(bs).  This loop bounds
+// the whole decode (one lane per frame), and a segment length held in a register instead of the
+// constant 64 measured 3 to 5 % slower on frames of 4096 samples: hence one copy per length.
+template <uint32_t SH>
+FG_HD uint32_t walk_residual_at(BitReader &b, uint32_t bs, uint32_t order, DecSub &d) {
     const uint32_t method = br_u(b, 2);
     if (method > 1u) return ST_SUBFRAME;
     const uint32_t pbits = method ? 5u : 4u, esc = method ? 31u : 15u;
@@ -255,6 +265,7 @@ FG_HD uint32_t walk_residual(BitReader &b, uint32_t bs, uint32_t order, DecSub &
     if ((bs >> porder) < order || (bs % nparts) != 0) return ST_SUBFRAME;
     d.method = (uint8_t)method;
     d.porder = (uint8_t)porder;
+    constexpr uint32_t L = 1u << SH;
     uint32_t i = order, seg = 0;
     for (uint32_t pt = 0; pt < nparts; pt++) {
         const uint32_t cnt = (bs >> porder) - (pt == 0 ? order : 0u);
@@ -263,7 +274,7 @@ FG_HD uint32_t walk_residual(BitReader &b, uint32_t bs, uint32_t order, DecSub &
         uint32_t w = 0;
         if (k == esc) w = br_u(b, 5);
         for (uint32_t j = 0; j < cnt; j++, i++) {
-            while (seg < kSegs && 64u * seg <= i) {
+            while (seg < kSegs && L * seg <= i) {
                 d.seg_pos[seg] = j == 0 ? field : b.pos;
                 d.seg_par[seg] = (uint8_t)((k == esc ? (PAR_ESC | w) : k) | (j == 0 ? PAR_FIELD : 0u));
                 seg++;
@@ -284,9 +295,23 @@ FG_HD uint32_t walk_residual(BitReader &b, uint32_t bs, uint32_t order, DecSub &
     return ST_OK;
 }
 
+// MAXSH: the largest segment shift the caller's frames can have.  A caller whose frames have at
+// most 4096 samples (parse_header's max_block) says 6 and compiles the instructions such frames
+// always ran, and nothing else; 8 takes every frame up to kMaxBlock.
+template <uint32_t MAXSH>
+FG_HD uint32_t walk_residual_upto(BitReader &b, uint32_t bs, uint32_t order, DecSub &d) {
+    if (MAXSH == 6u || bs <= 4096u) return walk_residual_at<6>(b, bs, order, d);
+    if (MAXSH == 7u || bs <= 8192u) return walk_residual_at<7>(b, bs, order, d);
+    return walk_residual_at<8>(b, bs, order, d);
+}
+FG_HD uint32_t walk_residual(BitReader &b, uint32_t bs, uint32_t order, DecSub &d) {
+    return walk_residual_upto<8>(b, bs, order, d);
+}
+
 // 9.2: one subframe of bps bits per sample; fills d.  The rules and their order are
 // decode_subframe's of the verifier decoder.
-FG_HD uint32_t walk_subframe(BitReader &b, uint32_t bs, uint32_t bps, DecSub &d) {
+template <uint32_t MAXSH>
+FG_HD uint32_t walk_subframe_upto(BitReader &b, uint32_t bs, uint32_t bps, DecSub &d) {
     d.warm_pos = d.coef_pos = d.end_pos = 0;
     d.type = d.order = d.waste = d.sbps = d.method = d.porder = d.prec = d.shift = 0;
     if (br_u(b, 1) != 0) return ST_SUBFRAME;  // 9.2.1: padding bit
@@ -316,7 +341,7 @@ FG_HD uint32_t walk_subframe(BitReader &b, uint32_t bs, uint32_t bps, DecSub &d)
         if (order > bs) return ST_SUBFRAME;
         d.warm_pos = b.pos;
         br_skip(b, order * sbps);
-        const uint32_t rc = walk_residual(b, bs, order, d);
+        const uint32_t rc = walk_residual_upto<MAXSH>(b, bs, order, d);
         if (rc) return rc;
     } else if (t >= 32) {  // 9.2.6 LPC
         const uint32_t order = (t & 31u) + 1u;
@@ -333,7 +358,7 @@ FG_HD uint32_t walk_subframe(BitReader &b, uint32_t bs, uint32_t bps, DecSub &d)
         d.shift = (uint8_t)shift;
         d.coef_pos = b.pos;
         br_skip(b, order * prec);
-        const uint32_t rc = walk_residual(b, bs, order, d);
+        const uint32_t rc = walk_residual_upto<MAXSH>(b, bs, order, d);
         if (rc) return rc;
     } else {
         return ST_SUBFRAME;  // reserved types
@@ -341,17 +366,22 @@ FG_HD uint32_t walk_subframe(BitReader &b, uint32_t bs, uint32_t bps, DecSub &d)
     d.end_pos = b.pos;
     return b.err ? ST_TRUNCATED : ST_OK;
 }
+FG_HD uint32_t walk_subframe(BitReader &b, uint32_t bs, uint32_t bps, DecSub &d) {
+    return walk_subframe_upto<8>(b, bs, bps, d);
+}
 
 // The whole provisional check of one frame: header, every subframe's walk, the padding and the
 // presence of the CRC-16 (its value is checked by the caller over body_bytes).  subs: h.nch entries.
-FG_HD uint32_t parse_frame(const uint8_t *p, uint32_t len, uint32_t stream_rate, uint32_t channels, uint32_t bits,
-                           uint32_t max_block, FrameHdr &h, DecSub *subs, uint32_t &body_bytes) {
+// MAXSH = 6 needs max_block <= 4096: a larger frame is RANGE before any subframe is walked.
+template <uint32_t MAXSH>
+FG_HD uint32_t parse_frame_upto(const uint8_t *p, uint32_t len, uint32_t stream_rate, uint32_t channels, uint32_t bits,
+                                uint32_t max_block, FrameHdr &h, DecSub *subs, uint32_t &body_bytes) {
     BitReader b = br_make(p, len);
     body_bytes = 0;
     uint32_t st = parse_header(b, bits, stream_rate, channels, bits, max_block, h);
     if (st) return st;
     for (uint32_t c = 0; c < h.nch; c++) {
-        st = walk_subframe(b, h.block_size, sub_bps(h.channel_assign, c, h.bits), subs[c]);
+        st = walk_subframe_upto<MAXSH>(b, h.block_size, sub_bps(h.channel_assign, c, h.bits), subs[c]);
         if (st) return st;
     }
     while (b.pos & 7u)  // 9.3: zero padding to a byte boundary
@@ -362,17 +392,22 @@ FG_HD uint32_t parse_frame(const uint8_t *p, uint32_t len, uint32_t stream_rate,
     body_bytes = body;
     return ST_OK;
 }
+FG_HD uint32_t parse_frame(const uint8_t *p, uint32_t len, uint32_t stream_rate, uint32_t channels, uint32_t bits,
+                           uint32_t max_block, FrameHdr &h, DecSub *subs, uint32_t &body_bytes) {
+    return parse_frame_upto<8>(p, len, stream_rate, channels, bits, max_block, h, subs, body_bytes);
+}
 
 // ---- segment decode -------------------------------------------------------------------------
-// Residuals of samples max(64 s, order) .. min(64 s + 64, bs) - 1 of a FIXED / LPC subframe, each
+// Residuals of samples max(L s, order) .. min(L s + L, bs) - 1, L = seg_len(bs), of a FIXED / LPC subframe, each
 // handed to put(i, value); crosses partition boundaries (a partition may be shorter than a
 // segment).  Returns the bit position after the segment's last code.
 template <typename Put>
 FG_HD uint32_t decode_segment(const uint8_t *p, uint32_t len, const DecSub &d, uint32_t bs, uint32_t s, uint32_t &err,
                               Put &&put) {
     BitReader b = br_make(p, len, d.seg_pos[s]);
-    uint32_t i = 64u * s < d.order ? d.order : 64u * s;
-    const uint32_t end = 64u * s + 64u < bs ? 64u * s + 64u : bs;
+    const uint32_t L = seg_len(bs);
+    uint32_t i = L * s < d.order ? d.order : L * s;
+    const uint32_t end = L * s + L < bs ? L * s + L : bs;
     const uint32_t psize = bs >> d.porder;
     const uint32_t pbits = d.method ? 5u : 4u, escv = d.method ? 31u : 15u;
     uint32_t par = d.seg_par[s];

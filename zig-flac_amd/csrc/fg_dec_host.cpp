@@ -549,7 +549,8 @@ int decode_chunk(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff
                  F overlap) {
     DecScratch *d = c->dec;
     hipStream_t st = c->stream;
-    const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u), need = (uint64_t)n * c->cfg.block_size * per;
+    // (a decode-only context's block_size is its max_block, up to 16384: 64-bit products)
+    const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u), need = (uint64_t)n * (uint64_t)c->cfg.block_size * per;
     HIPCHK(grow(d->d_pcm, d->pcm_cap, need));  // the chunk before this one was waited for
     HIPCHK(hipMemsetAsync(d->d_pcm, 0, need, st));
     const int rc = dec_core(c, d_frames, d_foff, d_fbytes, n, nullptr, d->d_pcm, need, nullptr, false,
@@ -594,7 +595,9 @@ int flacgpu_decode_frames_device(flacgpu_ctx *c, const uint8_t *d_frames, const 
 int flacgpu_verify_plan_device(flacgpu_ctx *c, const flacgpu_plan *p, const void *d_pcm, const uint8_t *d_out,
                                const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
                                flacgpu_decode_result *d_results, uint32_t *d_bad_count, void *hip_stream) {
-    if (!c || !p || p->ctx != c || !d_pcm || !d_out || !d_frame_offsets || !d_frame_bytes || !d_results || !d_bad_count ||
+    if (!c) return FLACGPU_ERR_INVALID_INPUT;
+    FG_ENCODER_ONLY(c);  // a plan is an encoder context's
+    if (!p || p->ctx != c || !d_pcm || !d_out || !d_frame_offsets || !d_frame_bytes || !d_results || !d_bad_count ||
         p->n_frames > c->max_frames)
         return FLACGPU_ERR_INVALID_INPUT;
     HIPCHK(hipSetDevice(c->device));
@@ -884,7 +887,7 @@ int fg::decode_files_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *
     uint64_t pcm_total = 0, longest = 0;
     for (uint32_t i = 0; i < n; i++) {
         const bool ok = ires[i].status == idx::IDX_OK && ires[i].n_frames <= tb.caps[i];
-        const uint64_t most = ok ? ires[i].n_frames * c->cfg.block_size * per : 0u;
+        const uint64_t most = ok ? ires[i].n_frames * (uint64_t)c->cfg.block_size * per : 0u;
         pcm_offs[i] = pcm_total;
         pcm_caps[i] = std::min<uint64_t>(most, pcm_cap[i]);
         pcm_total += (pcm_caps[i] + 63u) & ~(uint64_t)63u;

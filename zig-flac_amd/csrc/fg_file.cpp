@@ -278,6 +278,7 @@ int flacgpu_encode_file(flacgpu_ctx *ctx, const void *pcm, uint32_t bytes_per_sa
                         uint8_t *out, size_t out_cap, size_t *out_len) {
     if (!ctx || !out || !out_len || (!pcm && n_samples)) return FLACGPU_ERR_INVALID_INPUT;
     *out_len = 0;
+    if (fg::ctx_decode_only(ctx)) return FLACGPU_ERR_INVALID_CONFIG;
     flacgpu_config cfg;
     int rc = flacgpu_get_config(ctx, &cfg);
     if (rc) return rc;
@@ -338,6 +339,7 @@ int flacgpu_encode_file(flacgpu_ctx *ctx, const void *pcm, uint32_t bytes_per_sa
 int flacgpu_encode_files(flacgpu_ctx *ctx, uint32_t n_files, const void *const *pcm, uint32_t bytes_per_sample,
                          const uint64_t *n_samples, uint8_t *const *out, const size_t *out_cap, size_t *out_len) {
     if (!ctx || (n_files && (!pcm || !n_samples || !out || !out_cap || !out_len))) return FLACGPU_ERR_INVALID_INPUT;
+    if (fg::ctx_decode_only(ctx)) return FLACGPU_ERR_INVALID_CONFIG;
     flacgpu_config cfg;
     int rc = flacgpu_get_config(ctx, &cfg);
     if (rc) return rc;

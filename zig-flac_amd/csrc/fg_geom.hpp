@@ -2,7 +2,8 @@
 // function of the configuration and the output-invariant knobs.  flacgpu_open (fg_api.cpp) calls
 // enc_geometry once and keeps the result; the stand-alone host program of the tests
 // (tests/cpp/geom_host_main.cpp, tests/test_geom_host.py) pins it row by row against
-// tests/golden/geometry.json.  No HIP, no environment, no state: compiles under hipcc and plain g++
+// tests/golden/geometry.json.  dec_geometry is the same for the decoder's reconstruct kernel
+// (launch_dec_recon calls it; tests/cpp/decgeom_host_main.cpp, tests/golden/dec_geometry.json).  No HIP, no environment, no state: compiles under hipcc and plain g++
 // (a host-only includer defines __host__ / __device__ away before including, for fg_layout.hpp).
 #pragma once
 #include <stdint.h>
@@ -235,6 +236,47 @@ inline int enc_geometry(const flacgpu_config &cfg, const Knobs &k, EncGeom &g) {
     if (g.lds > kLdsLimit || g.lds_tail > kLdsLimit || g.lds_pack > kLdsLimit || g.lds_pack4 > kLdsLimit)
         return FLACGPU_ERR_INVALID_CONFIG;
     return FLACGPU_OK;
+}
+
+// ---- the decoder's reconstruct kernel (fg_dec.hip: k_dec_recon) ------------------------------
+// One workgroup of W waves restores W subframes at a time, each into a plane of LDS: `elem`-byte
+// elements (4; 8 for 32-bit samples: the 33-bit side channel and the verifier decoder's 64-bit
+// sums), plane_words of them: the block rounded up to B = 4096, 8192 or 16384, and B / 64 pad
+// elements, one per segment of a B-sample frame (fg_dec.hip phys()).
+// A frame of more channels than W takes ceil(C / W) rounds in each of two passes.
+struct DecGeom {
+    bool ok = false;
+    uint32_t elem = 0, plane_words = 0, W = 0, lds = 0, passes = 0;
+};
+
+constexpr uint32_t kDecStaticLds = 16;  // k_dec_recon's own __shared__ words (static_assert there)
+
+// channels 1..8, bits 8 / 16 / 24 / 32, block 1..FLACGPU_DECODER_MAX_BLOCK: the context's largest frame.
+inline DecGeom dec_geometry(uint32_t channels, uint32_t bits, uint32_t block) {
+    DecGeom g;
+    if (channels < 1 || channels > 8 || (bits != 8 && bits != 16 && bits != 24 && bits != 32)) return g;
+    if (block < 1 || block > FLACGPU_DECODER_MAX_BLOCK) return g;
+    g.elem = bits == 32 ? 8u : 4u;
+    const uint32_t B = block <= 4096u ? 4096u : (block <= 8192u ? 8192u : 16384u);
+    g.plane_words = B + B / 64u;
+    const uint32_t plane_bytes = g.plane_words * g.elem;
+    if (B == 4096u) {
+        // every channel's wave at once (8 x 16.25 KiB = 130 KiB at most); 64-bit planes: at most
+        // four waves (4 x 32.5 KiB) -- what every context launched with before larger blocks existed
+        g.W = bits == 32 ? (channels < 4u ? channels : 4u) : channels;
+    } else {
+        // one workgroup per CU: as many planes as the CU's LDS holds beside the kernel's own words
+        const uint32_t fit = (kLdsLimit - kDecStaticLds) / plane_bytes;
+        g.W = channels < fit ? channels : fit;
+    }
+    // the stereo decorrelation reads both planes of a frame in one round
+    if (g.W < (channels < 2u ? channels : 2u)) return g;
+    // (that rule alone would admit one 64-bit plane of 16384: the stated limit covers mono too)
+    if (bits == 32 && block > FLACGPU_DECODER_MAX_BLOCK_32) return g;
+    g.lds = g.W * plane_bytes;
+    g.passes = channels > g.W ? 2u : 1u;
+    g.ok = true;
+    return g;
 }
 
 }  // namespace fg

@@ -46,13 +46,20 @@ class FlacBank:
         self.sample_rates = [int(si.sample_rate) for si in infos]
         self.compressed_bytes = sum(len(b) for b in bare)
         stated = [int(si.interchannel_samples) for si in infos]
+        # the context decodes the largest block any file states; a larger one than the decoder takes
+        # would only show as BAD_FRAME at crop time
+        most = flacgpu.decoder_max_block(self.bits)
+        for i, si in enumerate(infos):
+            if int(si.max_block_size) > most:
+                raise ValueError(f"FlacBank: file {i} states blocks of {int(si.max_block_size)} samples, the decoder takes "
+                                 f"at most {most} at {self.bits} bits")
 
         # ---- everything below needs the device
         import numpy as np
         import torch
 
         self.device = torch.device("cuda", device)
-        block = min(max([int(si.max_block_size) for si in infos] + [16]), 4096)
+        block = max([int(si.max_block_size) for si in infos] + [16])
         self._dec = flacgpu.Decoder(self.channels, self.bits, self.sample_rates[0], device=device, max_frames=max_frames,
                                     block_size=block)
         n = len(files)

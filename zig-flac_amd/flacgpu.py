@@ -291,6 +291,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
     sig = {
         "flacgpu_config_default": (Config, [U32, U32, U32]),
         "flacgpu_open": (I32, [I32, ctypes.POINTER(Config), U32, ctypes.POINTER(P)]),
+        "flacgpu_open_decoder": (I32, [I32, U32, ctypes.c_uint8, ctypes.c_uint8, U32, U32, ctypes.POINTER(P)]),
         "flacgpu_close": (None, [P]),
         "flacgpu_strerror": (ctypes.c_char_p, [I32]),
         "flacgpu_abi_version": (I32, []),
@@ -400,7 +401,7 @@ def exported_symbols() -> list:
         "flacgpu_decode_file", "flacgpu_flac_index_device",
         "flacgpu_flac_index_streams_device", "flacgpu_decode_streams_device", "flacgpu_decode_files",
         "flacgpu_flac_positions_streams_device", "flacgpu_decode_windows_device", "flacgpu_decode_files_windows",
-        "flacgpu_decode_windows_device_as",
+        "flacgpu_decode_windows_device_as", "flacgpu_open_decoder",
     ]
 
 
@@ -933,13 +934,34 @@ class Encoder(_DecodeOps):
         return list(arr)[: n.value]
 
 
+DECODER_MAX_BLOCK = 16384  # FLACGPU_DECODER_MAX_BLOCK
+DECODER_MAX_BLOCK_32 = 8192  # FLACGPU_DECODER_MAX_BLOCK_32: at 32 bits per sample
+
+
+def decoder_max_block(bits: int) -> int:
+    return DECODER_MAX_BLOCK_32 if bits == 32 else DECODER_MAX_BLOCK
+
+
 class Decoder(Encoder):
     """A context used to decode: frames of `channels` x `bits` with blocks of at most block_size
-    samples.  There is no CPU fallback: without a device the constructor raises FlacGpuError(-5)."""
+    samples.  Up to 4096 it is the encoder's context (flacgpu_open); above, a decode-only one
+    (flacgpu_open_decoder: up to decoder_max_block(bits) samples), on which every encode method raises
+    FlacGpuError(-1).  There is no CPU fallback: without a device the constructor raises FlacGpuError(-5)."""
 
     def __init__(self, channels: int, bits: int, sample_rate: int, device: int = 0, max_frames: int = 4096,
                  block_size: int = 4096):
-        super().__init__(channels, bits, sample_rate, device=device, max_frames=max_frames, block_size=block_size)
+        if block_size <= 4096:
+            super().__init__(channels, bits, sample_rate, device=device, max_frames=max_frames, block_size=block_size)
+            return
+        self.lib = load_library()
+        self.cfg = Config(sample_rate, min(block_size, 0xFFFF), channels, bits, 0, 0, 0, 0)
+        self.channels, self.bits, self.sample_rate, self.block_size = channels, bits, sample_rate, block_size
+        self.bytes_per_sample = bits // 8
+        self.max_frames = max_frames
+        h = ctypes.c_void_p()
+        _check(self.lib.flacgpu_open_decoder(device, sample_rate, channels, bits, block_size, max_frames, ctypes.byref(h)),
+               "open_decoder")
+        self.ctx = h
 
 
 class MultiEncoder:
