@@ -646,6 +646,38 @@ int flacgpu_decode_windows_device_as(flacgpu_ctx *ctx, const uint8_t *d_data,
                                      uint32_t sample_format, uint32_t flags,
                                      void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
                                      flacgpu_window_result *d_results, void *hip_stream);
+/* The same delivery with a channel count other than the source's.  A window has K = out_channels
+ * (1 to 8) channels; channel_masks (HOST memory, K entries) names the source channels of each: bit
+ * c of channel_masks[k] is source channel c of the context's C.  With m the number of bits set,
+ * sample t of output channel k is
+ *   m = 0        zero in every format (bit pattern 0)
+ *   m = 1        that source sample's element, bit for bit what flacgpu_decode_windows_device_as
+ *                delivers
+ *   m = 2, 4, 8  the exact mean: with s the exact integer sum of the m sign-extended source samples
+ *                (|s| <= 8 * 2^31), FLACGPU_SAMPLE_F32 is (float)s * 2^-(bits - 1 + log2 m) -- the
+ *                conversion rounds to nearest-even (inexact only for |s| >= 2^24), the scale is
+ *                exact; in [-1, 1] -- and F16 and BF16 are that value narrowed as above
+ * A mix is valid when no mask has a bit at or above C, every m is 0, 1, 2, 4 or 8, and for
+ * FLACGPU_SAMPLE_I32 every m is at most 1 (selection, duplication, permutation and silence: a
+ * mean has no integer value to deliver).  Layout, padding and capacity are those of
+ * flacgpu_decode_windows_device_as with K in place of C: element t * K + k, or k * count + t with
+ * FLACGPU_DELIVER_PLANAR; out_offsets and out_caps in ELEMENTS; TOO_SMALL where K * count (PLANAR
+ * or PAD) or else K * n exceeds out_caps[w].  An invalid mix, out_channels outside 1..8, a NULL
+ * channel_masks and every argument error of flacgpu_decode_windows_device_as:
+ * FLACGPU_ERR_INVALID_INPUT before any device work.  Everything else -- the one wait, the chunks,
+ * BAD_INDEX and BAD_FRAME, windows that share streams and overlap, what is timed -- is as in
+ * flacgpu_decode_windows_device. */
+int flacgpu_decode_windows_device_mix(flacgpu_ctx *ctx, const uint8_t *d_data,
+                                      uint32_t n_streams, const uint64_t *table_first,
+                                      const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                      const flacgpu_index_result *d_index_results,
+                                      const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
+                                      uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
+                                      const uint64_t *window_count,
+                                      uint32_t sample_format, uint32_t flags,
+                                      uint32_t out_channels, const uint8_t *channel_masks,
+                                      void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
+                                      flacgpu_window_result *d_results, void *hip_stream);
 /* Windows of whole files in host memory: window w is samples [window_start[w], + window_count[w])
  * of file window_file[w] (< n_files), delivered to pcm_out[w] (capacity pcm_cap[w]) with
  * n_samples[w].  Metadata is parsed on the host as in flacgpu_decode_files; the good files' frames

@@ -51,6 +51,14 @@ median, and the parse and reconstruct kernel times in a pass of their own.  FLAC
 another build of the library for the same row of an earlier commit.
 
     python tools/decode_rate.py --legs bigblock --bigblock-out profiles/decode_bigblock_rate.json
+
+The mix leg (--mix-out; opt-in, not part of `all`) takes the windows leg's files and windows, stereo
+to mono, f32, planar and padded: flacgpu_decode_windows_device_mix with the mask of both channels
+against flacgpu_decode_windows_device_as followed by x.mean(dim=1, keepdim=True), alternated (HIP
+events, the median).  The two tensors are compared; they may differ in the last place, since the
+mix rounds the exact sum once and torch rounds each channel's element and then their mean.
+
+    python tools/decode_rate.py --legs mix --mix-out profiles/decode_mix_rate.json
 """
 import argparse
 import ctypes
@@ -684,6 +692,106 @@ def deliver_rate(n_files: int, frames_each: int, window: int, warmup: int, repea
     return res
 
 
+def mix_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: int) -> dict:
+    import numpy as np
+    import torch
+
+    import flacgpu
+    import synth
+
+    ch, bits, rate, _ = PRESETS["c2"]
+    per = ch * (bits // 8)
+    dev = torch.device("cuda", 0)
+    unit = synth.synth_pcm(64 * 4096, ch, bits, rate)
+    n_each = frames_each * 4096
+    pcm = (unit * ((frames_each + 63) // 64))[: n_each * per]
+    start = (n_each // 3 // 4096) * 4096 + 1234  # not a multiple of the block size
+    assert start % 4096 and start + window <= n_each
+    with flacgpu.Encoder(ch, bits, rate, device=0, max_frames=n_files * frames_each) as enc:
+        flacs = enc.encode_files([pcm] * n_files)
+        first = flacgpu.flac_index(flacs[0])[1]
+        bodies = [f[first:] for f in flacs]
+        offs, at = [], 0
+        for b in bodies:
+            offs.append(at)
+            at += (len(b) + 63) & ~63
+        host = np.zeros(at + 16, dtype=np.uint8)
+        for o, b in zip(offs, bodies):
+            host[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
+        d_buf = torch.from_numpy(host).to(dev)
+        lens = [len(b) for b in bodies]
+        caps = [n // 8 + 1 for n in lens]
+        tfirst = [int(v) for v in np.cumsum([0] + caps)[:-1]]
+        d_off = torch.zeros(sum(caps), dtype=torch.int64, device=dev)
+        d_fb = torch.zeros(sum(caps), dtype=torch.int32, device=dev)
+        d_pos = torch.zeros(sum(caps), dtype=torch.int64, device=dev)
+        d_tot = torch.zeros(n_files, dtype=torch.int64, device=dev)
+        d_ir = torch.zeros(16 * n_files, dtype=torch.uint8, device=dev)
+        d_wres = torch.zeros(32 * n_files, dtype=torch.uint8, device=dev)
+        st = torch.cuda.current_stream(dev).cuda_stream
+        sbits, srates = [bits] * n_files, [rate] * n_files
+        enc.flac_index_streams_device(d_buf.data_ptr(), offs, lens, tfirst, caps, d_off.data_ptr(), d_fb.data_ptr(),
+                                      d_ir.data_ptr(), stream_bits=sbits, stream_rates=srates, stream=st)
+        enc.flac_positions_streams_device(d_buf.data_ptr(), tfirst, caps, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(),
+                                          d_pos.data_ptr(), d_tot.data_ptr(), stream_bits=sbits, stream_rates=srates, stream=st)
+        tables = (d_buf.data_ptr(), tfirst, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(), d_pos.data_ptr(), d_tot.data_ptr())
+        planar_pad = flacgpu.DELIVER_PLANAR | flacgpu.DELIVER_PAD
+        crops = [(i, start, window) for i in range(n_files)]
+        x_mix = torch.zeros((n_files, 1, window), dtype=torch.float32, device=dev)
+        x_as = torch.zeros((n_files, ch, window), dtype=torch.float32, device=dev)
+
+        def mix():
+            enc.decode_windows_device_mix(*tables, crops, flacgpu.SAMPLE_F32, planar_pad, [3], x_mix.data_ptr(),
+                                          [i * window for i in range(n_files)], [window] * n_files, d_wres.data_ptr(), stream=st)
+            return x_mix
+
+        def as_then_mean():
+            enc.decode_windows_device_as(*tables, crops, flacgpu.SAMPLE_F32, planar_pad, x_as.data_ptr(),
+                                         [i * ch * window for i in range(n_files)], [ch * window] * n_files, d_wres.data_ptr(),
+                                         stream=st)
+            return x_as.mean(dim=1, keepdim=True)
+
+        def event_ms(fn):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            return a.elapsed_time(b)
+
+        def summary(ms):
+            return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms), "ms": ms}
+
+        def all_ok():
+            raw = d_wres.cpu().numpy().tobytes()
+            return [(r.status, r.n_samples) for r in (flacgpu.WindowResult * n_files).from_buffer_copy(raw)] == [(0, window)] * n_files
+
+        legs = {"mix_f32": mix, "as_f32_then_mean": as_then_mean}
+        for _ in range(warmup):
+            for fn in legs.values():
+                fn()
+                enc.sync_check(st)
+                assert all_ok()
+        # the expectation from the PCM: the exact sum, rounded once
+        v = np.frombuffer(pcm, dtype=np.int16).reshape(n_each, ch)[start:start + window].astype(np.int64).sum(axis=1)
+        want = torch.from_numpy(v.astype(np.float32) * np.float32(2.0 ** -bits))
+        got = mix().cpu()
+        assert torch.equal(got[0, 0], want) and torch.equal(got[-1, 0], want), "the mixed tensor differs from the PCM's exact mean"
+        other = as_then_mean().cpu()
+        ms = {k: [] for k in legs}
+        for _ in range(repeats):  # alternated
+            for k, fn in legs.items():
+                ms[k].append(event_ms(fn))
+        res = {"files": n_files, "frames_per_file": frames_each, "channels": ch, "bits": bits, "out_channels": 1, "mask": 3,
+               "window_samples": window, "window_start": start, "window_bytes": n_files * window * per,
+               "layout": "f32, planar, padded", "warmup": warmup, "repeats": repeats,
+               "elements_that_differ_from_torch_mean": int((got != other).sum()), "elements": got.numel()}
+        for k in legs:
+            res[k] = summary(ms[k])
+        res["mix_f32"]["x_as_then_mean"] = res["as_f32_then_mean"]["ms_median"] / res["mix_f32"]["ms_median"]
+    return res
+
+
 def bigblock_rate(blocks, n_streams: int, warmup: int, repeats: int) -> dict:
     import numpy as np
     import torch
@@ -757,7 +865,8 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock"), default="all")
+    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix"), default="all")
+    ap.add_argument("--mix-out", default=os.path.join(ROOT, "profiles", "decode_mix_rate.json"))
     ap.add_argument("--bigblock-out", default=os.path.join(ROOT, "profiles", "decode_bigblock_rate.json"))
     ap.add_argument("--blocks", default="4096,4608,16384")
     ap.add_argument("--streams", type=int, default=16)
@@ -773,6 +882,13 @@ def main():
         print(json.dumps({"bigblock": br}), flush=True)
         with open(a.bigblock_out, "w") as f:
             json.dump(br, f, indent=1)
+            f.write("\n")
+        return
+    if a.legs == "mix":  # opt-in: `all` leaves it out
+        mr = {"c2": mix_rate(a.files, a.frames // a.files, a.window, a.warmup, a.repeats)}
+        print(json.dumps({"mix": mr}), flush=True)
+        with open(a.mix_out, "w") as f:
+            json.dump(mr, f, indent=1)
             f.write("\n")
         return
     if a.legs == "deliver":  # opt-in: `all` leaves it out

@@ -447,7 +447,7 @@ int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexR
     HIPCHK(hipMemcpyAsync(wc.d_args, args.data(), (uint64_t)n * sizeof(window::WindowArg), hipMemcpyHostToDevice, st));
     {
         Timed t(c, FLACGPU_K_SCAN, st);
-        const uint32_t unit = dv.format == deliver::SAMPLE_BYTES ? dv.channels * dv.sample_bytes : dv.channels;
+        const uint32_t unit = dv.format == deliver::SAMPLE_BYTES ? dv.channels * dv.sample_bytes : dv.out_channels;
         HIPCHK(launch_window_cover(wc.d_args, d_ires, d_pos, d_totals, unit, dv.flags, wc.d_recs, n, st));
     }
     HIPCHK(hipMemcpyAsync(wc.recs.data(), wc.d_recs, (uint64_t)n * sizeof(window::Cover), hipMemcpyDeviceToHost, st));
@@ -459,8 +459,9 @@ int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexR
 // covering frames are its frames, cut with all the others' into chunks of max_frames; its PCM
 // region is span * per bytes of the context's window scratch (bases 16-byte aligned); its result is
 // a scratch StreamResult.  After the last chunk k_window_copy moves each clean window's bytes to
-// d_pcm_out + out_offsets[w] -- or, where dv converts, k_window_deliver writes its elements from
-// element out_offsets[w] of d_pcm_out on -- and k_window_results writes d_results.
+// d_pcm_out + out_offsets[w] -- or, where dv converts, k_window_deliver (k_window_mix where dv
+// mixes: dv.out_channels channels a sample) writes its elements from element out_offsets[w] of
+// d_pcm_out on -- and k_window_results writes d_results.
 int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_first, const uint64_t *d_foff,
                    const uint32_t *d_fbytes, const WindowsCall &wc, const uint32_t *window_stream,
                    const uint64_t *window_count, const deliver::Delivery &dv, uint8_t *d_pcm_out, const uint64_t *out_offsets,
@@ -530,7 +531,9 @@ int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_
                                 st, &cs);
         if (rc) return rc;
     }
-    if (convert)
+    if (convert && dv.mix)
+        HIPCHK(launch_window_mix(wc.d_recs, sres, wc.d_args, x->win_pcm, d_base, d_pcm_out, d_dst, dv, n, max_written, st));
+    else if (convert)
         HIPCHK(launch_window_deliver(wc.d_recs, sres, wc.d_args, x->win_pcm, d_base, d_pcm_out, d_dst, dv, n, max_written, st));
     else
         HIPCHK(launch_window_copy(wc.d_recs, sres, x->win_pcm, d_base, d_pcm_out, d_dst, (uint32_t)per, n, max_bytes, st));
@@ -687,14 +690,16 @@ int flacgpu_flac_positions_streams_device(flacgpu_ctx *c, const uint8_t *d_data,
 
 namespace {
 
-// flacgpu_decode_windows_device (format SAMPLE_BYTES, no flags: offsets and caps in bytes) and
-// flacgpu_decode_windows_device_as (offsets and caps in elements) behind their own checks
+// flacgpu_decode_windows_device (format SAMPLE_BYTES, no flags: offsets and caps in bytes),
+// flacgpu_decode_windows_device_as (offsets and caps in elements) and
+// flacgpu_decode_windows_device_mix (`masks`: its out_channels channel masks, else NULL) behind
+// their own checks
 int windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
                    const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes, const flacgpu_index_result *d_index_results,
                    const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples, uint32_t n_windows,
                    const uint32_t *window_stream, const uint64_t *window_start, const uint64_t *window_count,
-                   uint32_t sample_format, uint32_t flags, void *d_out, const uint64_t *offsets, const uint64_t *caps,
-                   flacgpu_window_result *d_results, void *hip_stream) {
+                   uint32_t sample_format, uint32_t flags, uint32_t out_channels, const uint8_t *masks, void *d_out,
+                   const uint64_t *offsets, const uint64_t *caps, flacgpu_window_result *d_results, void *hip_stream) {
     if (!c || !d_data || !table_first || !d_frame_offsets || !d_frame_bytes || !d_index_results || !d_frame_first_sample ||
         !d_stream_samples || n_windows > 65535u)
         return FLACGPU_ERR_INVALID_INPUT;
@@ -702,12 +707,18 @@ int windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, co
         return FLACGPU_ERR_INVALID_INPUT;
     for (uint32_t w = 0; w < n_windows; w++)
         if (window_stream[w] >= n_streams || offsets[w] + caps[w] < offsets[w]) return FLACGPU_ERR_INVALID_INPUT;
+    deliver::Delivery dv = deliver::identity_delivery(sample_format, flags, c->g.C, c->g.bits / 8u);
+    if (masks) {
+        if (!deliver::mix_valid(c->g.C, out_channels, masks, sample_format)) return FLACGPU_ERR_INVALID_INPUT;
+        dv.mix = 1u;
+        dv.out_channels = out_channels;
+        for (uint32_t k = 0; k < deliver::kMixMaxChannels; k++) dv.masks[k] = k < out_channels ? masks[k] : (uint8_t)0;
+    }
     if (n_windows == 0) return FLACGPU_OK;
     HIPCHK(hipSetDevice(c->device));
     int rc = dec_scratch(c);
     if (rc) return rc;
     hipStream_t st = pick_stream(c, hip_stream);
-    const deliver::Delivery dv{sample_format, flags, c->g.C, c->g.bits / 8u};
     WindowsCall wc;
     rc = windows_cover(c, table_first, (const idx::IndexResult *)d_index_results, d_frame_first_sample, d_stream_samples,
                        n_windows, window_stream, window_start, window_count, caps, dv, wc, st);
@@ -727,7 +738,7 @@ int flacgpu_decode_windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_
                                   void *hip_stream) {
     return windows_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results,
                           d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
-                          deliver::SAMPLE_BYTES, 0u, d_pcm_out, pcm_offsets, pcm_caps, d_results, hip_stream);
+                          deliver::SAMPLE_BYTES, 0u, 0u, nullptr, d_pcm_out, pcm_offsets, pcm_caps, d_results, hip_stream);
 }
 
 int flacgpu_decode_windows_device_as(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
@@ -742,7 +753,25 @@ int flacgpu_decode_windows_device_as(flacgpu_ctx *c, const uint8_t *d_data, uint
         return FLACGPU_ERR_INVALID_INPUT;
     return windows_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results,
                           d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
-                          sample_format, flags, d_out, out_offsets, out_caps, d_results, hip_stream);
+                          sample_format, flags, 0u, nullptr, d_out, out_offsets, out_caps, d_results, hip_stream);
+}
+
+int flacgpu_decode_windows_device_mix(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
+                                      const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                      const flacgpu_index_result *d_index_results, const uint64_t *d_frame_first_sample,
+                                      const uint64_t *d_stream_samples, uint32_t n_windows, const uint32_t *window_stream,
+                                      const uint64_t *window_start, const uint64_t *window_count, uint32_t sample_format,
+                                      uint32_t flags, uint32_t out_channels, const uint8_t *channel_masks, void *d_out,
+                                      const uint64_t *out_offsets, const uint64_t *out_caps, flacgpu_window_result *d_results,
+                                      void *hip_stream) {
+    if (!c || sample_format >= deliver::SAMPLE_FORMATS || (flags & ~deliver::DELIVER_FLAGS) ||
+        ((uintptr_t)d_out & (deliver::elem_size(sample_format) - 1u)) || !channel_masks || out_channels < 1u ||
+        out_channels > deliver::kMixMaxChannels)
+        return FLACGPU_ERR_INVALID_INPUT;
+    return windows_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results,
+                          d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
+                          sample_format, flags, out_channels, channel_masks, d_out, out_offsets, out_caps, d_results,
+                          hip_stream);
 }
 
 // every chunk's frames and frame table are uploaded, its results land at results + f0
@@ -996,7 +1025,7 @@ int fg::decode_files_windows_resident(flacgpu_ctx *c, uint32_t n, const uint8_t 
     if (rc) return rc;
     rc = positions_core(c, d->d_frames, n, first.data(), caps.data(), f_off, f_bytes, d_ires, bits, rates, f_pos, d_totals, st);
     if (rc) return rc;
-    const deliver::Delivery bytes{deliver::SAMPLE_BYTES, 0u, c->g.C, c->g.bits / 8u};
+    const deliver::Delivery bytes = deliver::identity_delivery(deliver::SAMPLE_BYTES, 0u, c->g.C, c->g.bits / 8u);
     WindowsCall wc;
     rc = windows_cover(c, first.data(), d_ires, f_pos, d_totals, n_windows, window_file, window_start, window_count, pcm_cap,
                        bytes, wc, st);

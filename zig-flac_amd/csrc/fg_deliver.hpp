@@ -1,7 +1,7 @@
 // fg_deliver.hpp -- the scalar rules of delivering decoded sample windows as tensor elements,
-// shared by the device kernel (k_window_deliver, fg_window.hip), the host layer (fg_dec_host.cpp)
-// and the stand-alone host program of the tests (tests/cpp/deliver_host_main.cpp).  Compiles under
-// hipcc and plain g++.
+// shared by the device kernels (k_window_deliver and k_window_mix, fg_window.hip), the host layer
+// (fg_dec_host.cpp) and the stand-alone host programs of the tests (tests/cpp/deliver_host_main.cpp,
+// tests/cpp/mix_host_main.cpp).  Compiles under hipcc and plain g++.
 //
 // A SOURCE SAMPLE is the B = bits / 8 bytes at a byte address of any alignment: signed two's
 // complement, little-endian, sign-extended to i32 -- what every decode call here writes to PCM,
@@ -11,7 +11,8 @@
 // with DELIVER_PAD the elements of t in [n, count) are written as zero.  A ROW is a run of
 // consecutive destination elements (one plane, or the whole interleaved region); its ROW PLAN cuts
 // it into the elements before the first 16-byte boundary, whole 16-byte units and the elements
-// after them: the element-granular counterpart of window::copy_plan.
+// after them: the element-granular counterpart of window::copy_plan.  With a CHANNEL MIX the
+// region has K output channels in place of C, each made of a set of source channels (below).
 #pragma once
 #include <stdint.h>
 
@@ -24,11 +25,23 @@ enum : uint32_t { SAMPLE_I32 = 0, SAMPLE_F32 = 1, SAMPLE_F16 = 2, SAMPLE_BF16 = 
 enum : uint32_t { DELIVER_PLANAR = 1, DELIVER_PAD = 2, DELIVER_FLAGS = 3 };                               // = FLACGPU_DELIVER_*
 constexpr uint32_t SAMPLE_BYTES = 0xFFFFFFFFu;  // not an element format: the byte copy of flacgpu_decode_windows_device
 
+constexpr uint32_t kMixMaxChannels = 8;  // output channels of a mix, and source channels of a mask
+
 // How a window call delivers: `format` SAMPLE_BYTES copies the PCM bytes (k_window_copy, flags 0);
-// any other format converts (k_window_deliver).
+// any other format converts (k_window_deliver) or, with `mix` set, converts and mixes
+// (k_window_mix): out_channels output channels, output channel k made of the source channels whose
+// bits masks[k] has.  Without `mix` out_channels = channels and masks[k] = 1 << k, the identity.
 struct Delivery {
     uint32_t format, flags, channels, sample_bytes;
+    uint32_t mix, out_channels;
+    uint8_t masks[kMixMaxChannels];
 };
+
+FG_HD Delivery identity_delivery(uint32_t format, uint32_t flags, uint32_t channels, uint32_t sample_bytes) {
+    Delivery dv = {format, flags, channels, sample_bytes, 0u, channels, {0, 0, 0, 0, 0, 0, 0, 0}};
+    for (uint32_t k = 0; k < channels && k < kMixMaxChannels; k++) dv.masks[k] = (uint8_t)(1u << k);
+    return dv;
+}
 
 FG_HD uint32_t elem_size(uint32_t format) { return format <= SAMPLE_F32 ? 4u : 2u; }
 
@@ -90,6 +103,61 @@ FG_HD uint32_t element(int32_t x, uint32_t bits, uint32_t format) {
     const uint32_t f = f32_bits(x, bits);
     if (format == SAMPLE_F32) return f;
     return format == SAMPLE_F16 ? f16_bits(f) : bf16_bits(f);
+}
+
+// ---- the channel mix ----------------------------------------------------------------------------
+// Output channel k of a mix is made of the m source channels in its mask (bit c: source channel c):
+// m = 0 is silence (bit pattern 0), m = 1 that channel's element, m = 2, 4 or 8 the exact mean.
+FG_HD uint32_t mask_count(uint32_t mask) {
+    uint32_t m = 0;
+    for (; mask; mask &= mask - 1u) m++;
+    return m;
+}
+
+// A mix of K output channels over a source of C: K is 1 to 8, no mask has a bit at or above C,
+// every mask holds 0, 1, 2, 4 or 8 channels, and SAMPLE_I32 -- which has no value for a mean -- at
+// most one.
+FG_HD bool mix_valid(uint32_t C, uint32_t K, const uint8_t *masks, uint32_t format) {
+    if (!masks || C < 1u || C > kMixMaxChannels || K < 1u || K > kMixMaxChannels || format >= SAMPLE_FORMATS) return false;
+    for (uint32_t k = 0; k < K; k++) {
+        const uint32_t m = mask_count(masks[k]);
+        if ((uint32_t)masks[k] >> C) return false;
+        if (m != 0u && m != 1u && m != 2u && m != 4u && m != 8u) return false;
+        if (format == SAMPLE_I32 && m > 1u) return false;
+    }
+    return true;
+}
+
+// The mean of m = 2^log2m samples of `bits` bits whose exact sum is s (|s| <= 8 * 2^31), in a
+// float `format`: (float)s * 2^-(bits - 1 + log2m).  s goes through double, which holds it exactly,
+// so the one rounding -- to nearest-even, inexact only for |s| >= 2^24 -- is that of the double ->
+// float conversion, the same instruction class on the host and the device; the scale is a normal
+// power of two (>= 2^-34) and the product exact, in [-1, 1].
+FG_HD uint32_t mean_element(int64_t s, uint32_t bits, uint32_t log2m, uint32_t format) {
+    union {
+        float f;
+        uint32_t u;
+    } sc, v;
+    sc.u = (127u - (bits - 1u + log2m)) << 23;
+    v.f = (float)(double)s * sc.f;
+    if (format == SAMPLE_F32) return v.u;
+    return format == SAMPLE_F16 ? f16_bits(v.u) : bf16_bits(v.u);
+}
+
+// Output channel `mask` of one sample whose C source channels are the B-byte samples from byte
+// offset `off` of `words` on (sample_in_words): only the channels in the mask are read.
+FG_HD uint32_t mix_element(const uint32_t *words, uint32_t off, uint32_t B, uint32_t mask, uint32_t format) {
+    const uint32_t m = mask_count(mask);
+    if (m == 0u) return 0u;
+    int64_t s = 0;
+    int32_t one = 0;
+    for (uint32_t c = 0; mask >> c; c++)
+        if ((mask >> c) & 1u) {
+            one = sample_in_words(words, off + c * B, B);
+            s += one;
+        }
+    if (m == 1u) return element(one, 8u * B, format);
+    return mean_element(s, 8u * B, m == 2u ? 1u : (m == 4u ? 2u : 3u), format);
 }
 
 // The capacity rule.  A window that delivers n of its `count` stated samples needs count * unit of

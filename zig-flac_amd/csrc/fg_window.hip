@@ -12,6 +12,9 @@
 //   k_window_deliver  in place of k_window_copy for flacgpu_decode_windows_device_as: the delivered
 //                     samples converted to tensor elements (fg_deliver.hpp), interleaved or planar,
 //                     the rest of a padded window zeroed
+//   k_window_mix      in place of k_window_deliver for flacgpu_decode_windows_device_mix: the same
+//                     pass with a channel count other than the source's, every output channel the
+//                     exact mean of a set of source channels, one of them, or silence
 //   k_window_results  per window: its flacgpu_window_result
 //
 // Every index is bounded by what the index left and the host sized: a frame i of stream s is
@@ -229,6 +232,88 @@ __global__ void __launch_bounds__(256) k_window_deliver(const Cover *recs, const
     }
 }
 
+// One element of a mixed tile: output channel `mask` of the tile's sample t, or zero past its
+// `nsrc` decoded samples (the padding).
+__device__ __forceinline__ uint32_t mix_tile_element(const uint32_t *words, uint32_t lead, uint32_t t, uint32_t nsrc, uint32_t per,
+                                                     uint32_t mask, const deliver::Delivery &dv) {
+    if (t >= nsrc) return 0u;
+    return deliver::mix_element(words, lead + t * per, dv.sample_bytes, mask, dv.format);
+}
+
+// k_window_deliver with a channel mix (flacgpu_decode_windows_device_mix): window w (blockIdx.y) as
+// K = dv.out_channels channels of dv.format elements to out + dst_off[w] elements, output channel k
+// of a sample made of the source channels in dv.masks[k] (deliver::mix_element).  The source tile
+// is k_window_deliver's -- tile_samples(per) consecutive source samples as the aligned 8-byte words
+// that hold them, no word past the one with the window's last byte, nothing read for a tile of
+// padding alone --; the rows are the destination's: K planes of the tile's samples, or one
+// interleaved row of samples * K elements, each cut by its row plan.  A window that is not clean
+// writes nothing; one with no samples still writes its padding.
+__global__ void __launch_bounds__(256) k_window_mix(const Cover *recs, const streams::StreamResult *res, const WindowArg *args,
+                                                     const uint8_t *scratch, const uint64_t *src_base, uint8_t *out,
+                                                     const uint64_t *dst_off, deliver::Delivery dv) {
+    __shared__ uint64_t s_src[deliver::kTileWords];
+    const uint32_t w = blockIdx.y, tid = threadIdx.x;
+    const Cover c = recs[w];
+    if (!window_clean(c, res[w])) return;
+    const uint64_t count = args[w].count, n = c.n_samples;
+    const uint64_t total = deliver::written_samples(n, count, dv.flags);
+    if (total == 0) return;
+    const uint32_t K = dv.out_channels, per = dv.channels * dv.sample_bytes, esz = deliver::elem_size(dv.format);
+    const uint32_t per_unit = 16u / esz, T = deliver::tile_samples(per);
+    const bool planar = (dv.flags & deliver::DELIVER_PLANAR) != 0;
+    uint64_t masks = 0;  // mask k in byte k: indexed by shifts, so that the argument is never addressed
+#pragma unroll
+    for (uint32_t k = 0; k < deliver::kMixMaxChannels; k++) masks |= (uint64_t)dv.masks[k] << (8u * k);
+    const uint8_t *src = scratch + src_base[w] + c.skip * per;
+    uint8_t *dst = out + dst_off[w] * esz;
+    const uint64_t n_tiles = (total + T - 1u) / T;
+    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint64_t t0 = tile * T;
+        const uint32_t ns = (uint32_t)(total - t0 < T ? total - t0 : T);          // samples written
+        const uint32_t nsrc = t0 < n ? (uint32_t)(n - t0 < T ? n - t0 : T) : 0u;  // of them decoded ones
+        uint32_t lead = 0;
+        if (nsrc) {
+            const uintptr_t a = (uintptr_t)(src + t0 * per), a0 = a & ~(uintptr_t)7;
+            lead = (uint32_t)(a - a0);
+            const uint32_t n_words = (lead + nsrc * per + 7u) / 8u;  // <= kTileWords
+            for (uint32_t i = tid; i < n_words; i += 256u) s_src[i] = ((const uint64_t *)a0)[i];
+        }
+        __syncthreads();
+        const uint32_t *words = (const uint32_t *)s_src;
+        const uint32_t rows = planar ? K : 1u, row_elems = planar ? ns : ns * K;
+        const uint32_t max_units = row_elems / per_unit, slots = max_units + 2u;  // a row's units, its head, its tail
+        for (uint32_t item = tid; item < rows * slots; item += 256u) {
+            const uint32_t r = item / slots, k = item - r * slots;
+            uint8_t *row = dst + (planar ? (uint64_t)r * count + t0 : t0 * K) * esz;
+            const deliver::RowPlan p = deliver::row_plan((uint64_t)(uintptr_t)row, row_elems, esz);
+            // row element e: sample e of plane r, or sample e / K, channel e % K of the interleaved row
+            auto elem = [&](uint32_t e) {
+                const uint32_t t = planar ? e : e / K, ch = planar ? r : e - t * K;
+                return mix_tile_element(words, lead, t, nsrc, per, (uint32_t)(masks >> (8u * ch)) & 0xFFu, dv);
+            };
+            if (k < max_units) {
+                if (k >= p.units) continue;
+                const uint32_t e0 = p.head + k * per_unit;
+                uint32_t q[4];
+                if (esz == 4u) {
+#pragma unroll
+                    for (uint32_t j = 0; j < 4u; j++) q[j] = elem(e0 + j);
+                } else {
+#pragma unroll
+                    for (uint32_t j = 0; j < 4u; j++) q[j] = elem(e0 + 2u * j) | (elem(e0 + 2u * j + 1u) << 16);
+                }
+                *(uint4 *)(row + (uint64_t)e0 * esz) = make_uint4(q[0], q[1], q[2], q[3]);
+            } else if (k == max_units) {
+                for (uint32_t e = 0; e < p.head; e++) store_element(row, e, esz, elem(e));
+            } else {
+                const uint32_t e1 = p.head + (uint32_t)p.units * per_unit;
+                for (uint32_t e = e1; e < e1 + p.tail; e++) store_element(row, e, esz, elem(e));
+            }
+        }
+        __syncthreads();  // s_src is written again by the next tile
+    }
+}
+
 __global__ void __launch_bounds__(256) k_window_results(const Cover *recs, const streams::StreamResult *res, WindowResult *out,
                                                          uint32_t n) {
     const uint32_t w = blockIdx.x * 256u + threadIdx.x;
@@ -303,6 +388,18 @@ hipError_t launch_window_deliver(const Cover *recs, const streams::StreamResult 
     const uint64_t tiles = (max_samples + T - 1u) / T;
     const uint32_t gx = (uint32_t)(tiles > 1024u ? 1024u : tiles);
     hipLaunchKernelGGL(k_window_deliver, dim3(gx, n), dim3(256), 0, st, recs, res, args, scratch, src_base, out, dst_off, dv);
+    return hipGetLastError();
+}
+
+// launch_window_deliver's grid for a Delivery with `mix` set: the tiles are of source samples either way
+hipError_t launch_window_mix(const Cover *recs, const streams::StreamResult *res, const WindowArg *args, const uint8_t *scratch,
+                             const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off, const deliver::Delivery &dv,
+                             uint32_t n, uint64_t max_samples, hipStream_t st) {
+    if (n == 0 || max_samples == 0) return hipSuccess;
+    const uint32_t T = deliver::tile_samples(dv.channels * dv.sample_bytes);
+    const uint64_t tiles = (max_samples + T - 1u) / T;
+    const uint32_t gx = (uint32_t)(tiles > 1024u ? 1024u : tiles);
+    hipLaunchKernelGGL(k_window_mix, dim3(gx, n), dim3(256), 0, st, recs, res, args, scratch, src_base, out, dst_off, dv);
     return hipGetLastError();
 }
 

@@ -5,7 +5,11 @@ scanned once (flacgpu_flac_index_streams_device, flacgpu_flac_positions_streams_
 `crops` call then decodes only the frames that hold the requested samples and delivers them as
 [crop, channel, time] (or [crop, time, channel]) elements in one pass
 (flacgpu_decode_windows_device_as), on the caller's current torch stream.  Plumbing over the C ABI:
-there is no CPU path.  A bank takes no locks: one bank per thread, like a context."""
+there is no CPU path.  A bank takes no locks: one bank per thread, like a context.
+
+FlacBank holds files of one channel count and depth.  FlacMixBank holds any, as one FlacBank per
+(channels, bits), and delivers every crop with the bank's one channel count through
+flacgpu_decode_windows_device_mix."""
 from __future__ import annotations
 
 from typing import Optional, Sequence
@@ -24,35 +28,48 @@ def _formats():
             torch.bfloat16: flacgpu.SAMPLE_BF16}
 
 
+def _parse(who: str, i: int, f: bytes):
+    """File i's STREAMINFO and its bare frames, parsed on the host."""
+    try:
+        si, first, _ = flacgpu.flac_index(f)
+    except flacgpu.FlacGpuError as e:
+        raise ValueError(f"{who}: file {i} is not a FLAC file this library indexes ({e})") from None
+    return si, bytes(f[first:])
+
+
+def _check_blocks(who: str, i: int, si) -> None:
+    """The block-size rule: a larger block than the decoder takes would only show as BAD_FRAME at crop time."""
+    most = flacgpu.decoder_max_block(int(si.bit_depth))
+    if int(si.max_block_size) > most:
+        raise ValueError(f"{who}: file {i} states blocks of {int(si.max_block_size)} samples, the decoder takes "
+                         f"at most {most} at {int(si.bit_depth)} bits")
+
+
 class FlacBank:
-    def __init__(self, files: Sequence[bytes], device: int = 0, max_frames: int = 4096):
+    def __init__(self, files: Sequence[bytes], device: int = 0, max_frames: int = 4096, _group=None):
+        # _group: (who, [the caller's file index], [(STREAMINFO, bare frames)]) from FlacMixBank, whose
+        # files are parsed and checked already and whose messages name its caller's indices
+        who, names, parsed = _group if _group else ("FlacBank", range(len(files)), None)
         if len(files) == 0:
             raise ValueError("FlacBank: no files")
         if len(files) > 65535:
             raise ValueError("FlacBank: more than 65535 files")
         infos, bare = [], []
         for i, f in enumerate(files):
-            try:
-                si, first, _ = flacgpu.flac_index(f)
-            except flacgpu.FlacGpuError as e:
-                raise ValueError(f"FlacBank: file {i} is not a FLAC file this library indexes ({e})") from None
+            si, frames = parsed[i] if parsed else _parse(who, i, f)
             if infos and (si.channels, si.bit_depth) != (infos[0].channels, infos[0].bit_depth):
                 raise ValueError(f"FlacBank: file {i} has {si.channels} channels of {si.bit_depth} bits, file 0 has "
                                  f"{infos[0].channels} of {infos[0].bit_depth}: one bank holds one channel count and depth")
             infos.append(si)
-            bare.append(bytes(f[first:]))
+            bare.append(frames)
         self._dec = None
         self.channels, self.bits = int(infos[0].channels), int(infos[0].bit_depth)
         self.sample_rates = [int(si.sample_rate) for si in infos]
         self.compressed_bytes = sum(len(b) for b in bare)
         stated = [int(si.interchannel_samples) for si in infos]
-        # the context decodes the largest block any file states; a larger one than the decoder takes
-        # would only show as BAD_FRAME at crop time
-        most = flacgpu.decoder_max_block(self.bits)
+        # the context decodes the largest block any file states
         for i, si in enumerate(infos):
-            if int(si.max_block_size) > most:
-                raise ValueError(f"FlacBank: file {i} states blocks of {int(si.max_block_size)} samples, the decoder takes "
-                                 f"at most {most} at {self.bits} bits")
+            _check_blocks(who, names[i], si)
 
         # ---- everything below needs the device
         import numpy as np
@@ -95,10 +112,10 @@ class FlacBank:
         for i in range(n):
             if ires[i].status != flacgpu.INDEX_OK:
                 self.close()
-                raise flacgpu.FlacGpuError(-2, f"FlacBank: the device index refuses file {i} (status {ires[i].status})")
+                raise flacgpu.FlacGpuError(-2, f"{who}: the device index refuses file {names[i]} (status {ires[i].status})")
             if stated[i] and self.samples[i] != stated[i]:
                 self.close()
-                raise ValueError(f"FlacBank: file {i} holds {self.samples[i]} samples, its STREAMINFO states {stated[i]}")
+                raise ValueError(f"{who}: file {names[i]} holds {self.samples[i]} samples, its STREAMINFO states {stated[i]}")
 
     def close(self) -> None:
         if getattr(self, "_dec", None) is not None:
@@ -174,6 +191,196 @@ class FlacBank:
                 if s != flacgpu.WINDOW_OK:
                     bad = f", frame {res[w].first_bad_frame}" if s == flacgpu.WINDOW_BAD_FRAME else ""
                     raise flacgpu.FlacGpuError(-2, f"FlacBank.crops: crop {w} (file {int(file[w])}, start {int(start[w])}) is "
+                                                   f"{WINDOW_STATUS.get(s, s)}{bad}")
+            return x, n
+        return x, n, statuses
+
+
+MIX_MAX_CHANNELS = 8
+
+
+def _mix_error(C: int, masks: Sequence[int], integers: bool = False) -> Optional[str]:
+    """Why `masks` is no valid mix of a source of C channels (the rule of
+    flacgpu_decode_windows_device_mix, checked here so that it is a ValueError before any call), or None."""
+    for k, m in enumerate(masks):
+        if not 0 <= m <= 255:
+            return f"mask {k} is not an integer in 0..255"
+        if m >> C:
+            return f"mask {k} ({m:#x}) names a channel at or above {C}"
+        count = bin(m).count("1")
+        if count not in (0, 1, 2, 4, 8):
+            return f"mask {k} ({m:#x}) is a mean of {count} channels; 2, 4 and 8 are offered"
+        if integers and count > 1:
+            return f"mask {k} ({m:#x}) is a mean, which int32 cannot deliver"
+    return None
+
+
+def _default_masks(C: int, K: int) -> Optional[list]:
+    if C == K:
+        return [1 << k for k in range(K)]
+    if C == 1:
+        return [1] * K
+    if K == 1 and C in (2, 4, 8):
+        return [(1 << C) - 1]
+    return None
+
+
+class FlacMixBank:
+    """FLAC files of any channel counts and depths, crops of any of them as `channels` channels.
+
+    The files are grouped by (channels, bits), in file order; every group is a FlacBank of its own
+    -- one decode context, one upload, one index -- and a crop is delivered by its group through
+    flacgpu_decode_windows_device_mix with the group's channel masks: channel_map[C], a list of
+    `channels` masks (bit c: source channel c; 0, 1, 2, 4 or 8 bits) for sources of C channels,
+    or else the default: identity where C == channels, the one channel to every output where
+    C == 1, the mean of all where channels == 1 and C is 2, 4 or 8.  Rates are reported, never
+    converted.  A bank takes no locks: one bank per thread."""
+
+    def __init__(self, files: Sequence[bytes], channels: int, device: int = 0, max_frames: int = 4096,
+                 channel_map: Optional[dict] = None):
+        who, K = "FlacMixBank", int(channels)
+        self._groups: list = []
+        if len(files) == 0:
+            raise ValueError(f"{who}: no files")
+        if len(files) > 65535:
+            raise ValueError(f"{who}: more than 65535 files")
+        if not 1 <= K <= MIX_MAX_CHANNELS:
+            raise ValueError(f"{who}: channels is {K}, not 1 to {MIX_MAX_CHANNELS}")
+        parsed = [_parse(who, i, f) for i, f in enumerate(files)]
+        self.channels = K
+        self.file_channels = [int(si.channels) for si, _ in parsed]
+        self.file_bits = [int(si.bit_depth) for si, _ in parsed]
+        self.sample_rates = [int(si.sample_rate) for si, _ in parsed]
+        self.compressed_bytes = sum(len(b) for _, b in parsed)
+        members: dict = {}  # (channels, bits) -> the caller's file indices, in order
+        for i in range(len(files)):
+            members.setdefault((self.file_channels[i], self.file_bits[i]), []).append(i)
+        masks_of = {}
+        for (C, bits), idx in members.items():
+            if C in masks_of:
+                continue
+            given = channel_map.get(C) if channel_map else None
+            masks = [int(m) for m in given] if given is not None else _default_masks(C, K)
+            if masks is None:
+                raise ValueError(f"{who}: file {idx[0]} has {C} channels and there is no default mix of {C} channels "
+                                 f"to {K}: give channel_map[{C}]")
+            why = f"it has {len(masks)} masks, not {K}" if len(masks) != K else _mix_error(C, masks)
+            if why:
+                raise ValueError(f"{who}: channel_map[{C}], which file {idx[0]} needs, is not valid: {why}")
+            masks_of[C] = masks
+        for i, (si, _) in enumerate(parsed):
+            _check_blocks(who, i, si)
+
+        # ---- everything below needs the device
+        self._where = [None] * len(files)  # file -> (group, its index there)
+        self.samples = [0] * len(files)
+        try:
+            for g, ((C, bits), idx) in enumerate(members.items()):
+                bank = FlacBank([files[i] for i in idx], device=device, max_frames=max_frames,
+                                _group=(who, idx, [parsed[i] for i in idx]))
+                self._groups.append((bank, masks_of[C]))
+                for j, i in enumerate(idx):
+                    self._where[i] = (g, j)
+                    self.samples[i] = bank.samples[j]
+        except Exception:
+            self.close()
+            raise
+        self.device = self._groups[0][0].device
+        self.bits = sorted(set(self.file_bits))  # the depths the bank holds
+
+    def close(self) -> None:
+        for bank, _ in getattr(self, "_groups", []):
+            bank.close()
+        self._groups = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return len(self.sample_rates)
+
+    def crops(self, file: Sequence[int], start: Sequence[int], length: int, dtype=None, planar: bool = True,
+              pad: bool = True, out=None, strict: bool = True):
+        """FlacBank.crops over the mixed bank -> (x, n), or (x, n, statuses) with strict=False: x of
+        shape [W, channels, length] (planar) or [W, length, channels], every crop mixed to the bank's
+        channels by its file's masks; n and the statuses in the caller's order.  float dtypes scale
+        each file by its own depth; dtype=torch.int32 needs a bank of one depth (the integers of two
+        depths have different scales) and masks without a mean.  The crops are routed to their
+        format groups; every group queues its calls (at most 65535 windows each) on
+        torch.cuda.current_stream(device) into the one x, and the call waits once per such call of
+        a group that has crops, then once for the results.  A damaged frame in one file harms no
+        crop of another."""
+        import torch
+
+        who = "FlacMixBank"
+        if not self._groups:
+            raise ValueError(f"{who}: closed")
+        dtype = torch.float32 if dtype is None else dtype
+        fmt = _formats().get(dtype)
+        if fmt is None:
+            raise ValueError(f"{who}: dtype {dtype} is none of float32, float16, bfloat16, int32")
+        if fmt == flacgpu.SAMPLE_I32:
+            if len(self.bits) > 1:
+                raise ValueError(f"{who}: int32 crops of a bank that holds depths {self.bits}: the integers would have "
+                                 f"different scales")
+            for bank, masks in self._groups:
+                why = _mix_error(bank.channels, masks, integers=True)
+                if why:
+                    raise ValueError(f"{who}: int32 crops of {bank.channels}-channel files: {why}")
+        W, K, length = len(file), self.channels, int(length)
+        if len(start) != W:
+            raise ValueError(f"{who}: file and start differ in length")
+        if length < 0 or any(not 0 <= int(f) < len(self) for f in file) or any(int(s) < 0 for s in start):
+            raise ValueError(f"{who}: a file index, a start or the length is out of range")
+        shape = (W, K, length) if planar else (W, length, K)
+        routed = [[] for _ in self._groups]  # group -> its crops, in the caller's order
+        for w in range(W):
+            routed[self._where[int(file[w])][0]].append(w)
+        order = [w for ws in routed for w in ws]  # row r of d_res is crop order[r]
+        with torch.cuda.device(self.device):
+            if out is not None:
+                if (tuple(out.shape) != shape or out.dtype != dtype or out.device != self.device or not out.is_contiguous()):
+                    raise ValueError(f"{who}: out must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
+                x = out
+                if not pad:
+                    x.zero_()
+            else:
+                x = torch.empty(shape, dtype=dtype, device=self.device) if pad else torch.zeros(shape, dtype=dtype,
+                                                                                                 device=self.device)
+            flags = (flacgpu.DELIVER_PLANAR if planar else 0) | (flacgpu.DELIVER_PAD if pad else 0)
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            d_res = torch.empty(32 * max(W, 1), dtype=torch.uint8, device=self.device)
+            per_crop, row = K * length, 0
+            for (bank, masks), ws in zip(self._groups, routed):
+                for w0 in range(0, len(ws), MAX_WINDOWS):
+                    part = ws[w0:w0 + MAX_WINDOWS]
+                    windows = [(self._where[int(file[w])][1], int(start[w]), length) for w in part]
+                    bank._dec.decode_windows_device_mix(
+                        bank._data.data_ptr(), bank._first, bank._off.data_ptr(), bank._fbytes.data_ptr(),
+                        bank._ires.data_ptr(), bank._pos.data_ptr(), bank._totals.data_ptr(), windows, fmt, flags, masks,
+                        x.data_ptr(), [w * per_crop for w in part], [per_crop] * len(part), d_res.data_ptr() + 32 * row,
+                        stream=st)
+                    row += len(part)
+            rows = (flacgpu.WindowResult * max(W, 1)).from_buffer_copy(d_res.cpu().numpy().tobytes())  # waits for st
+        res = [None] * W
+        for r, w in enumerate(order):
+            res[w] = rows[r]
+        n = [int(res[w].n_samples) for w in range(W)]
+        statuses = [int(res[w].status) for w in range(W)]
+        if strict:
+            for w, s in enumerate(statuses):
+                if s != flacgpu.WINDOW_OK:
+                    bad = f", frame {res[w].first_bad_frame}" if s == flacgpu.WINDOW_BAD_FRAME else ""
+                    raise flacgpu.FlacGpuError(-2, f"{who}.crops: crop {w} (file {int(file[w])}, start {int(start[w])}) is "
                                                    f"{WINDOW_STATUS.get(s, s)}{bad}")
             return x, n
         return x, n, statuses

@@ -364,6 +364,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_decode_windows_device": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, P, P, P, P, P]),
         "flacgpu_decode_files_windows": (I32, [P, U32, P, P, U32, P, P, P, P, P, P, P]),
         "flacgpu_decode_windows_device_as": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, U32, P, P, P, P, P]),
+        "flacgpu_decode_windows_device_mix": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, U32, U32, P, P, P, P, P, P]),
     }
     # an older build named by FLACGPU_LIB (same-box A/B runs, tools/ab.sh) may predate later entry
     # points: those stay unbound there; the in-tree library must export every one
@@ -401,7 +402,7 @@ def exported_symbols() -> list:
         "flacgpu_decode_file", "flacgpu_flac_index_device",
         "flacgpu_flac_index_streams_device", "flacgpu_decode_streams_device", "flacgpu_decode_files",
         "flacgpu_flac_positions_streams_device", "flacgpu_decode_windows_device", "flacgpu_decode_files_windows",
-        "flacgpu_decode_windows_device_as", "flacgpu_open_decoder",
+        "flacgpu_decode_windows_device_as", "flacgpu_open_decoder", "flacgpu_decode_windows_device_mix",
     ]
 
 
@@ -622,6 +623,24 @@ class _DecodeOps:
             d_frame_first_sample, d_stream_samples, len(windows), _u32s([w[0] for w in windows]),
             _u64s([w[1] for w in windows]), _u64s([w[2] for w in windows]), sample_format, flags, d_out,
             _u64s(out_offsets), _u64s(out_caps), d_results, _stream(stream)), "decode_windows_device_as")
+
+    def decode_windows_device_mix(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int, d_frame_bytes: int,
+                                  d_index_results: int, d_frame_first_sample: int, d_stream_samples: int,
+                                  windows: Sequence, sample_format: int, flags: int, channel_masks: Sequence[int],
+                                  d_out: int, out_offsets: Sequence[int], out_caps: Sequence[int], d_results: int,
+                                  stream: Optional[int] = None) -> None:
+        """flacgpu_decode_windows_device_mix: decode_windows_device_as with len(channel_masks) output
+        channels, output channel k made of the source channels whose bits channel_masks[k] has (their
+        exact mean, the one, or silence); offsets and caps in elements of that channel count."""
+        masks = [int(m) for m in channel_masks]
+        if any(not 0 <= m <= 255 for m in masks):
+            raise FlacGpuError(-2, "decode_windows_device_mix: a channel mask is not in 0..255")
+        _check(self.lib.flacgpu_decode_windows_device_mix(
+            self.ctx, d_data, len(table_first), _u64s(table_first), d_frame_offsets, d_frame_bytes, d_index_results,
+            d_frame_first_sample, d_stream_samples, len(windows), _u32s([w[0] for w in windows]),
+            _u64s([w[1] for w in windows]), _u64s([w[2] for w in windows]), sample_format, flags, len(masks),
+            (ctypes.c_uint8 * max(len(masks), 1))(*masks), d_out, _u64s(out_offsets), _u64s(out_caps), d_results,
+            _stream(stream)), "decode_windows_device_mix")
 
     def decode_files_windows(self, flacs: Sequence[bytes], windows: Sequence, guard: int = 0,
                              pcm_caps: Optional[Sequence[int]] = None):
