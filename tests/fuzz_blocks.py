@@ -6,10 +6,17 @@ random step size (Rice parameters across their whole range), sparse spikes
 noise (mixed escape / Rice partitions), full-scale extremes and alternation
 (wide-overflow path, 33-bit sides), constant runs, wasted bits, and sums of
 sinusoids (where LPC wins).
+
+"extreme" treats every channel alike, so its alternation leaves a stereo side
+channel at 0; "antiphase" is the opposite-phase alternation (L = lo/hi,
+R = hi/lo: a side of +-(2^bits - 1), the widest there is).  It is not in KINDS,
+which stream() draws from -- the seeded streams keep their draws -- and has
+streams of its own (antiphase_stream).
 """
 import numpy as np
 
 KINDS = ["walk", "spikes", "mixture", "extreme", "constant", "wasted", "sines", "noise"]
+ALL_KINDS = KINDS + ["antiphase"]
 
 
 def block(rng, n, channels, bits, kind):
@@ -34,6 +41,13 @@ def block(rng, n, channels, bits, kind):
         if rng.random() < 0.5:
             x[::2] = lo
             x[1::2] = hi
+    elif kind == "antiphase":
+        x = np.empty((n, channels), dtype=np.int64)
+        x[::2, 0::2], x[1::2, 0::2] = lo, hi
+        x[::2, 1::2], x[1::2, 1::2] = hi, lo
+        if rng.random() < 0.5:  # a few samples off the rails: the side is no two-valued signal
+            idx = rng.integers(0, n, size=max(1, n // 61))
+            x[idx] = rng.integers(lo, hi + 1, size=(len(idx), channels))
     elif kind == "constant":
         x = np.full((n, channels), int(rng.integers(lo, hi + 1)), dtype=np.int64)
         if rng.random() < 0.3 and n > 1:
@@ -60,5 +74,17 @@ def stream(seed, channels, bits, n_frames_max=3):
     tail = int(rng.integers(1, 4097))
     parts = [block(rng, 4096 if f < nf - 1 else tail, channels, bits, KINDS[int(rng.integers(0, len(KINDS)))])
              for f in range(nf)]
+    s = np.concatenate(parts, axis=0)
+    return synth.to_pcm_bytes(s, bits), len(s)
+
+
+def antiphase_stream(seed, channels, bits, n_frames_max=3):
+    """As stream(), every frame of the "antiphase" kind."""
+    import synth
+
+    rng = np.random.default_rng(seed)
+    nf = int(rng.integers(1, n_frames_max + 1))
+    tail = int(rng.integers(1, 4097))
+    parts = [block(rng, 4096 if f < nf - 1 else tail, channels, bits, "antiphase") for f in range(nf)]
     s = np.concatenate(parts, axis=0)
     return synth.to_pcm_bytes(s, bits), len(s)

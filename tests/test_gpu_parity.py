@@ -121,6 +121,27 @@ def test_block_size_1152():
     check_stream(2, 16, 44100, 1152 * 40 + 5, block_size=1152)
 
 
+def assert_record_matches(rec, orec, where):
+    """One frame's decision record against the restatement's: the channel code and, for every
+    candidate (the losing ones too), type, wasted bits, depth, estimate, order, partition order,
+    method and parameters (LPC: precision, shift, coefficients; CONSTANT: the value)."""
+    assert rec.channel_code == orec.channel_code, f"{where} channel code"
+    for c in range(orec.n_cand):
+        g, o = rec.cand[c], orec.cand[c]
+        ctx = f"{where} cand {c}"
+        assert (g.type, g.waste, g.bits) == (o.type, o.waste, o.bits), ctx
+        assert g.estimate == o.estimate, ctx + f" estimate {g.estimate} vs {o.estimate}"
+        if o.type >= 2:
+            assert (g.order, g.part_order, g.method) == (o.order, o.part_order, o.method), ctx
+            np_ = 1 << o.part_order
+            assert list(g.params)[:np_] == list(o.params)[:np_], ctx
+        if o.type == 3:
+            assert (g.lpc_precision, g.lpc_shift) == (o.lpc_precision, o.lpc_shift), ctx
+            assert list(g.lpc_coefs)[:o.order] == list(o.lpc_coefs)[:o.order], ctx
+        if o.type == 0:
+            assert g.constant == o.constant, ctx
+
+
 def _records_match(ch, bits, rate, n, stream=0, lpc=0):
     pcm = synth.synth_pcm(n, ch, bits, rate, stream=stream)
     enc = gpu_encoder(ch, bits, rate, **({"lpc_order": lpc} if lpc else {}))
@@ -137,21 +158,7 @@ def _records_match(ch, bits, rate, n, stream=0, lpc=0):
         planes = [np.ascontiguousarray(samples[f * bs:(f + 1) * bs, c]).astype(np.int32) for c in range(ch)]
         nn = len(planes[0])
         ref_bytes, orec = oracle_ref.encode_frame(planes, nn, f, ch, bits, rate, lpc=lpc)
-        assert rec.channel_code == orec.channel_code, f"frame {f} channel code"
-        for c in range(orec.n_cand):
-            g, o = rec.cand[c], orec.cand[c]
-            ctx = f"frame {f} cand {c}"
-            assert (g.type, g.waste, g.bits) == (o.type, o.waste, o.bits), ctx
-            assert g.estimate == o.estimate, ctx + f" estimate {g.estimate} vs {o.estimate}"
-            if o.type >= 2:
-                assert (g.order, g.part_order, g.method) == (o.order, o.part_order, o.method), ctx
-                np_ = 1 << o.part_order
-                assert list(g.params)[:np_] == list(o.params)[:np_], ctx
-            if o.type == 3:
-                assert (g.lpc_precision, g.lpc_shift) == (o.lpc_precision, o.lpc_shift), ctx
-                assert list(g.lpc_coefs)[:o.order] == list(o.lpc_coefs)[:o.order], ctx
-            if o.type == 0:
-                assert g.constant == o.constant, ctx
+        assert_record_matches(rec, orec, f"frame {f}")
     return got
 
 
