@@ -15,9 +15,9 @@
 //       Prints {"too_small": [0 | 1 ...]}.
 //   deliver_host_main rows
 //       For the formats i32, f32, f16 and bf16, every destination alignment within 16 bytes that the
-//       element size allows and every row length 0-40: the row filled by its plan (head elements,
-//       whole 16-byte units, tail elements) in a guarded buffer against the straightforward
-//       conversion element by element.  Prints {"cases": count}.
+//       element size allows and every row length 0-40: the row filled slot by slot by the kernel's
+//       own fill_row_slot (head elements, whole 16-byte units, tail elements) in a guarded buffer
+//       against the straightforward conversion element by element.  Prints {"cases": count}.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -134,19 +134,9 @@ int run_rows() {
                 if (p.head >= per_unit || p.tail >= per_unit || p.head + per_unit * p.units + p.tail != len)
                     fail("the plan does not add up");
                 if ((p.units || p.tail) && ((uintptr_t)(dst + p.head * esz) & 15u)) fail("a unit is not aligned");
-                auto store = [&](uint32_t e) {
-                    const uint32_t v = elem(e);
-                    std::memcpy(dst + (size_t)e * esz, &v, esz);
-                };
-                for (uint32_t e = 0; e < p.head; e++) store(e);
-                for (uint64_t u = 0; u < p.units; u++) {
-                    uint32_t q[4];
-                    const uint32_t e0 = p.head + (uint32_t)u * per_unit;
-                    for (uint32_t j = 0; j < 4u; j++)
-                        q[j] = esz == 4u ? elem(e0 + j) : (elem(e0 + 2u * j) | (elem(e0 + 2u * j + 1u) << 16));
-                    std::memcpy(__builtin_assume_aligned(dst + (size_t)e0 * esz, 16), q, 16);
-                }
-                for (uint32_t e = len - p.tail; e < len; e++) store(e);
+                // the row as the kernel fills it: every slot, by the kernel's own function
+                const uint32_t max_units = len / per_unit;
+                for (uint32_t k = 0; k < max_units + 2u; k++) fill_row_slot(dst, len, esz, k, max_units, elem);
                 if (std::memcmp(base, want.data(), size) != 0) fail("the row differs from the straightforward conversion");
                 std::free(words);
                 std::free(dp);

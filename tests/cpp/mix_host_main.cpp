@@ -17,9 +17,10 @@
 //   mix_host_main rows
 //       For the four formats, every destination alignment within 16 bytes that the element size
 //       allows, 0-40 samples written, C in {1, 2, 3, 8}, K in {1, 2, 3}, planar and interleaved,
-//       with and without padding: the tile's rows filled by their plans (head elements, whole
-//       16-byte units, tail elements) in a guarded buffer, as k_window_mix fills them, against the
-//       rule element by element from load_sample.  Prints {"cases": count}.
+//       with and without padding: the tile's rows filled slot by slot by the kernel's own
+//       fill_row_slot (head elements, whole 16-byte units, tail elements) in a guarded buffer, with
+//       the element rule of k_window_elements<true>, against the rule element by element from
+//       load_sample.  Prints {"cases": count}.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -178,7 +179,7 @@ int run_rows() {
                                     const size_t at = planar ? (size_t)k * count + t : (size_t)t * K + k;
                                     std::memcpy(want.data() + PAD + da + at * esz, &v, esz);
                                 }
-                            // the tile as the kernel fills it (t0 = 0)
+                            // the tile as the kernel fills it (t0 = 0): every slot of every row, by the kernel's own function
                             const uint32_t rows = planar ? K : 1u, row_elems = planar ? ns : ns * K;
                             for (uint32_t r = 0; r < rows; r++) {
                                 uint8_t *row = dst + (planar ? (size_t)r * count : 0u) * esz;
@@ -189,19 +190,8 @@ int run_rows() {
                                     const uint32_t t = planar ? e : e / K, ch = planar ? r : e - t * K;
                                     return t < nsrc ? mix_element(words, LEAD + t * per, B, masks[ch], format) : 0u;
                                 };
-                                auto store = [&](uint32_t e) {
-                                    const uint32_t v = elem(e);
-                                    std::memcpy(row + (size_t)e * esz, &v, esz);
-                                };
-                                for (uint32_t e = 0; e < p.head; e++) store(e);
-                                for (uint64_t u = 0; u < p.units; u++) {
-                                    uint32_t q[4];
-                                    const uint32_t e0 = p.head + (uint32_t)u * per_unit;
-                                    for (uint32_t j = 0; j < 4u; j++)
-                                        q[j] = esz == 4u ? elem(e0 + j) : (elem(e0 + 2u * j) | (elem(e0 + 2u * j + 1u) << 16));
-                                    std::memcpy(__builtin_assume_aligned(row + (size_t)e0 * esz, 16), q, 16);
-                                }
-                                for (uint32_t e = row_elems - p.tail; e < row_elems; e++) store(e);
+                                const uint32_t max_units = row_elems / per_unit;
+                                for (uint32_t k = 0; k < max_units + 2u; k++) fill_row_slot(row, row_elems, esz, k, max_units, elem);
                             }
                             if (std::memcmp(base, want.data(), size) != 0) fail("the rows differ from the rule element by element");
                             std::free(words);

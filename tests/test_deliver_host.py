@@ -6,7 +6,7 @@ stand-alone program tests/cpp/deliver_host_main.cpp.  No GPU.
 `convert`: int -> f32 -> f16 / bf16 as bit patterns against numpy (f32, f16) and torch on the CPU
 (bf16): all 16-bit and 8-bit values, and for 24 and 32 bits a directed set (the ties of every
 conversion, the limits, the f16 subnormal range) plus 10^5 seeded random values.  `capacity`: the
-capacity rule against Python integers.  `rows`: the row plan, filled by a plain loop, against the
+capacity rule against Python integers.  `rows`: the row plan, filled by the kernel's own fill_row_slot, against the
 element-by-element conversion in a guarded buffer.  Bit patterns are compared; no tolerance."""
 import json
 import os

@@ -23,7 +23,7 @@ import oracle_ref  # noqa: E402
 import synth  # noqa: E402
 import test_gpu_decode as tgd  # noqa: E402
 import test_gpu_frame_grammar as tgf  # noqa: E402
-import test_gpu_windows as tgw  # noqa: E402
+import window_helpers as wh  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -178,7 +178,7 @@ WINDOWS = {  # (start, count): inside a big frame, across each boundary, everyth
 @pytest.mark.parametrize("name", sorted(WINDOWS))
 def test_windows_inside_and_across_big_frames(name):
     c = bb.case(name)
-    tgw._grammar_call(c, [(0, s, n) for s, n in WINDOWS[name]], tgw.odd_layout, block_size=16384)
+    wh.grammar_call(c, [(0, s, n) for s, n in WINDOWS[name]], wh.odd_layout, block_size=16384)
 
 
 def test_flacbank_crops_of_big_frames():

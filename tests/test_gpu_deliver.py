@@ -9,7 +9,7 @@ Every output buffer is filled with 0xA5 before the call and compared whole, so a
 anywhere fails.  The files are those of test_gpu_windows.py: stereo 16-bit, blocks of 256,
 [64, 1, 3, 70, 0] frames, decoded by a context that holds 64 frames per call.
 
-Mutation counts (each mutant of k_window_deliver / its host side fails tests here): DESIGN.md 7b."""
+Mutation counts (each mutant of k_window_elements<false> / its host side fails tests here): DESIGN.md 7b."""
 import os
 import random
 import sys
@@ -23,38 +23,18 @@ sys.path.insert(0, HERE)
 import flac_bits  # noqa: E402
 import frame_grammar as fg  # noqa: E402
 import synth  # noqa: E402
+from window_helpers import (BITS, BLOCK, CH, FRAMES, GUARD, NONE, PER, RATE, Resident, _bare, _blocks, _samples,  # noqa: E402,F401
+                            _torch, cover)
+from window_helpers import ctx, files, resident  # noqa: E402,F401  (fixtures: the five stereo 16-bit files)
 
 pytestmark = pytest.mark.gpu
 
-CH, BITS, RATE, BLOCK, PER = 2, 16, 44100, 256, 4
-FRAMES = [64, 1, 3, 70, 0]
-SHORT_LAST = {2: 100}  # file 2's last frame has 100 samples
-GUARD = 5  # table entries before the first slice, between two slices and after the last
-NONE = 0xFFFFFFFF
 DEC_RANGE = 7
 U64 = (1 << 64) - 1
 I32, F32, F16, BF16 = range(4)
 PLANAR, PAD = 1, 2
 ESZ = {I32: 4, F32: 4, F16: 2, BF16: 2}
 FORMAT_NAMES = {I32: "i32", F32: "f32", F16: "f16", BF16: "bf16"}
-
-
-def _torch():
-    import torch
-
-    return torch, torch.device("cuda", 0)
-
-
-def _samples(i):
-    n = FRAMES[i] * BLOCK
-    return n - (BLOCK - SHORT_LAST[i]) if i in SHORT_LAST else n
-
-
-def _blocks(i):
-    b = [BLOCK] * FRAMES[i]
-    if i in SHORT_LAST:
-        b[-1] = SHORT_LAST[i]
-    return b
 
 
 # ---- the expectation: PCM bytes -> integers -> elements, by numpy and torch-CPU only ------------
@@ -84,18 +64,6 @@ def elements(x, bits, fmt):
     return torch.from_numpy(np.ascontiguousarray(f32)).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
 
 
-def cover(blocks, start, count):
-    """(first covering frame, covering frames, samples delivered) by a plain loop."""
-    total = sum(blocks)
-    take = min(count, max(total - start, 0))
-    hit, at = [], 0
-    for i, b in enumerate(blocks):
-        if take and at + b > start and at < start + take:
-            hit.append(i)
-        at += b
-    return (hit[0] if hit else 0, len(hit), take)
-
-
 def need(take, count, flags):
     return count if flags & (PLANAR | PAD) else take
 
@@ -110,75 +78,6 @@ def layout(sizes, fmt):
         offs.append(at)
         at += n + 3
     return offs, ((at * ESZ[fmt] + 64) // 16) * 16
-
-
-class Resident:
-    """Streams [(bare frames, bits, rate)] at odd offsets of one device buffer, indexed and their
-    positions scanned once; the tables stay on the device for any number of window calls."""
-
-    def __init__(self, d, streams):
-        import flacgpu
-
-        torch, dev = _torch()
-        self.d, self.n = d, len(streams)
-        blob, self.offs = bytearray(b"\xA5" * 3), []
-        for data, _, _ in streams:
-            if len(blob) % 2 == 0:
-                blob += b"\xA5"
-            self.offs.append(len(blob))
-            blob += data
-        blob += b"\xA5" * 16
-        self.caps = [len(s[0]) // 8 + 1 for s in streams]
-        self.first, at = [], GUARD
-        for c in self.caps:
-            self.first.append(at)
-            at += c + GUARD
-        self.st = torch.cuda.current_stream(dev).cuda_stream
-        self.d_buf = torch.from_numpy(np.frombuffer(bytes(blob), dtype=np.uint8).copy()).to(dev)
-        self.d_off = torch.full((8 * at,), 0xA5, dtype=torch.uint8, device=dev)
-        self.d_fb = torch.full((4 * at,), 0xA5, dtype=torch.uint8, device=dev)
-        self.d_ires = torch.full((16 * self.n,), 0xA5, dtype=torch.uint8, device=dev)
-        self.d_pos = torch.full((8 * at,), 0xA5, dtype=torch.uint8, device=dev)
-        self.d_tot = torch.full((8 * self.n,), 0xA5, dtype=torch.uint8, device=dev)
-        bits, rates = [s[1] for s in streams], [s[2] for s in streams]
-        d.flac_index_streams_device(self.d_buf.data_ptr(), self.offs, [len(s[0]) for s in streams], self.first, self.caps,
-                                    self.d_off.data_ptr(), self.d_fb.data_ptr(), self.d_ires.data_ptr(), stream_bits=bits,
-                                    stream_rates=rates, stream=self.st)
-        d.flac_positions_streams_device(self.d_buf.data_ptr(), self.first, self.caps, self.d_off.data_ptr(),
-                                        self.d_fb.data_ptr(), self.d_ires.data_ptr(), self.d_pos.data_ptr(),
-                                        self.d_tot.data_ptr(), stream_bits=bits, stream_rates=rates, stream=self.st)
-        d.sync_check(self.st)
-        self.index = [(r.status, r.n_frames) for r in
-                      (flacgpu.IndexResult * self.n).from_buffer_copy(self.d_ires.cpu().numpy().tobytes())]
-        self.totals = [int(v) for v in np.frombuffer(self.d_tot.cpu().numpy().tobytes(), dtype=np.uint64)]
-
-    def _call(self, windows, size, call):
-        import flacgpu
-
-        torch, dev = _torch()
-        n = len(windows)
-        d_out = torch.full((size,), 0xA5, dtype=torch.uint8, device=dev)
-        assert d_out.data_ptr() % 16 == 0
-        d_res = torch.full((32 * n,), 0xA5, dtype=torch.uint8, device=dev)
-        call(d_out.data_ptr(), d_res.data_ptr())
-        self.d.sync_check(self.st)
-        res = list((flacgpu.WindowResult * n).from_buffer_copy(d_res.cpu().numpy().tobytes()))
-        return d_out.cpu().numpy().tobytes(), res
-
-    def _tables(self):
-        return (self.d_buf.data_ptr(), self.first, self.d_off.data_ptr(), self.d_fb.data_ptr(), self.d_ires.data_ptr(),
-                self.d_pos.data_ptr(), self.d_tot.data_ptr())
-
-    def deliver(self, windows, fmt, flags, offsets, caps, size):
-        """One flacgpu_decode_windows_device_as call into a 0xA5-filled buffer of `size` bytes ->
-        (the buffer's bytes, [WindowResult]); offsets and caps in elements."""
-        return self._call(windows, size, lambda out, res: self.d.decode_windows_device_as(
-            *self._tables(), windows, fmt, flags, out, offsets, caps, res, stream=self.st))
-
-    def decode(self, windows, offsets, caps, size):
-        """The byte call, flacgpu_decode_windows_device, the same way."""
-        return self._call(windows, size, lambda out, res: self.d.decode_windows_device(
-            *self._tables(), windows, out, offsets, caps, res, stream=self.st))
 
 
 def check_delivery(out, res, windows, blocks_of, ints_of, channels, bits, fmt, flags, offsets, caps, expect_status=None):
@@ -216,43 +115,12 @@ def check_delivery(out, res, windows, blocks_of, ints_of, channels, bits, fmt, f
 
 # ---- the stereo files ----------------------------------------------------------------------------
 @pytest.fixture(scope="module")
-def files():
-    """[(flac file, its PCM)], made once by the encoder on the GPU."""
-    import flacgpu
-
-    pcms = [synth.synth_pcm(_samples(i), CH, BITS, RATE, stream=10 + i) if FRAMES[i] else b"" for i in range(len(FRAMES))]
-    with flacgpu.Encoder(CH, BITS, RATE, device=0, max_frames=128, block_size=BLOCK) as enc:
-        flacs = enc.encode_files(pcms)
-    assert [len(flacgpu.flac_index(f)[2]) for f in flacs] == FRAMES
-    return list(zip(flacs, pcms))
-
-
-@pytest.fixture(scope="module")
 def file_ints(files):
     """The files' samples as int32 [samples, channels]: computed once, shared, never changed."""
     out = {i: ints(pcm, CH, BITS) for i, (_, pcm) in enumerate(files)}
     for v in out.values():
         v.setflags(write=False)
     return out
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import flacgpu
-
-    with flacgpu.Decoder(CH, BITS, RATE, device=0, max_frames=64, block_size=BLOCK) as d:
-        yield d
-
-
-def _bare(flac):
-    import flacgpu
-
-    return flac[flacgpu.flac_index(flac)[1]:]
-
-
-@pytest.fixture(scope="module")
-def resident(ctx, files):
-    return Resident(ctx, [(_bare(f), BITS, RATE) for f, _ in files])
 
 
 def forty_windows():

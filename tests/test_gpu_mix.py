@@ -1,5 +1,5 @@
 """Sample windows delivered with a channel mix on the GPU: flacgpu_decode_windows_device_mix
-(k_window_mix) and FlacMixBank.
+(k_window_elements<true>) and FlacMixBank.
 
 Everything compares bit patterns for equality; there is no tolerance.  The expected elements are
 the generators' own PCM (synth.synth_pcm, the PCM this file builds, frame_grammar.case_pcm) turned
@@ -13,7 +13,7 @@ of the decoder.  Every output buffer is filled with 0xA5 before the call and com
 stray write anywhere fails.  Blocks of 256 (the golden 3-channel file: 4096), files of at most 70
 frames, contexts of 64 frames per call.
 
-Mutation counts (each mutant of k_window_mix / its host side fails tests here): DESIGN.md 7b."""
+Mutation counts (each mutant of k_window_elements<true> / its host side fails tests here): DESIGN.md 7b."""
 import json
 import os
 import random
@@ -29,9 +29,9 @@ import frame_grammar as fg  # noqa: E402
 import oracle_ref  # noqa: E402
 import synth  # noqa: E402
 import test_gpu_deliver as tgd  # noqa: E402
-from test_gpu_deliver import (BF16, BITS, BLOCK, CH, ESZ, F16, F32, FORMAT_NAMES, FRAMES, I32, NONE, PAD, PLANAR, RATE,  # noqa: E402
-                              Resident, cover, elements, ints, layout, need)
-from test_gpu_deliver import ctx, file_ints, files, resident  # noqa: E402,F401  (fixtures: the five stereo 16-bit files)
+from test_gpu_deliver import BF16, ESZ, F16, F32, FORMAT_NAMES, I32, PAD, PLANAR, elements, file_ints, ints, layout, need  # noqa: E402,F401
+from window_helpers import BITS, BLOCK, CH, FRAMES, NONE, RATE, Resident, cover  # noqa: E402
+from window_helpers import ctx, files, resident  # noqa: E402,F401  (fixtures: the five stereo 16-bit files)
 
 pytestmark = pytest.mark.gpu
 

@@ -18,170 +18,14 @@ sys.path.insert(0, os.path.join(HERE, "golden"))
 
 import frame_grammar as fg  # noqa: E402
 import synth  # noqa: E402
+from window_helpers import (BITS, BLOCK, CH, FRAMES, GUARD, NONE, PER, RATE, Resident, _bare, _blocks, _samples,  # noqa: E402
+                            _torch, check_windows, cover, grammar_call, odd_layout)
+from window_helpers import ctx, files, resident  # noqa: E402,F401  (fixtures: the five stereo 16-bit files)
 
 pytestmark = pytest.mark.gpu
 
-CH, BITS, RATE, BLOCK, PER = 2, 16, 44100, 256, 4
-FRAMES = [64, 1, 3, 70, 0]
-SHORT_LAST = {2: 100}  # file 2's last frame has 100 samples
-GUARD = 5  # table entries before the first slice, between two slices and after the last
 FILL64 = 0xA5A5A5A5A5A5A5A5
-NONE = 0xFFFFFFFF
 DEC_RANGE = 7
-
-
-def _torch():
-    import torch
-
-    return torch, torch.device("cuda", 0)
-
-
-def _samples(i):
-    n = FRAMES[i] * BLOCK
-    return n - (BLOCK - SHORT_LAST[i]) if i in SHORT_LAST else n
-
-
-def _blocks(i):
-    b = [BLOCK] * FRAMES[i]
-    if i in SHORT_LAST:
-        b[-1] = SHORT_LAST[i]
-    return b
-
-
-@pytest.fixture(scope="module")
-def files():
-    """[(flac file, its PCM)], made once by the encoder on the GPU."""
-    import flacgpu
-
-    pcms = [synth.synth_pcm(_samples(i), CH, BITS, RATE, stream=10 + i) if FRAMES[i] else b"" for i in range(len(FRAMES))]
-    with flacgpu.Encoder(CH, BITS, RATE, device=0, max_frames=128, block_size=BLOCK) as enc:
-        flacs = enc.encode_files(pcms)
-    assert [len(flacgpu.flac_index(f)[2]) for f in flacs] == FRAMES
-    return list(zip(flacs, pcms))
-
-
-@pytest.fixture(scope="module")
-def ctx():
-    import flacgpu
-
-    with flacgpu.Decoder(CH, BITS, RATE, device=0, max_frames=64, block_size=BLOCK) as d:
-        yield d
-
-
-def _bare(flac):
-    import flacgpu
-
-    return flac[flacgpu.flac_index(flac)[1]:]
-
-
-class Resident:
-    """Streams [(bare frames, bits, rate)] at odd offsets of one device buffer, indexed and their
-    positions scanned once; the tables stay on the device for any number of window calls."""
-
-    def __init__(self, d, streams):
-        import flacgpu
-
-        torch, dev = _torch()
-        self.d, self.n = d, len(streams)
-        blob, self.offs = bytearray(b"\xA5" * 3), []
-        for data, _, _ in streams:
-            if len(blob) % 2 == 0:
-                blob += b"\xA5"
-            self.offs.append(len(blob))
-            blob += data
-        blob += b"\xA5" * 16
-        self.caps = [len(s[0]) // 8 + 1 for s in streams]
-        self.first, at = [], GUARD
-        for c in self.caps:
-            self.first.append(at)
-            at += c + GUARD
-        self.entries = at
-        self.st = torch.cuda.current_stream(dev).cuda_stream
-        self.d_buf = torch.from_numpy(np.frombuffer(bytes(blob), dtype=np.uint8).copy()).to(dev)
-        self.d_off = torch.full((8 * at,), 0xA5, dtype=torch.uint8, device=dev)
-        self.d_fb = torch.full((4 * at,), 0xA5, dtype=torch.uint8, device=dev)
-        self.d_ires = torch.full((16 * self.n,), 0xA5, dtype=torch.uint8, device=dev)
-        self.d_pos = torch.full((8 * at,), 0xA5, dtype=torch.uint8, device=dev)  # poisoned
-        self.d_tot = torch.full((8 * self.n,), 0xA5, dtype=torch.uint8, device=dev)
-        bits, rates = [s[1] for s in streams], [s[2] for s in streams]
-        d.flac_index_streams_device(self.d_buf.data_ptr(), self.offs, [len(s[0]) for s in streams], self.first, self.caps,
-                                    self.d_off.data_ptr(), self.d_fb.data_ptr(), self.d_ires.data_ptr(), stream_bits=bits,
-                                    stream_rates=rates, stream=self.st)
-        d.flac_positions_streams_device(self.d_buf.data_ptr(), self.first, self.caps, self.d_off.data_ptr(),
-                                        self.d_fb.data_ptr(), self.d_ires.data_ptr(), self.d_pos.data_ptr(),
-                                        self.d_tot.data_ptr(), stream_bits=bits, stream_rates=rates, stream=self.st)
-        d.sync_check(self.st)
-        self.index = [(r.status, r.n_frames) for r in
-                      (flacgpu.IndexResult * self.n).from_buffer_copy(self.d_ires.cpu().numpy().tobytes())]
-        self.pos = np.frombuffer(self.d_pos.cpu().numpy().tobytes(), dtype=np.uint64)
-        self.totals = [int(v) for v in np.frombuffer(self.d_tot.cpu().numpy().tobytes(), dtype=np.uint64)]
-
-    def positions(self, s):
-        return [int(v) for v in self.pos[self.first[s]:self.first[s] + self.index[s][1]]]
-
-    def decode(self, windows, offsets, caps, size):
-        """One flacgpu_decode_windows_device call into a 0xA5-filled buffer of `size` bytes ->
-        (the buffer's bytes, [WindowResult])."""
-        import flacgpu
-
-        torch, dev = _torch()
-        n = len(windows)
-        d_out = torch.full((size,), 0xA5, dtype=torch.uint8, device=dev)
-        assert d_out.data_ptr() % 16 == 0
-        d_res = torch.full((32 * n,), 0xA5, dtype=torch.uint8, device=dev)
-        self.d.decode_windows_device(self.d_buf.data_ptr(), self.first, self.d_off.data_ptr(), self.d_fb.data_ptr(),
-                                     self.d_ires.data_ptr(), self.d_pos.data_ptr(), self.d_tot.data_ptr(), windows,
-                                     d_out.data_ptr(), offsets, caps, d_res.data_ptr(), stream=self.st)
-        self.d.sync_check(self.st)
-        res = list((flacgpu.WindowResult * n).from_buffer_copy(d_res.cpu().numpy().tobytes()))
-        return d_out.cpu().numpy().tobytes(), res
-
-
-def cover(blocks, start, count):
-    """(first covering frame, covering frames, samples delivered) by a plain loop."""
-    total = sum(blocks)
-    take = min(count, max(total - start, 0))
-    hit, at = [], 0
-    for i, b in enumerate(blocks):
-        if take and at + b > start and at < start + take:
-            hit.append(i)
-        at += b
-    return (hit[0] if hit else 0, len(hit), take)
-
-
-def odd_layout(sizes, gaps=(7, 9, 13, 3, 11, 5, 15, 1)):
-    """Regions of the given sizes at odd offsets with odd gaps between them -> ([offset], total)."""
-    offs, at = [], 1
-    for k, n in enumerate(sizes):
-        if at % 2 == 0:
-            at += 1
-        offs.append(at)
-        at += n + gaps[k % len(gaps)]
-    return offs, at + 16
-
-
-def check_windows(out, res, windows, blocks_of, pcm_of, per, offsets, caps, expect_status=None):
-    """Every result and every byte of the output buffer, for windows whose expected status is OK
-    but for those in expect_status {window: (status, first_bad_frame, first_bad_status)}."""
-    expect_status = expect_status or {}
-    want = bytearray(b"\xA5" * len(out))
-    for w, ((s, start, count), r) in enumerate(zip(windows, res)):
-        first, frames, take = cover(blocks_of[s], start, count)
-        if w in expect_status:
-            st, bad, bad_st = expect_status[w]
-            assert (r.status, r.n_samples, r.first_bad_frame, r.first_bad_status) == (st, 0, bad, bad_st), w
-            continue
-        assert (r.status, r.n_samples, r.n_frames, r.first_bad_frame, r.first_bad_status) == (0, take, frames, NONE, 0), w
-        if frames:
-            assert r.first_frame == first, w
-        assert take * per <= caps[w]
-        want[offsets[w]:offsets[w] + take * per] = pcm_of[s][start * per:(start + take) * per]
-    assert out == bytes(want)  # the delivered bytes, and 0xA5 everywhere else
-
-
-@pytest.fixture(scope="module")
-def resident(ctx, files):
-    return Resident(ctx, [(_bare(f), BITS, RATE) for f, _ in files])
 
 
 def test_positions_are_the_prefix_sums(resident):
@@ -263,25 +107,6 @@ def _case(name):
     return next(c for c in fg.cases() if c["name"] == name)
 
 
-def _grammar_call(c, windows, offsets_of, block_size=4096, expect_status=None):
-    """The grammar case as the one stream of a context of its own; windows [(0, start, count)]."""
-    import flacgpu
-
-    per = c["channels"] * (c["bits"] // 8)
-    blocks = [f["block"] for f in c["frames"]]
-    with flacgpu.Decoder(c["channels"], c["bits"], c["rate"], device=0, max_frames=64, block_size=block_size) as d:
-        r = Resident(d, [(fg.case_bytes(c), c["bits"], c["rate"])])
-        assert r.index == [(0, len(blocks))] and r.totals == [sum(blocks)]
-        assert r.positions(0) == [sum(blocks[:k]) for k in range(len(blocks))]
-        sizes = [cover(blocks, s, n)[2] * per for _, s, n in windows]
-        offs, size = offsets_of(sizes)
-        out, res = r.decode(windows, offs, sizes, size)
-    if expect_status is None:
-        assert [x.status for x in res] == [0] * len(windows)
-    check_windows(out, res, windows, {0: blocks}, {0: fg.case_pcm(c)}, per, offs, sizes, expect_status=expect_status)
-    return res
-
-
 def test_alignment_sweep_mono_8_bit():
     """per = 1: a window for every (source mod 16, destination mod 16) pair at lengths 1, 15, 16, 17
     and 47.  The source of a copy starts `skip` bytes into 16-byte aligned scratch, and skip = start
@@ -297,19 +122,19 @@ def test_alignment_sweep_mono_8_bit():
                 windows.append((0, start, n))
                 dst.append(64 * len(dst) + da)
     assert len(windows) == 1280 and any(s + n > 1152 for _, s, n in windows)
-    _grammar_call(c, windows, lambda sizes: (dst, 64 * len(dst) + 64))
+    grammar_call(c, windows, lambda sizes: (dst, 64 * len(dst) + 64))
 
 
 def test_24_bit_mono():
     c = _case("waste_and_unary")  # blocks 128, 192, 1152, 256, 100; per = 3
     windows = [(0, 0, 1828), (0, 127, 2), (0, 5, 7), (0, 319, 1153), (0, 1700, 500), (0, 1471, 2), (0, 1828, 3)]
-    _grammar_call(c, windows, odd_layout)
+    grammar_call(c, windows, odd_layout)
 
 
 def test_eight_channels_32_bit():
     c = _case("eight_by_32")  # blocks 1000, 4096, 17; per = 32: a checking and a writing pass of two rounds
     windows = [(0, 999, 2), (0, 0, 5113), (0, 5095, 100), (0, 1003, 10), (0, 3, 1)]
-    _grammar_call(c, windows, odd_layout)
+    grammar_call(c, windows, odd_layout)
 
 
 def test_frames_outside_a_window_are_not_decoded():
@@ -319,7 +144,7 @@ def test_frames_outside_a_window_are_not_decoded():
     c = _case("waste_and_unary")
     assert [f["block"] for f in c["frames"]] == [128, 192, 1152, 256, 100]
     windows = [(0, 100, 220), (0, 1482, 300), (0, 300, 100), (0, 320, 1), (0, 1471, 1), (0, 1472, 356)]
-    res = _grammar_call(c, windows, odd_layout, block_size=256,
+    res = grammar_call(c, windows, odd_layout, block_size=256,
                         expect_status={2: (2, 2, DEC_RANGE), 3: (2, 2, DEC_RANGE), 4: (2, 2, DEC_RANGE)})
     assert [r.status for r in res] == [0, 0, 2, 2, 2, 0]
     assert (res[0].first_frame, res[0].n_frames) == (0, 2) and (res[1].first_frame, res[1].n_frames) == (3, 2)

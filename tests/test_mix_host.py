@@ -8,7 +8,7 @@ sum -> f32, times the power of two; f16) and torch on the CPU (bf16): all pairs 
 and per depth a directed set (the limits, 24-bit pairs summing to +-2^24, 32-bit sums on and next
 to the ties of the 64-bit -> f32 rounding around every power of two from 2^24 to 2^34, sums whose
 f16 result is subnormal) plus 10^5 seeded random tuples; m = 1 against element() and m = 0 against
-0 inside the program.  `rows`: the destination rows of a tile, filled by their plans, against the
+0 inside the program.  `rows`: the destination rows of a tile, filled by the kernel's own fill_row_slot, against the
 rule element by element in a guarded buffer.  Bit patterns are compared; no tolerance."""
 import json
 import os

@@ -61,6 +61,7 @@ mix rounds the exact sum once and torch rounds each channel's element and then t
     python tools/decode_rate.py --legs mix --mix-out profiles/decode_mix_rate.json
 """
 import argparse
+import contextlib
 import ctypes
 import json
 import os
@@ -389,7 +390,14 @@ def files_rate(n_files: int, frames_each: int, warmup: int, repeats: int) -> dic
     return res
 
 
-def windows_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: int) -> dict:
+@contextlib.contextmanager
+def resident_windows(n_files: int, frames_each: int, window: int):
+    """The resident set of the windows, deliver and mix legs: n_files C2 files of frames_each frames
+    encoded on the GPU, their frames in one HBM buffer at 64-byte offsets and indexed once, and one
+    window of `window` samples per file from a start that is no multiple of the block size.  The
+    positions are the caller's to queue (r.positions()): the windows leg times them."""
+    from types import SimpleNamespace
+
     import numpy as np
     import torch
 
@@ -404,12 +412,9 @@ def windows_rate(n_files: int, frames_each: int, window: int, warmup: int, repea
     pcm = (unit * ((frames_each + 63) // 64))[: n_each * per]
     start = (n_each // 3 // 4096) * 4096 + 1234  # not a multiple of the block size
     assert start % 4096 and start + window <= n_each
-    want = pcm[start * per:(start + window) * per]
-    L = flacgpu.load_library()
     with flacgpu.Encoder(ch, bits, rate, device=0, max_frames=n_files * frames_each) as enc:
         flacs = enc.encode_files([pcm] * n_files)
         first = flacgpu.flac_index(flacs[0])[1]
-        # ---- resident: the files' frames in one HBM buffer, indexed and scanned once ----
         bodies = [f[first:] for f in flacs]
         offs, at = [], 0
         for b in bodies:
@@ -428,9 +433,6 @@ def windows_rate(n_files: int, frames_each: int, window: int, warmup: int, repea
         d_tot = torch.zeros(n_files, dtype=torch.int64, device=dev)
         d_ir = torch.zeros(16 * n_files, dtype=torch.uint8, device=dev)
         d_wres = torch.zeros(32 * n_files, dtype=torch.uint8, device=dev)
-        d_sres = torch.zeros(32 * n_files, dtype=torch.uint8, device=dev)
-        d_win = torch.zeros(n_files * window * per, dtype=torch.uint8, device=dev)
-        d_all = torch.zeros(n_files * len(pcm), dtype=torch.uint8, device=dev)
         st = torch.cuda.current_stream(dev).cuda_stream
         sbits, srates = [bits] * n_files, [rate] * n_files
         enc.flac_index_streams_device(d_buf.data_ptr(), offs, lens, tfirst, caps, d_off.data_ptr(), d_fb.data_ptr(),
@@ -441,34 +443,59 @@ def windows_rate(n_files: int, frames_each: int, window: int, warmup: int, repea
                                               d_ir.data_ptr(), d_pos.data_ptr(), d_tot.data_ptr(), stream_bits=sbits,
                                               stream_rates=srates, stream=st)
 
-        crops = [(i, start, window) for i in range(n_files)]
+        def results():
+            """[(status, n_samples)] of the last window call."""
+            raw = d_wres.cpu().numpy().tobytes()
+            return [(r.status, r.n_samples) for r in (flacgpu.WindowResult * n_files).from_buffer_copy(raw)]
+
+        yield SimpleNamespace(
+            enc=enc, ch=ch, bits=bits, rate=rate, per=per, dev=dev, pcm=pcm, n_each=n_each, start=start, flacs=flacs, offs=offs,
+            lens=lens, d_buf=d_buf, d_wres=d_wres, st=st, sbits=sbits, srates=srates, positions=positions, results=results,
+            tables=(d_buf.data_ptr(), tfirst, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(), d_pos.data_ptr(),
+                    d_tot.data_ptr()),
+            crops=[(i, start, window) for i in range(n_files)])
+
+
+def event_ms(fn):
+    """fn's time on the current stream between two HIP events."""
+    import torch
+
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def summary(ms, keep=False):
+    res = {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
+    return dict(res, ms=ms) if keep else res
+
+
+def windows_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: int) -> dict:
+    import torch
+
+    import flacgpu
+
+    L = flacgpu.load_library()
+    with resident_windows(n_files, frames_each, window) as r:
+        enc, per, pcm, n_each, start, st, flacs, crops = r.enc, r.per, r.pcm, r.n_each, r.start, r.st, r.flacs, r.crops
+        ch, bits, lens, positions, window_results = r.ch, r.bits, r.lens, r.positions, r.results
+        want = pcm[start * per:(start + window) * per]
+        d_sres = torch.zeros(32 * n_files, dtype=torch.uint8, device=r.dev)
+        d_win = torch.zeros(n_files * window * per, dtype=torch.uint8, device=r.dev)
+        d_all = torch.zeros(n_files * len(pcm), dtype=torch.uint8, device=r.dev)
         crop_offs, crop_caps = [i * window * per for i in range(n_files)], [window * per] * n_files
         wholes = [(i, 0, n_each) for i in range(n_files)]
         whole_offs, whole_caps = [i * len(pcm) for i in range(n_files)], [len(pcm)] * n_files
 
         def windows(wins, w_offs, w_caps, d_out):
-            enc.decode_windows_device(d_buf.data_ptr(), tfirst, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(),
-                                      d_pos.data_ptr(), d_tot.data_ptr(), wins, d_out.data_ptr(), w_offs, w_caps,
-                                      d_wres.data_ptr(), stream=st)
+            enc.decode_windows_device(*r.tables, wins, d_out.data_ptr(), w_offs, w_caps, r.d_wres.data_ptr(), stream=st)
 
         def streams():
-            enc.decode_streams_device(d_buf.data_ptr(), offs, lens, d_all.data_ptr(), whole_offs, whole_caps,
-                                      d_sres.data_ptr(), stream_bits=sbits, stream_rates=srates, stream=st)
-
-        def event_ms(fn):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            return a.elapsed_time(b)
-
-        def summary(ms):
-            return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
-
-        def window_results():
-            raw = d_wres.cpu().numpy().tobytes()
-            return [(r.status, r.n_samples) for r in (flacgpu.WindowResult * n_files).from_buffer_copy(raw)]
+            enc.decode_streams_device(r.d_buf.data_ptr(), r.offs, lens, d_all.data_ptr(), whole_offs, whole_caps,
+                                      d_sres.data_ptr(), stream_bits=r.sbits, stream_rates=r.srates, stream=st)
 
         for _ in range(warmup):
             positions()
@@ -561,44 +588,11 @@ def deliver_rate(n_files: int, frames_each: int, window: int, warmup: int, repea
     import torch
 
     import flacgpu
-    import synth
 
-    ch, bits, rate, _ = PRESETS["c2"]
-    per = ch * (bits // 8)
-    dev = torch.device("cuda", 0)
-    unit = synth.synth_pcm(64 * 4096, ch, bits, rate)
-    n_each = frames_each * 4096
-    pcm = (unit * ((frames_each + 63) // 64))[: n_each * per]
-    start = (n_each // 3 // 4096) * 4096 + 1234  # not a multiple of the block size
-    assert start % 4096 and start + window <= n_each
-    with flacgpu.Encoder(ch, bits, rate, device=0, max_frames=n_files * frames_each) as enc:
-        flacs = enc.encode_files([pcm] * n_files)
-        first = flacgpu.flac_index(flacs[0])[1]
-        bodies = [f[first:] for f in flacs]
-        offs, at = [], 0
-        for b in bodies:
-            offs.append(at)
-            at += (len(b) + 63) & ~63
-        host = np.zeros(at + 16, dtype=np.uint8)
-        for o, b in zip(offs, bodies):
-            host[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
-        d_buf = torch.from_numpy(host).to(dev)
-        lens = [len(b) for b in bodies]
-        caps = [n // 8 + 1 for n in lens]
-        tfirst = [int(v) for v in np.cumsum([0] + caps)[:-1]]
-        d_off = torch.zeros(sum(caps), dtype=torch.int64, device=dev)
-        d_fb = torch.zeros(sum(caps), dtype=torch.int32, device=dev)
-        d_pos = torch.zeros(sum(caps), dtype=torch.int64, device=dev)
-        d_tot = torch.zeros(n_files, dtype=torch.int64, device=dev)
-        d_ir = torch.zeros(16 * n_files, dtype=torch.uint8, device=dev)
-        d_wres = torch.zeros(32 * n_files, dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        sbits, srates = [bits] * n_files, [rate] * n_files
-        enc.flac_index_streams_device(d_buf.data_ptr(), offs, lens, tfirst, caps, d_off.data_ptr(), d_fb.data_ptr(),
-                                      d_ir.data_ptr(), stream_bits=sbits, stream_rates=srates, stream=st)
-        enc.flac_positions_streams_device(d_buf.data_ptr(), tfirst, caps, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(),
-                                          d_pos.data_ptr(), d_tot.data_ptr(), stream_bits=sbits, stream_rates=srates, stream=st)
-        tables = (d_buf.data_ptr(), tfirst, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(), d_pos.data_ptr(), d_tot.data_ptr())
+    with resident_windows(n_files, frames_each, window) as r:
+        enc, ch, bits, per, dev, pcm, n_each, st, crops = r.enc, r.ch, r.bits, r.per, r.dev, r.pcm, r.n_each, r.st, r.crops
+        tables, d_wres, start = r.tables, r.d_wres, r.start
+        r.positions()
         planar_pad = flacgpu.DELIVER_PLANAR | flacgpu.DELIVER_PAD
 
         def deliver(wins, fmt, x):
@@ -617,22 +611,9 @@ def deliver_rate(n_files: int, frames_each: int, window: int, warmup: int, repea
             x = d_out.view(torch.int16).view(len(wins), wins[0][2], ch).to(torch.float32) * (2.0 ** -(bits - 1))
             return x.to(dtype).transpose(1, 2).contiguous()
 
-        def event_ms(fn):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            return a.elapsed_time(b)
-
-        def summary(ms):
-            return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms)}
-
         def all_ok(n):
-            raw = d_wres.cpu().numpy().tobytes()
-            return [(r.status, r.n_samples) for r in (flacgpu.WindowResult * n_files).from_buffer_copy(raw)] == [(0, n)] * n_files
+            return r.results() == [(0, n)] * n_files
 
-        crops = [(i, start, window) for i in range(n_files)]
         d_win = torch.zeros(n_files * window * per, dtype=torch.uint8, device=dev)
         x32 = torch.zeros((n_files, ch, window), dtype=torch.float32, device=dev)
         x16 = torch.zeros((n_files, ch, window), dtype=torch.bfloat16, device=dev)
@@ -697,46 +678,12 @@ def mix_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: 
     import torch
 
     import flacgpu
-    import synth
 
-    ch, bits, rate, _ = PRESETS["c2"]
-    per = ch * (bits // 8)
-    dev = torch.device("cuda", 0)
-    unit = synth.synth_pcm(64 * 4096, ch, bits, rate)
-    n_each = frames_each * 4096
-    pcm = (unit * ((frames_each + 63) // 64))[: n_each * per]
-    start = (n_each // 3 // 4096) * 4096 + 1234  # not a multiple of the block size
-    assert start % 4096 and start + window <= n_each
-    with flacgpu.Encoder(ch, bits, rate, device=0, max_frames=n_files * frames_each) as enc:
-        flacs = enc.encode_files([pcm] * n_files)
-        first = flacgpu.flac_index(flacs[0])[1]
-        bodies = [f[first:] for f in flacs]
-        offs, at = [], 0
-        for b in bodies:
-            offs.append(at)
-            at += (len(b) + 63) & ~63
-        host = np.zeros(at + 16, dtype=np.uint8)
-        for o, b in zip(offs, bodies):
-            host[o:o + len(b)] = np.frombuffer(b, dtype=np.uint8)
-        d_buf = torch.from_numpy(host).to(dev)
-        lens = [len(b) for b in bodies]
-        caps = [n // 8 + 1 for n in lens]
-        tfirst = [int(v) for v in np.cumsum([0] + caps)[:-1]]
-        d_off = torch.zeros(sum(caps), dtype=torch.int64, device=dev)
-        d_fb = torch.zeros(sum(caps), dtype=torch.int32, device=dev)
-        d_pos = torch.zeros(sum(caps), dtype=torch.int64, device=dev)
-        d_tot = torch.zeros(n_files, dtype=torch.int64, device=dev)
-        d_ir = torch.zeros(16 * n_files, dtype=torch.uint8, device=dev)
-        d_wres = torch.zeros(32 * n_files, dtype=torch.uint8, device=dev)
-        st = torch.cuda.current_stream(dev).cuda_stream
-        sbits, srates = [bits] * n_files, [rate] * n_files
-        enc.flac_index_streams_device(d_buf.data_ptr(), offs, lens, tfirst, caps, d_off.data_ptr(), d_fb.data_ptr(),
-                                      d_ir.data_ptr(), stream_bits=sbits, stream_rates=srates, stream=st)
-        enc.flac_positions_streams_device(d_buf.data_ptr(), tfirst, caps, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(),
-                                          d_pos.data_ptr(), d_tot.data_ptr(), stream_bits=sbits, stream_rates=srates, stream=st)
-        tables = (d_buf.data_ptr(), tfirst, d_off.data_ptr(), d_fb.data_ptr(), d_ir.data_ptr(), d_pos.data_ptr(), d_tot.data_ptr())
+    with resident_windows(n_files, frames_each, window) as r:
+        enc, ch, bits, per, dev, pcm, n_each, st, crops = r.enc, r.ch, r.bits, r.per, r.dev, r.pcm, r.n_each, r.st, r.crops
+        tables, d_wres, start = r.tables, r.d_wres, r.start
+        r.positions()
         planar_pad = flacgpu.DELIVER_PLANAR | flacgpu.DELIVER_PAD
-        crops = [(i, start, window) for i in range(n_files)]
         x_mix = torch.zeros((n_files, 1, window), dtype=torch.float32, device=dev)
         x_as = torch.zeros((n_files, ch, window), dtype=torch.float32, device=dev)
 
@@ -751,20 +698,8 @@ def mix_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: 
                                          stream=st)
             return x_as.mean(dim=1, keepdim=True)
 
-        def event_ms(fn):
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            return a.elapsed_time(b)
-
-        def summary(ms):
-            return {"ms_median": statistics.median(ms), "ms_min": min(ms), "ms_max": max(ms), "ms": ms}
-
         def all_ok():
-            raw = d_wres.cpu().numpy().tobytes()
-            return [(r.status, r.n_samples) for r in (flacgpu.WindowResult * n_files).from_buffer_copy(raw)] == [(0, window)] * n_files
+            return r.results() == [(0, window)] * n_files
 
         legs = {"mix_f32": mix, "as_f32_then_mean": as_then_mean}
         for _ in range(warmup):
@@ -787,7 +722,7 @@ def mix_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: 
                "layout": "f32, planar, padded", "warmup": warmup, "repeats": repeats,
                "elements_that_differ_from_torch_mean": int((got != other).sum()), "elements": got.numel()}
         for k in legs:
-            res[k] = summary(ms[k])
+            res[k] = summary(ms[k], keep=True)
         res["mix_f32"]["x_as_then_mean"] = res["as_f32_then_mean"]["ms_median"] / res["mix_f32"]["ms_median"]
     return res
 

@@ -191,12 +191,10 @@ hipError_t launch_window_init(const window::Cover *recs, streams::StreamResult *
 hipError_t launch_window_copy(const window::Cover *recs, const streams::StreamResult *res, const uint8_t *scratch,
                               const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off, uint32_t per, uint32_t n,
                               uint64_t max_bytes, hipStream_t st);
-hipError_t launch_window_deliver(const window::Cover *recs, const streams::StreamResult *res, const window::WindowArg *args,
-                                 const uint8_t *scratch, const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off,
-                                 const deliver::Delivery &dv, uint32_t n, uint64_t max_samples, hipStream_t st);
-hipError_t launch_window_mix(const window::Cover *recs, const streams::StreamResult *res, const window::WindowArg *args,
-                             const uint8_t *scratch, const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off,
-                             const deliver::Delivery &dv, uint32_t n, uint64_t max_samples, hipStream_t st);
+// k_window_elements<dv.mix>: the delivery as tensor elements, with a channel mix or without
+hipError_t launch_window_elements(const window::Cover *recs, const streams::StreamResult *res, const window::WindowArg *args,
+                                  const uint8_t *scratch, const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off,
+                                  const deliver::Delivery &dv, uint32_t n, uint64_t max_samples, hipStream_t st);
 hipError_t launch_window_results(const window::Cover *recs, const streams::StreamResult *res, window::WindowResult *out,
                                  uint32_t n, hipStream_t st);
 // fg_misc.hip

@@ -263,6 +263,9 @@ int index_streams_core(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const 
     return FLACGPU_OK;
 }
 
+// the table entries a stream of len bytes can need: a frame is at least 9 bytes
+inline uint64_t table_cap_for(uint64_t len) { return len / 8u + 1u; }
+
 bool streams_args_ok(uint32_t n, const uint64_t *lens) {
     if (n > idx::kIdxMaxStreams) return false;
     for (uint32_t s = 0; s < n; s++)
@@ -271,7 +274,7 @@ bool streams_args_ok(uint32_t n, const uint64_t *lens) {
 }
 
 // The frame tables of a many-streams decode, in the context's index scratch: stream s owns
-// lens[s] / 8 + 1 entries (a frame is at least 9 bytes) from first[s].
+// table_cap_for(lens[s]) entries from first[s].
 struct StreamTables {
     std::vector<uint64_t> first, caps;
     uint64_t *f_off = nullptr;
@@ -296,7 +299,7 @@ int streams_index(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const uint6
     }
     for (uint32_t s = 0; s < n; s++) {
         tb.first[s] = total;
-        tb.caps[s] = lens[s] / 8u + 1u;
+        tb.caps[s] = table_cap_for(lens[s]);
         total += tb.caps[s];
     }
     auto table = [&](uint8_t *base) {
@@ -315,69 +318,103 @@ int streams_index(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const uint6
     return FLACGPU_OK;
 }
 
+// What a many-streams decode and a window decode share once every stream s < n -- a stream, or the
+// covering frames of a window -- has its frame count.  prepare() cuts frames[] into segments and
+// chunks of max_frames frames, carves the packed frame table, the meta rows, `carried`, whatever
+// `extra` takes and the segments out of buf (grown, after a wait for st where it must), and uploads
+// `host` -- rows of n values: row 0 the PCM bases, 1 the PCM caps, 2 the first table entries, the
+// rest the caller's -- and the segments.  The caller's init kernel goes between the two steps.
+// run() packs the frame tables and puts every chunk through parse, segment offsets, reconstruct
+// and fold.  Both only queue.
+struct ChunkRun {
+    std::vector<streams::Segment> segs;
+    std::vector<uint32_t> chunk_seg;
+    uint32_t n = 0;
+    uint64_t *p_off = nullptr, *meta = nullptr, *carried = nullptr;
+    uint32_t *p_bytes = nullptr;
+    streams::Segment *d_segs = nullptr;
+
+    uint64_t *row(uint32_t r) const { return meta + (uint64_t)r * n; }
+
+    template <class Extra>
+    int prepare(flacgpu_ctx *c, const std::vector<uint64_t> &frames, const std::vector<uint64_t> &host, uint8_t *&buf,
+                uint64_t &cap, Extra extra, hipStream_t st) {
+        n = (uint32_t)frames.size();
+        try {
+            streams::cut_segments(frames, c->max_frames, segs, chunk_seg);
+        } catch (...) {
+            return FLACGPU_ERR_OUT_OF_MEMORY;
+        }
+        const uint64_t n_packed = (uint64_t)(chunk_seg.empty() ? 0u : chunk_seg.size() - 1u) * c->max_frames;
+        auto carve = [&](uint8_t *base) {
+            Carve v{base};
+            v.take(n_packed, p_off);
+            v.take(host.size(), meta);  // one upload
+            v.take(n, carried);
+            extra(v);
+            v.take(segs.size(), d_segs);
+            return v.take(n_packed, p_bytes);
+        };
+        HIPCHK(grow(buf, cap, carve(nullptr), &st));
+        carve(buf);
+        HIPCHK(hipMemcpyAsync(meta, host.data(), host.size() * 8u, hipMemcpyHostToDevice, st));
+        if (!segs.empty())
+            HIPCHK(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(streams::Segment), hipMemcpyHostToDevice, st));
+        return FLACGPU_OK;
+    }
+
+    // the frames of d_data by the tables f_off / f_bytes into d_out, of which `whole` bytes are the
+    // capacity k_dec_recon checks: the end of the last region
+    int run(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *f_off, const uint32_t *f_bytes, uint8_t *d_out,
+            uint64_t whole, streams::StreamResult *res, hipStream_t st) const {
+        HIPCHK(launch_streams_gather(d_segs, (uint32_t)segs.size(), row(2), f_off, f_bytes, p_off, p_bytes, st));
+        for (uint32_t k = 0; k + 1u < chunk_seg.size(); k++) {
+            const uint32_t s0 = chunk_seg[k], s1 = chunk_seg[k + 1u];
+            const uint32_t nf = segs[s1 - 1u].first + segs[s1 - 1u].count;
+            const ChunkStreams cs{d_segs + s0, s1 - s0, row(0), row(1), carried, res};
+            const int rc = dec_core(c, d_data, p_off + (uint64_t)k * c->max_frames, p_bytes + (uint64_t)k * c->max_frames, nf,
+                                    nullptr, d_out, whole, nullptr, false, (flacgpu_decode_result *)c->dec->d_results, nullptr,
+                                    st, &cs);
+            if (rc) return rc;
+        }
+        return FLACGPU_OK;
+    }
+};
+
 // Everything after the index of a many-streams decode, only queued: the streams' results set up,
-// the frame tables of the OK streams packed, every chunk of max_frames frames through parse,
-// segment offsets, reconstruct and fold, then (d_md5) one batched MD5 over the decoded regions.
+// the frame tables of the OK streams packed and every chunk decoded (ChunkRun), then (d_md5) one
+// batched MD5 over the decoded regions.
 int streams_decode(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const StreamTables &tb,
                    const std::vector<idx::IndexResult> &ires, uint8_t *d_pcm_out, const uint64_t *pcm_offsets,
                    const uint64_t *pcm_caps, streams::StreamResult *d_results, uint8_t *d_md5, hipStream_t st) {
-    DecScratch *d = c->dec;
-    IdxScratch *x = c->idx;
     std::vector<uint64_t> frames, host;
-    std::vector<streams::Segment> segs;
-    std::vector<uint32_t> chunk_seg;
-    uint64_t whole = 0;  // the capacity k_dec_recon checks: the end of the last region
+    uint64_t whole = 0;
     try {
         frames.assign(n, 0);
-        for (uint32_t s = 0; s < n; s++) {
-            if (ires[s].status == idx::IDX_OK && ires[s].n_frames <= tb.caps[s]) frames[s] = ires[s].n_frames;
-            whole = std::max(whole, pcm_offsets[s] + pcm_caps[s]);
-        }
-        streams::cut_segments(frames, c->max_frames, segs, chunk_seg);
         host.resize(3u * (uint64_t)n);
     } catch (...) {
         return FLACGPU_ERR_OUT_OF_MEMORY;
     }
-    const uint32_t n_chunks = chunk_seg.empty() ? 0u : (uint32_t)chunk_seg.size() - 1u;
-    const uint64_t n_packed = (uint64_t)n_chunks * c->max_frames;
-    uint64_t *p_off = nullptr, *meta = nullptr, *carried = nullptr, *md5_lens = nullptr;
-    uint32_t *p_bytes = nullptr;
-    streams::Segment *d_segs = nullptr;
-    auto carve = [&](uint8_t *base) {
-        Carve v{base};
-        v.take(n_packed, p_off);
-        v.take(3u * (uint64_t)n, meta);  // pcm base, pcm cap, table first: one upload
-        v.take(n, carried, md5_lens);
-        v.take(segs.size(), d_segs);
-        return v.take(n_packed, p_bytes);
-    };
-    HIPCHK(grow(x->packed, x->packed_cap, carve(nullptr), &st));
-    carve(x->packed);
-    uint64_t *d_base = meta, *d_cap = meta + n, *d_first = meta + 2u * (uint64_t)n;
     for (uint32_t s = 0; s < n; s++) {
+        if (ires[s].status == idx::IDX_OK && ires[s].n_frames <= tb.caps[s]) frames[s] = ires[s].n_frames;
+        whole = std::max(whole, pcm_offsets[s] + pcm_caps[s]);
         host[s] = pcm_offsets[s];
         host[n + s] = pcm_caps[s];
         host[2u * (uint64_t)n + s] = tb.first[s];
     }
-    HIPCHK(hipMemcpyAsync(meta, host.data(), host.size() * 8u, hipMemcpyHostToDevice, st));
-    if (!segs.empty())
-        HIPCHK(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(streams::Segment), hipMemcpyHostToDevice, st));
-    HIPCHK(launch_streams_init(tb.d_ires, d_results, carried, n, st));
-    HIPCHK(launch_streams_gather(d_segs, (uint32_t)segs.size(), d_first, tb.f_off, tb.f_bytes, p_off, p_bytes, st));
-    for (uint32_t k = 0; k < n_chunks; k++) {
-        const uint32_t s0 = chunk_seg[k], s1 = chunk_seg[k + 1u];
-        const uint32_t nf = segs[s1 - 1u].first + segs[s1 - 1u].count;
-        const ChunkStreams cs{d_segs + s0, s1 - s0, d_base, d_cap, carried, d_results};
-        const int rc = dec_core(c, d_data, p_off + (uint64_t)k * c->max_frames, p_bytes + (uint64_t)k * c->max_frames, nf,
-                                nullptr, d_pcm_out, whole, nullptr, false, (flacgpu_decode_result *)d->d_results, nullptr,
-                                st, &cs);
-        if (rc) return rc;
-    }
+    ChunkRun run;
+    uint64_t *md5_lens = nullptr;
+    int rc = run.prepare(c, frames, host, c->idx->packed, c->idx->packed_cap, [&](Carve &v) { v.take(n, md5_lens); }, st);
+    if (rc) return rc;
+    HIPCHK(launch_streams_init(tb.d_ires, d_results, run.carried, n, st));
+    rc = run.run(c, d_data, tb.f_off, tb.f_bytes, d_pcm_out, whole, d_results, st);
+    if (rc) return rc;
     if (d_md5) {
         HIPCHK(launch_streams_md5_lens(d_results, c->g.C * (c->g.bits / 8u), md5_lens, n, st));
         {
             Timed t(c, FLACGPU_K_MD5, st);
-            HIPCHK(launch_md5_streams(d_pcm_out, d_base, md5_lens, nullptr, n, nullptr, d_md5, st, c->g.md5_kernel, c->k.md5_prio));
+            HIPCHK(launch_md5_streams(d_pcm_out, run.row(0), md5_lens, nullptr, n, nullptr, d_md5, st, c->g.md5_kernel,
+                                      c->k.md5_prio));
         }
         HIPCHK(launch_streams_md5_mask(d_results, d_md5, n, st));
     }
@@ -456,88 +493,83 @@ int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexR
 }
 
 // The second half, only queued.  Every window plays the role a stream plays in streams_decode: its
-// covering frames are its frames, cut with all the others' into chunks of max_frames; its PCM
-// region is span * per bytes of the context's window scratch (bases 16-byte aligned); its result is
-// a scratch StreamResult.  After the last chunk k_window_copy moves each clean window's bytes to
-// d_pcm_out + out_offsets[w] -- or, where dv converts, k_window_deliver (k_window_mix where dv
-// mixes: dv.out_channels channels a sample) writes its elements from element out_offsets[w] of
-// d_pcm_out on -- and k_window_results writes d_results.
+// covering frames are its frames, cut with all the others' into chunks of max_frames (ChunkRun);
+// its PCM region is span * per bytes of the context's window scratch (bases 16-byte aligned); its
+// result is a scratch StreamResult.  After the last chunk k_window_copy moves each clean window's
+// bytes to d_pcm_out + out_offsets[w] -- or, where dv converts, k_window_elements (its mix
+// instantiation where dv mixes: dv.out_channels channels a sample) writes its elements from element
+// out_offsets[w] of d_pcm_out on -- and k_window_results writes d_results.
 int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_first, const uint64_t *d_foff,
                    const uint32_t *d_fbytes, const WindowsCall &wc, const uint32_t *window_stream,
                    const uint64_t *window_count, const deliver::Delivery &dv, uint8_t *d_pcm_out, const uint64_t *out_offsets,
                    window::WindowResult *d_results, hipStream_t st) {
-    DecScratch *d = c->dec;
     IdxScratch *x = c->idx;
     const uint32_t n = wc.n;
     const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u);
-    std::vector<uint64_t> frames, host;
-    std::vector<streams::Segment> segs;
-    std::vector<uint32_t> chunk_seg;
+    std::vector<uint64_t> frames, host;  // host: scratch base, scratch cap, table first, destination
     const bool convert = dv.format != deliver::SAMPLE_BYTES;
-    uint64_t whole = 0, max_bytes = 0;  // whole: the end of the last region, the capacity k_dec_recon checks
+    uint64_t whole = 0, max_bytes = 0;  // whole: the end of the last region
     uint64_t max_written = 0;           // convert: the most samples a window writes, its padding included
     try {
         frames.assign(n, 0);
         host.assign(4u * (uint64_t)n, 0);
-        for (uint32_t w = 0; w < n; w++) {
-            const window::Cover &r = wc.recs[w];
-            const bool decode = r.status == window::WIN_OK && r.n_frames > 0;
-            host[w] = whole;
-            host[2u * (uint64_t)n + w] = table_first[window_stream[w]] + r.first_frame;
-            host[3u * (uint64_t)n + w] = out_offsets[w];
-            if (convert && r.status == window::WIN_OK)
-                max_written = std::max(max_written, deliver::written_samples(r.n_samples, window_count[w], dv.flags));
-            if (!decode) continue;
-            if (r.span > (1ull << 40) || r.n_samples > r.span) return FLACGPU_ERR_INVALID_INPUT;  // no stream's positions
-            frames[w] = r.n_frames;
-            host[n + w] = r.span * per;
-            whole += (r.span * per + 15u) & ~(uint64_t)15u;
-            if (whole > (1ull << 47)) return FLACGPU_ERR_OUT_OF_MEMORY;
-            max_bytes = std::max(max_bytes, r.n_samples * per);
-        }
-        streams::cut_segments(frames, c->max_frames, segs, chunk_seg);
     } catch (...) {
         return FLACGPU_ERR_OUT_OF_MEMORY;
     }
-    const uint32_t n_chunks = chunk_seg.empty() ? 0u : (uint32_t)chunk_seg.size() - 1u;
-    const uint64_t n_packed = (uint64_t)n_chunks * c->max_frames;
-    uint64_t *p_off = nullptr, *meta = nullptr, *carried = nullptr;
-    uint32_t *p_bytes = nullptr;
-    streams::Segment *d_segs = nullptr;
-    streams::StreamResult *sres = nullptr;
-    auto carve = [&](uint8_t *base) {
-        Carve v{base};
-        v.take(n_packed, p_off);
-        v.take(4u * (uint64_t)n, meta);  // scratch base, scratch cap, table first, destination: one upload
-        v.take(n, carried, sres);
-        v.take(segs.size(), d_segs);
-        return v.take(n_packed, p_bytes);
-    };
-    HIPCHK(grow(x->win, x->win_cap, carve(nullptr), &st));
-    carve(x->win);
-    HIPCHK(grow(x->win_pcm, x->win_pcm_cap, whole + 16u, &st));
-    uint64_t *d_base = meta, *d_cap = meta + n, *d_first = meta + 2u * (uint64_t)n, *d_dst = meta + 3u * (uint64_t)n;
-    HIPCHK(hipMemcpyAsync(meta, host.data(), host.size() * 8u, hipMemcpyHostToDevice, st));
-    if (!segs.empty())
-        HIPCHK(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(streams::Segment), hipMemcpyHostToDevice, st));
-    HIPCHK(launch_window_init(wc.d_recs, sres, carried, n, st));
-    HIPCHK(launch_streams_gather(d_segs, (uint32_t)segs.size(), d_first, d_foff, d_fbytes, p_off, p_bytes, st));
-    for (uint32_t k = 0; k < n_chunks; k++) {
-        const uint32_t s0 = chunk_seg[k], s1 = chunk_seg[k + 1u];
-        const uint32_t nf = segs[s1 - 1u].first + segs[s1 - 1u].count;
-        const ChunkStreams cs{d_segs + s0, s1 - s0, d_base, d_cap, carried, sres};
-        const int rc = dec_core(c, d_data, p_off + (uint64_t)k * c->max_frames, p_bytes + (uint64_t)k * c->max_frames, nf,
-                                nullptr, x->win_pcm, whole, nullptr, false, (flacgpu_decode_result *)d->d_results, nullptr,
-                                st, &cs);
-        if (rc) return rc;
+    for (uint32_t w = 0; w < n; w++) {
+        const window::Cover &r = wc.recs[w];
+        const bool decode = r.status == window::WIN_OK && r.n_frames > 0;
+        host[w] = whole;
+        host[2u * (uint64_t)n + w] = table_first[window_stream[w]] + r.first_frame;
+        host[3u * (uint64_t)n + w] = out_offsets[w];
+        if (convert && r.status == window::WIN_OK)
+            max_written = std::max(max_written, deliver::written_samples(r.n_samples, window_count[w], dv.flags));
+        if (!decode) continue;
+        if (r.span > (1ull << 40) || r.n_samples > r.span) return FLACGPU_ERR_INVALID_INPUT;  // no stream's positions
+        frames[w] = r.n_frames;
+        host[n + w] = r.span * per;
+        whole += (r.span * per + 15u) & ~(uint64_t)15u;
+        if (whole > (1ull << 47)) return FLACGPU_ERR_OUT_OF_MEMORY;
+        max_bytes = std::max(max_bytes, r.n_samples * per);
     }
-    if (convert && dv.mix)
-        HIPCHK(launch_window_mix(wc.d_recs, sres, wc.d_args, x->win_pcm, d_base, d_pcm_out, d_dst, dv, n, max_written, st));
-    else if (convert)
-        HIPCHK(launch_window_deliver(wc.d_recs, sres, wc.d_args, x->win_pcm, d_base, d_pcm_out, d_dst, dv, n, max_written, st));
+    HIPCHK(grow(x->win_pcm, x->win_pcm_cap, whole + 16u, &st));
+    ChunkRun run;
+    streams::StreamResult *sres = nullptr;
+    int rc = run.prepare(c, frames, host, x->win, x->win_cap, [&](Carve &v) { v.take(n, sres); }, st);
+    if (rc) return rc;
+    HIPCHK(launch_window_init(wc.d_recs, sres, run.carried, n, st));
+    rc = run.run(c, d_data, d_foff, d_fbytes, x->win_pcm, whole, sres, st);
+    if (rc) return rc;
+    const uint64_t *d_base = run.row(0), *d_dst = run.row(3);
+    if (convert)
+        HIPCHK(launch_window_elements(wc.d_recs, sres, wc.d_args, x->win_pcm, d_base, d_pcm_out, d_dst, dv, n, max_written, st));
     else
         HIPCHK(launch_window_copy(wc.d_recs, sres, x->win_pcm, d_base, d_pcm_out, d_dst, (uint32_t)per, n, max_bytes, st));
     HIPCHK(launch_window_results(wc.d_recs, sres, d_results, n, st));
+    return FLACGPU_OK;
+}
+
+// The files of a many-files call in one device buffer, the context's d_frames: file i at the
+// 64-byte aligned offs[i], lens[i] bytes, uploaded on st.
+int upload_files(flacgpu_ctx *c, uint32_t n, const uint8_t *const *p, const size_t *len, std::vector<uint64_t> &offs,
+                 std::vector<uint64_t> &lens, hipStream_t st) {
+    DecScratch *d = c->dec;
+    try {
+        offs.resize(n);
+        lens.resize(n);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        if (len[i] > 0xFFFFFFFFull) return FLACGPU_ERR_INVALID_INPUT;
+        offs[i] = total;
+        lens[i] = len[i];
+        total += (len[i] + 63u) & ~(uint64_t)63u;
+    }
+    HIPCHK(grow(d->d_frames, d->frames_cap, total + 16u, &st));
+    for (uint32_t i = 0; i < n; i++)
+        if (len[i]) HIPCHK(hipMemcpyAsync(d->d_frames + offs[i], p[i], len[i], hipMemcpyHostToDevice, st));
     return FLACGPU_OK;
 }
 
@@ -824,7 +856,7 @@ int fg::decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uin
     hipStream_t st = c->stream;
     IdxScratch *x = idx_scratch(c);
     if (!x) return 1;
-    const uint64_t fcap = len / 8u + 1u;
+    const uint64_t fcap = table_cap_for(len);
     uint64_t *f_off = nullptr;
     uint32_t *f_bytes = nullptr;
     idx::IndexResult *d_res = nullptr;
@@ -892,24 +924,14 @@ int fg::decode_files_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *
     std::vector<streams::StreamResult> res;
     StreamTables tb;
     try {
-        offs.resize(n);
-        lens.resize(n);
         pcm_offs.resize(n);
         pcm_caps.resize(n);
         res.resize(n);
     } catch (...) {
         return FLACGPU_ERR_OUT_OF_MEMORY;
     }
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        if (len[i] > 0xFFFFFFFFull) return FLACGPU_ERR_INVALID_INPUT;
-        offs[i] = total;
-        lens[i] = len[i];
-        total += (len[i] + 63u) & ~(uint64_t)63u;
-    }
-    HIPCHK(grow(d->d_frames, d->frames_cap, total + 16u, &st));
-    for (uint32_t i = 0; i < n; i++)
-        if (len[i]) HIPCHK(hipMemcpyAsync(d->d_frames + offs[i], p[i], len[i], hipMemcpyHostToDevice, st));
+    rc = upload_files(c, n, p, len, offs, lens, st);
+    if (rc) return rc;
     rc = streams_index(c, d->d_frames, n, offs.data(), lens.data(), bits, rates, tb, ires, st);
     if (rc) return rc;
     // the regions: what the file's frames can hold at most, cut to the caller's capacity
@@ -987,8 +1009,6 @@ int fg::decode_files_windows_resident(flacgpu_ctx *c, uint32_t n, const uint8_t 
     std::vector<uint64_t> offs, lens, first, caps, out_offs;
     std::vector<window::WindowResult> res;
     try {
-        offs.resize(n);
-        lens.resize(n);
         first.resize(n);
         caps.resize(n);
         out_offs.resize(n_windows);
@@ -996,19 +1016,14 @@ int fg::decode_files_windows_resident(flacgpu_ctx *c, uint32_t n, const uint8_t 
     } catch (...) {
         return FLACGPU_ERR_OUT_OF_MEMORY;
     }
-    uint64_t total = 0, entries = 0;
+    rc = upload_files(c, n, p, len, offs, lens, st);
+    if (rc) return rc;
+    uint64_t entries = 0;
     for (uint32_t i = 0; i < n; i++) {
-        if (len[i] > 0xFFFFFFFFull) return FLACGPU_ERR_INVALID_INPUT;
-        offs[i] = total;
-        lens[i] = len[i];
-        total += (len[i] + 63u) & ~(uint64_t)63u;
         first[i] = entries;
-        caps[i] = len[i] / 8u + 1u;  // a frame is at least 9 bytes
+        caps[i] = table_cap_for(len[i]);
         entries += caps[i];
     }
-    HIPCHK(grow(d->d_frames, d->frames_cap, total + 16u, &st));
-    for (uint32_t i = 0; i < n; i++)
-        if (len[i]) HIPCHK(hipMemcpyAsync(d->d_frames + offs[i], p[i], len[i], hipMemcpyHostToDevice, st));
     uint64_t *f_off = nullptr, *f_pos = nullptr, *d_totals = nullptr;
     uint32_t *f_bytes = nullptr;
     idx::IndexResult *d_ires = nullptr;

@@ -1,7 +1,8 @@
 // fg_deliver.hpp -- the scalar rules of delivering decoded sample windows as tensor elements,
-// shared by the device kernels (k_window_deliver and k_window_mix, fg_window.hip), the host layer
-// (fg_dec_host.cpp) and the stand-alone host programs of the tests (tests/cpp/deliver_host_main.cpp,
-// tests/cpp/mix_host_main.cpp).  Compiles under hipcc and plain g++.
+// shared by the device kernel (k_window_elements in its two instantiations, fg_window.hip), the
+// host layer (fg_dec_host.cpp) and the stand-alone host programs of the tests
+// (tests/cpp/deliver_host_main.cpp, tests/cpp/mix_host_main.cpp), which run the kernel's own row
+// code (fill_row_slot).  Compiles under hipcc and plain g++.
 //
 // A SOURCE SAMPLE is the B = bits / 8 bytes at a byte address of any alignment: signed two's
 // complement, little-endian, sign-extended to i32 -- what every decode call here writes to PCM,
@@ -28,9 +29,9 @@ constexpr uint32_t SAMPLE_BYTES = 0xFFFFFFFFu;  // not an element format: the by
 constexpr uint32_t kMixMaxChannels = 8;  // output channels of a mix, and source channels of a mask
 
 // How a window call delivers: `format` SAMPLE_BYTES copies the PCM bytes (k_window_copy, flags 0);
-// any other format converts (k_window_deliver) or, with `mix` set, converts and mixes
-// (k_window_mix): out_channels output channels, output channel k made of the source channels whose
-// bits masks[k] has.  Without `mix` out_channels = channels and masks[k] = 1 << k, the identity.
+// any other format converts (k_window_elements<false>) or, with `mix` set, converts and mixes
+// (k_window_elements<true>): out_channels output channels, output channel k made of the source
+// channels whose bits masks[k] has.  Without `mix` out_channels = channels and masks[k] = 1 << k.
 struct Delivery {
     uint32_t format, flags, channels, sample_bytes;
     uint32_t mix, out_channels;
@@ -187,7 +188,46 @@ FG_HD RowPlan row_plan(uint64_t dst_addr, uint64_t n, uint32_t esz) {
     return p;
 }
 
-// ---- the tile of k_window_deliver --------------------------------------------------------------
+// ---- a row's slots ---------------------------------------------------------------------------------
+// A row of row_elems elements is written as max_units + 2 independent SLOTS, max_units =
+// row_elems / (16 / esz) -- no plan has more units --: slot k < max_units is whole unit k (nothing
+// where the plan has fewer), slot max_units the head elements, the last slot the tail ones.
+// elem(e) is row element e: 32 bits, or 16 in the low half.  k_window_elements gives a thread a
+// slot; the host programs of the tests run the same function slot after slot.
+struct alignas(16) Unit {
+    uint32_t q[4];
+};
+
+FG_HD void store_element(uint8_t *row, uint64_t e, uint32_t esz, uint32_t v) {
+    if (esz == 4u) ((uint32_t *)row)[e] = v;
+    else ((uint16_t *)row)[e] = (uint16_t)v;
+}
+
+template <class Elem>
+FG_HD void fill_row_slot(uint8_t *row, uint32_t row_elems, uint32_t esz, uint32_t k, uint32_t max_units, Elem elem) {
+    const RowPlan p = row_plan((uint64_t)(uintptr_t)row, row_elems, esz);
+    const uint32_t per_unit = 16u / esz;
+    if (k < max_units) {
+        if (k >= p.units) return;
+        const uint32_t e0 = p.head + k * per_unit;
+        Unit u;
+        if (esz == 4u) {
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; j++) u.q[j] = elem(e0 + j);
+        } else {
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; j++) u.q[j] = elem(e0 + 2u * j) | (elem(e0 + 2u * j + 1u) << 16);
+        }
+        *(Unit *)(row + (uint64_t)e0 * esz) = u;  // 16-byte aligned by the plan: one store
+    } else if (k == max_units) {
+        for (uint32_t e = 0; e < p.head; e++) store_element(row, e, esz, elem(e));
+    } else {
+        const uint32_t e1 = p.head + (uint32_t)p.units * per_unit;
+        for (uint32_t e = e1; e < e1 + p.tail; e++) store_element(row, e, esz, elem(e));
+    }
+}
+
+// ---- the tile of k_window_elements --------------------------------------------------------------
 // A workgroup takes kTileBytes / per consecutive samples of one window (per = channels * bytes per
 // sample <= 32, so at least 128): their source bytes go to LDS as the aligned 8-byte words that
 // hold them, at most kTileWords.

@@ -9,12 +9,13 @@
 //                     chunk loop in which a window is what a stream is in fg_dec_streams.hip
 //   k_window_copy     per window (blockIdx.y), after the last chunk: the delivered bytes from the
 //                     window's decoded covering frames to the caller's region
-//   k_window_deliver  in place of k_window_copy for flacgpu_decode_windows_device_as: the delivered
-//                     samples converted to tensor elements (fg_deliver.hpp), interleaved or planar,
-//                     the rest of a padded window zeroed
-//   k_window_mix      in place of k_window_deliver for flacgpu_decode_windows_device_mix: the same
-//                     pass with a channel count other than the source's, every output channel the
-//                     exact mean of a set of source channels, one of them, or silence
+//   k_window_elements in place of k_window_copy, one kernel in two instantiations.  <false>, for
+//                     flacgpu_decode_windows_device_as: the delivered samples converted to tensor
+//                     elements (fg_deliver.hpp), interleaved or planar, the rest of a padded window
+//                     zeroed.  <true>, for flacgpu_decode_windows_device_mix: the same pass with a
+//                     channel count other than the source's, every output channel the exact mean
+//                     of a set of source channels, one of them, or silence.  Both write rows by
+//                     deliver::fill_row_slot, which the host programs of the tests run as well
 //   k_window_results  per window: its flacgpu_window_result
 //
 // Every index is bounded by what the index left and the host sized: a frame i of stream s is
@@ -157,81 +158,6 @@ __device__ __forceinline__ uint32_t tile_element(const uint32_t *words, uint32_t
                             dv.format);
 }
 
-__device__ __forceinline__ void store_element(uint8_t *row, uint64_t e, uint32_t esz, uint32_t v) {
-    if (esz == 4u) ((uint32_t *)row)[e] = v;
-    else ((uint16_t *)row)[e] = (uint16_t)v;
-}
-
-// In place of k_window_copy: window w (blockIdx.y) as elements of dv.format to out + dst_off[w]
-// elements.  A workgroup takes tiles of tile_samples(per) consecutive samples: the aligned 8-byte
-// words of the scratch that hold a tile's source bytes go to LDS (no word past the one that holds
-// the window's last byte is read; a tile of padding alone reads nothing), then every row of the
-// tile -- a plane's part, or the interleaved tile -- is written by its row plan: whole 16-byte
-// units built from LDS, one thread a unit, and the head and tail elements one at a time.  A window
-// that is not clean writes nothing; one with no samples still writes its padding.
-__global__ void __launch_bounds__(256) k_window_deliver(const Cover *recs, const streams::StreamResult *res, const WindowArg *args,
-                                                         const uint8_t *scratch, const uint64_t *src_base, uint8_t *out,
-                                                         const uint64_t *dst_off, deliver::Delivery dv) {
-    __shared__ uint64_t s_src[deliver::kTileWords];
-    const uint32_t w = blockIdx.y, tid = threadIdx.x;
-    const Cover c = recs[w];
-    if (!window_clean(c, res[w])) return;
-    const uint64_t count = args[w].count, n = c.n_samples;
-    const uint64_t total = deliver::written_samples(n, count, dv.flags);
-    if (total == 0) return;
-    const uint32_t C = dv.channels, per = C * dv.sample_bytes, esz = deliver::elem_size(dv.format), per_unit = 16u / esz;
-    const uint32_t T = deliver::tile_samples(per);
-    const bool planar = (dv.flags & deliver::DELIVER_PLANAR) != 0;
-    const uint8_t *src = scratch + src_base[w] + c.skip * per;
-    uint8_t *dst = out + dst_off[w] * esz;
-    const uint64_t n_tiles = (total + T - 1u) / T;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * T;
-        const uint32_t ns = (uint32_t)(total - t0 < T ? total - t0 : T);             // samples written
-        const uint32_t nsrc = t0 < n ? (uint32_t)(n - t0 < T ? n - t0 : T) : 0u;     // of them decoded ones
-        uint32_t lead = 0;
-        if (nsrc) {
-            const uintptr_t a = (uintptr_t)(src + t0 * per), a0 = a & ~(uintptr_t)7;
-            lead = (uint32_t)(a - a0);
-            const uint32_t n_words = (lead + nsrc * per + 7u) / 8u;  // <= kTileWords
-            for (uint32_t i = tid; i < n_words; i += 256u) s_src[i] = ((const uint64_t *)a0)[i];
-        }
-        __syncthreads();
-        const uint32_t *words = (const uint32_t *)s_src;
-        const uint32_t have = nsrc * C;
-        const uint32_t rows = planar ? C : 1u, row_elems = planar ? ns : ns * C;
-        const uint32_t max_units = row_elems / per_unit, slots = max_units + 2u;  // a row's units, its head, its tail
-        for (uint32_t item = tid; item < rows * slots; item += 256u) {
-            const uint32_t r = item / slots, k = item - r * slots;
-            uint8_t *row = dst + (planar ? (uint64_t)r * count + t0 : t0 * C) * esz;
-            const deliver::RowPlan p = deliver::row_plan((uint64_t)(uintptr_t)row, row_elems, esz);
-            const uint32_t mul = planar ? C : 1u, add = planar ? r : 0u;  // row element e is source element e * mul + add
-            if (k < max_units) {
-                if (k >= p.units) continue;
-                const uint32_t e0 = p.head + k * per_unit;
-                uint32_t q[4];
-                if (esz == 4u) {
-#pragma unroll
-                    for (uint32_t j = 0; j < 4u; j++) q[j] = tile_element(words, lead, (e0 + j) * mul + add, have, dv);
-                } else {
-#pragma unroll
-                    for (uint32_t j = 0; j < 4u; j++)
-                        q[j] = tile_element(words, lead, (e0 + 2u * j) * mul + add, have, dv) |
-                               (tile_element(words, lead, (e0 + 2u * j + 1u) * mul + add, have, dv) << 16);
-                }
-                *(uint4 *)(row + (uint64_t)e0 * esz) = make_uint4(q[0], q[1], q[2], q[3]);
-            } else if (k == max_units) {
-                for (uint32_t e = 0; e < p.head; e++) store_element(row, e, esz, tile_element(words, lead, e * mul + add, have, dv));
-            } else {
-                const uint32_t e1 = p.head + (uint32_t)p.units * per_unit;
-                for (uint32_t e = e1; e < e1 + p.tail; e++)
-                    store_element(row, e, esz, tile_element(words, lead, e * mul + add, have, dv));
-            }
-        }
-        __syncthreads();  // s_src is written again by the next tile
-    }
-}
-
 // One element of a mixed tile: output channel `mask` of the tile's sample t, or zero past its
 // `nsrc` decoded samples (the padding).
 __device__ __forceinline__ uint32_t mix_tile_element(const uint32_t *words, uint32_t lead, uint32_t t, uint32_t nsrc, uint32_t per,
@@ -240,17 +166,20 @@ __device__ __forceinline__ uint32_t mix_tile_element(const uint32_t *words, uint
     return deliver::mix_element(words, lead + t * per, dv.sample_bytes, mask, dv.format);
 }
 
-// k_window_deliver with a channel mix (flacgpu_decode_windows_device_mix): window w (blockIdx.y) as
-// K = dv.out_channels channels of dv.format elements to out + dst_off[w] elements, output channel k
-// of a sample made of the source channels in dv.masks[k] (deliver::mix_element).  The source tile
-// is k_window_deliver's -- tile_samples(per) consecutive source samples as the aligned 8-byte words
-// that hold them, no word past the one with the window's last byte, nothing read for a tile of
-// padding alone --; the rows are the destination's: K planes of the tile's samples, or one
-// interleaved row of samples * K elements, each cut by its row plan.  A window that is not clean
-// writes nothing; one with no samples still writes its padding.
-__global__ void __launch_bounds__(256) k_window_mix(const Cover *recs, const streams::StreamResult *res, const WindowArg *args,
-                                                     const uint8_t *scratch, const uint64_t *src_base, uint8_t *out,
-                                                     const uint64_t *dst_off, deliver::Delivery dv) {
+// In place of k_window_copy: window w (blockIdx.y) as K channels of dv.format elements to out +
+// dst_off[w] elements; K = dv.channels, or with Mix dv.out_channels, output channel k of a sample
+// then made of the source channels in dv.masks[k] (deliver::mix_element).  A workgroup takes tiles
+// of tile_samples(per) consecutive source samples: the aligned 8-byte words of the scratch that
+// hold a tile's source bytes go to LDS (no word past the one that holds the window's last byte is
+// read; a tile of padding alone reads nothing), then every row of the tile -- a plane's part, or
+// the interleaved tile of samples * K elements -- is written slot by slot, one thread a slot
+// (deliver::fill_row_slot): whole 16-byte units built from LDS, the head and the tail elements one
+// at a time.  A window that is not clean writes nothing; one with no samples still writes its
+// padding.
+template <bool Mix>
+__global__ void __launch_bounds__(256) k_window_elements(const Cover *recs, const streams::StreamResult *res, const WindowArg *args,
+                                                          const uint8_t *scratch, const uint64_t *src_base, uint8_t *out,
+                                                          const uint64_t *dst_off, deliver::Delivery dv) {
     __shared__ uint64_t s_src[deliver::kTileWords];
     const uint32_t w = blockIdx.y, tid = threadIdx.x;
     const Cover c = recs[w];
@@ -258,12 +187,14 @@ __global__ void __launch_bounds__(256) k_window_mix(const Cover *recs, const str
     const uint64_t count = args[w].count, n = c.n_samples;
     const uint64_t total = deliver::written_samples(n, count, dv.flags);
     if (total == 0) return;
-    const uint32_t K = dv.out_channels, per = dv.channels * dv.sample_bytes, esz = deliver::elem_size(dv.format);
-    const uint32_t per_unit = 16u / esz, T = deliver::tile_samples(per);
+    const uint32_t C = dv.channels, K = Mix ? dv.out_channels : C, per = C * dv.sample_bytes;
+    const uint32_t esz = deliver::elem_size(dv.format), per_unit = 16u / esz, T = deliver::tile_samples(per);
     const bool planar = (dv.flags & deliver::DELIVER_PLANAR) != 0;
     uint64_t masks = 0;  // mask k in byte k: indexed by shifts, so that the argument is never addressed
+    if (Mix) {
 #pragma unroll
-    for (uint32_t k = 0; k < deliver::kMixMaxChannels; k++) masks |= (uint64_t)dv.masks[k] << (8u * k);
+        for (uint32_t k = 0; k < deliver::kMixMaxChannels; k++) masks |= (uint64_t)dv.masks[k] << (8u * k);
+    }
     const uint8_t *src = scratch + src_base[w] + c.skip * per;
     uint8_t *dst = out + dst_off[w] * esz;
     const uint64_t n_tiles = (total + T - 1u) / T;
@@ -285,29 +216,16 @@ __global__ void __launch_bounds__(256) k_window_mix(const Cover *recs, const str
         for (uint32_t item = tid; item < rows * slots; item += 256u) {
             const uint32_t r = item / slots, k = item - r * slots;
             uint8_t *row = dst + (planar ? (uint64_t)r * count + t0 : t0 * K) * esz;
-            const deliver::RowPlan p = deliver::row_plan((uint64_t)(uintptr_t)row, row_elems, esz);
-            // row element e: sample e of plane r, or sample e / K, channel e % K of the interleaved row
-            auto elem = [&](uint32_t e) {
-                const uint32_t t = planar ? e : e / K, ch = planar ? r : e - t * K;
-                return mix_tile_element(words, lead, t, nsrc, per, (uint32_t)(masks >> (8u * ch)) & 0xFFu, dv);
-            };
-            if (k < max_units) {
-                if (k >= p.units) continue;
-                const uint32_t e0 = p.head + k * per_unit;
-                uint32_t q[4];
-                if (esz == 4u) {
-#pragma unroll
-                    for (uint32_t j = 0; j < 4u; j++) q[j] = elem(e0 + j);
-                } else {
-#pragma unroll
-                    for (uint32_t j = 0; j < 4u; j++) q[j] = elem(e0 + 2u * j) | (elem(e0 + 2u * j + 1u) << 16);
-                }
-                *(uint4 *)(row + (uint64_t)e0 * esz) = make_uint4(q[0], q[1], q[2], q[3]);
-            } else if (k == max_units) {
-                for (uint32_t e = 0; e < p.head; e++) store_element(row, e, esz, elem(e));
+            if (Mix) {
+                // row element e: sample e of plane r, or sample e / K, channel e % K of the interleaved row
+                deliver::fill_row_slot(row, row_elems, esz, k, max_units, [&](uint32_t e) {
+                    const uint32_t t = planar ? e : e / K, ch = planar ? r : e - t * K;
+                    return mix_tile_element(words, lead, t, nsrc, per, (uint32_t)(masks >> (8u * ch)) & 0xFFu, dv);
+                });
             } else {
-                const uint32_t e1 = p.head + (uint32_t)p.units * per_unit;
-                for (uint32_t e = e1; e < e1 + p.tail; e++) store_element(row, e, esz, elem(e));
+                const uint32_t mul = planar ? C : 1u, add = planar ? r : 0u;  // row element e is source element e * mul + add
+                deliver::fill_row_slot(row, row_elems, esz, k, max_units,
+                                       [&](uint32_t e) { return tile_element(words, lead, e * mul + add, nsrc * C, dv); });
             }
         }
         __syncthreads();  // s_src is written again by the next tile
@@ -379,27 +297,17 @@ hipError_t launch_window_copy(const Cover *recs, const streams::StreamResult *re
     return hipGetLastError();
 }
 
-// n <= 65535 (gridDim.y); max_samples: the most any window writes, padding included, which sizes gridDim.x
-hipError_t launch_window_deliver(const Cover *recs, const streams::StreamResult *res, const WindowArg *args,
-                                 const uint8_t *scratch, const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off,
-                                 const deliver::Delivery &dv, uint32_t n, uint64_t max_samples, hipStream_t st) {
+// n <= 65535 (gridDim.y); max_samples: the most any window writes, padding included, which sizes
+// gridDim.x: the tiles are of source samples with a mix or without
+hipError_t launch_window_elements(const Cover *recs, const streams::StreamResult *res, const WindowArg *args,
+                                  const uint8_t *scratch, const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off,
+                                  const deliver::Delivery &dv, uint32_t n, uint64_t max_samples, hipStream_t st) {
     if (n == 0 || max_samples == 0) return hipSuccess;
     const uint32_t T = deliver::tile_samples(dv.channels * dv.sample_bytes);
     const uint64_t tiles = (max_samples + T - 1u) / T;
     const uint32_t gx = (uint32_t)(tiles > 1024u ? 1024u : tiles);
-    hipLaunchKernelGGL(k_window_deliver, dim3(gx, n), dim3(256), 0, st, recs, res, args, scratch, src_base, out, dst_off, dv);
-    return hipGetLastError();
-}
-
-// launch_window_deliver's grid for a Delivery with `mix` set: the tiles are of source samples either way
-hipError_t launch_window_mix(const Cover *recs, const streams::StreamResult *res, const WindowArg *args, const uint8_t *scratch,
-                             const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off, const deliver::Delivery &dv,
-                             uint32_t n, uint64_t max_samples, hipStream_t st) {
-    if (n == 0 || max_samples == 0) return hipSuccess;
-    const uint32_t T = deliver::tile_samples(dv.channels * dv.sample_bytes);
-    const uint64_t tiles = (max_samples + T - 1u) / T;
-    const uint32_t gx = (uint32_t)(tiles > 1024u ? 1024u : tiles);
-    hipLaunchKernelGGL(k_window_mix, dim3(gx, n), dim3(256), 0, st, recs, res, args, scratch, src_base, out, dst_off, dv);
+    hipLaunchKernelGGL(dv.mix ? k_window_elements<true> : k_window_elements<false>, dim3(gx, n), dim3(256), 0, st, recs, res, args,
+                       scratch, src_base, out, dst_off, dv);
     return hipGetLastError();
 }
 

@@ -45,6 +45,68 @@ def _check_blocks(who: str, i: int, si) -> None:
                          f"at most {most} at {int(si.bit_depth)} bits")
 
 
+def _crops(who, device, n_files, K, groups, where, check, file, start, length, dtype, planar, pad, out, strict):
+    """The one body of FlacBank.crops and FlacMixBank.crops: crops of K channels from `groups` =
+    [(FlacBank, its channel masks or None)], file f being file where(f)[1] of group where(f)[0];
+    check(fmt): the caller's own refusals of a format, raised between the dtype's and the crops'."""
+    import torch
+
+    dtype = torch.float32 if dtype is None else dtype
+    fmt = _formats().get(dtype)
+    if fmt is None:
+        raise ValueError(f"{who}: dtype {dtype} is none of float32, float16, bfloat16, int32")
+    check(fmt)
+    W, length = len(file), int(length)
+    if len(start) != W:
+        raise ValueError(f"{who}: file and start differ in length")
+    if length < 0 or any(not 0 <= int(f) < n_files for f in file) or any(int(s) < 0 for s in start):
+        raise ValueError(f"{who}: a file index, a start or the length is out of range")
+    shape = (W, K, length) if planar else (W, length, K)
+    routed = [[] for _ in groups]  # group -> its crops, in the caller's order
+    for w in range(W):
+        routed[where(int(file[w]))[0]].append(w)
+    order = [w for ws in routed for w in ws]  # row r of d_res is crop order[r]
+    with torch.cuda.device(device):
+        if out is not None:
+            if (tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous()):
+                raise ValueError(f"{who}: out must be a contiguous {dtype} tensor of shape {shape} on {device}")
+            x = out
+            if not pad:
+                x.zero_()
+        else:
+            x = torch.empty(shape, dtype=dtype, device=device) if pad else torch.zeros(shape, dtype=dtype, device=device)
+        flags = (flacgpu.DELIVER_PLANAR if planar else 0) | (flacgpu.DELIVER_PAD if pad else 0)
+        st = torch.cuda.current_stream(device).cuda_stream
+        d_res = torch.empty(32 * max(W, 1), dtype=torch.uint8, device=device)
+        per_crop, row = K * length, 0
+        for (bank, masks), ws in zip(groups, routed):
+            for w0 in range(0, len(ws), MAX_WINDOWS):
+                part = ws[w0:w0 + MAX_WINDOWS]
+                windows = [(where(int(file[w]))[1], int(start[w]), length) for w in part]
+                tables = (bank._data.data_ptr(), bank._first, bank._off.data_ptr(), bank._fbytes.data_ptr(),
+                          bank._ires.data_ptr(), bank._pos.data_ptr(), bank._totals.data_ptr(), windows, fmt, flags)
+                to = (x.data_ptr(), [w * per_crop for w in part], [per_crop] * len(part), d_res.data_ptr() + 32 * row)
+                if masks is None:
+                    bank._dec.decode_windows_device_as(*tables, *to, stream=st)
+                else:
+                    bank._dec.decode_windows_device_mix(*tables, masks, *to, stream=st)
+                row += len(part)
+        rows = (flacgpu.WindowResult * max(W, 1)).from_buffer_copy(d_res.cpu().numpy().tobytes())  # waits for st
+    res = [None] * W
+    for r, w in enumerate(order):
+        res[w] = rows[r]
+    n = [int(res[w].n_samples) for w in range(W)]
+    statuses = [int(res[w].status) for w in range(W)]
+    if strict:
+        for w, s in enumerate(statuses):
+            if s != flacgpu.WINDOW_OK:
+                bad = f", frame {res[w].first_bad_frame}" if s == flacgpu.WINDOW_BAD_FRAME else ""
+                raise flacgpu.FlacGpuError(-2, f"{who}.crops: crop {w} (file {int(file[w])}, start {int(start[w])}) is "
+                                               f"{WINDOW_STATUS.get(s, s)}{bad}")
+        return x, n
+    return x, n, statuses
+
+
 class FlacBank:
     def __init__(self, files: Sequence[bytes], device: int = 0, max_frames: int = 4096, _group=None):
         # _group: (who, [the caller's file index], [(STREAMINFO, bare frames)]) from FlacMixBank, whose
@@ -148,52 +210,10 @@ class FlacBank:
         queued on torch.cuda.current_stream(device); the call waits for it.  strict: raise
         FlacGpuError for the first crop whose status is not OK; strict=False returns
         (x, n, statuses) instead.  out: a contiguous tensor of x's shape, dtype and device to fill."""
-        import torch
-
         if self._dec is None:
             raise ValueError("FlacBank: closed")
-        dtype = torch.float32 if dtype is None else dtype
-        fmt = _formats().get(dtype)
-        if fmt is None:
-            raise ValueError(f"FlacBank: dtype {dtype} is none of float32, float16, bfloat16, int32")
-        W, C, length = len(file), self.channels, int(length)
-        if len(start) != W:
-            raise ValueError("FlacBank: file and start differ in length")
-        if length < 0 or any(not 0 <= int(f) < len(self) for f in file) or any(int(s) < 0 for s in start):
-            raise ValueError("FlacBank: a file index, a start or the length is out of range")
-        shape = (W, C, length) if planar else (W, length, C)
-        with torch.cuda.device(self.device):
-            if out is not None:
-                if (tuple(out.shape) != shape or out.dtype != dtype or out.device != self.device or not out.is_contiguous()):
-                    raise ValueError(f"FlacBank: out must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
-                x = out
-                if not pad:
-                    x.zero_()
-            else:
-                x = torch.empty(shape, dtype=dtype, device=self.device) if pad else torch.zeros(shape, dtype=dtype,
-                                                                                                 device=self.device)
-            flags = (flacgpu.DELIVER_PLANAR if planar else 0) | (flacgpu.DELIVER_PAD if pad else 0)
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            d_res = torch.empty(32 * max(W, 1), dtype=torch.uint8, device=self.device)
-            per_crop = C * length
-            for w0 in range(0, W, MAX_WINDOWS):
-                w1 = min(W, w0 + MAX_WINDOWS)
-                windows = [(int(file[w]), int(start[w]), length) for w in range(w0, w1)]
-                self._dec.decode_windows_device_as(
-                    self._data.data_ptr(), self._first, self._off.data_ptr(), self._fbytes.data_ptr(), self._ires.data_ptr(),
-                    self._pos.data_ptr(), self._totals.data_ptr(), windows, fmt, flags, x.data_ptr(),
-                    [w * per_crop for w in range(w0, w1)], [per_crop] * (w1 - w0), d_res.data_ptr() + 32 * w0, stream=st)
-            res = (flacgpu.WindowResult * max(W, 1)).from_buffer_copy(d_res.cpu().numpy().tobytes())  # waits for st
-        n = [int(res[w].n_samples) for w in range(W)]
-        statuses = [int(res[w].status) for w in range(W)]
-        if strict:
-            for w, s in enumerate(statuses):
-                if s != flacgpu.WINDOW_OK:
-                    bad = f", frame {res[w].first_bad_frame}" if s == flacgpu.WINDOW_BAD_FRAME else ""
-                    raise flacgpu.FlacGpuError(-2, f"FlacBank.crops: crop {w} (file {int(file[w])}, start {int(start[w])}) is "
-                                                   f"{WINDOW_STATUS.get(s, s)}{bad}")
-            return x, n
-        return x, n, statuses
+        return _crops("FlacBank", self.device, len(self), self.channels, [(self, None)], lambda f: (0, f), lambda fmt: None,
+                      file, start, length, dtype, planar, pad, out, strict)
 
 
 MIX_MAX_CHANNELS = 8
@@ -319,16 +339,13 @@ class FlacMixBank:
         torch.cuda.current_stream(device) into the one x, and the call waits once per such call of
         a group that has crops, then once for the results.  A damaged frame in one file harms no
         crop of another."""
-        import torch
-
         who = "FlacMixBank"
         if not self._groups:
             raise ValueError(f"{who}: closed")
-        dtype = torch.float32 if dtype is None else dtype
-        fmt = _formats().get(dtype)
-        if fmt is None:
-            raise ValueError(f"{who}: dtype {dtype} is none of float32, float16, bfloat16, int32")
-        if fmt == flacgpu.SAMPLE_I32:
+
+        def check(fmt):
+            if fmt != flacgpu.SAMPLE_I32:
+                return
             if len(self.bits) > 1:
                 raise ValueError(f"{who}: int32 crops of a bank that holds depths {self.bits}: the integers would have "
                                  f"different scales")
@@ -336,51 +353,6 @@ class FlacMixBank:
                 why = _mix_error(bank.channels, masks, integers=True)
                 if why:
                     raise ValueError(f"{who}: int32 crops of {bank.channels}-channel files: {why}")
-        W, K, length = len(file), self.channels, int(length)
-        if len(start) != W:
-            raise ValueError(f"{who}: file and start differ in length")
-        if length < 0 or any(not 0 <= int(f) < len(self) for f in file) or any(int(s) < 0 for s in start):
-            raise ValueError(f"{who}: a file index, a start or the length is out of range")
-        shape = (W, K, length) if planar else (W, length, K)
-        routed = [[] for _ in self._groups]  # group -> its crops, in the caller's order
-        for w in range(W):
-            routed[self._where[int(file[w])][0]].append(w)
-        order = [w for ws in routed for w in ws]  # row r of d_res is crop order[r]
-        with torch.cuda.device(self.device):
-            if out is not None:
-                if (tuple(out.shape) != shape or out.dtype != dtype or out.device != self.device or not out.is_contiguous()):
-                    raise ValueError(f"{who}: out must be a contiguous {dtype} tensor of shape {shape} on {self.device}")
-                x = out
-                if not pad:
-                    x.zero_()
-            else:
-                x = torch.empty(shape, dtype=dtype, device=self.device) if pad else torch.zeros(shape, dtype=dtype,
-                                                                                                 device=self.device)
-            flags = (flacgpu.DELIVER_PLANAR if planar else 0) | (flacgpu.DELIVER_PAD if pad else 0)
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            d_res = torch.empty(32 * max(W, 1), dtype=torch.uint8, device=self.device)
-            per_crop, row = K * length, 0
-            for (bank, masks), ws in zip(self._groups, routed):
-                for w0 in range(0, len(ws), MAX_WINDOWS):
-                    part = ws[w0:w0 + MAX_WINDOWS]
-                    windows = [(self._where[int(file[w])][1], int(start[w]), length) for w in part]
-                    bank._dec.decode_windows_device_mix(
-                        bank._data.data_ptr(), bank._first, bank._off.data_ptr(), bank._fbytes.data_ptr(),
-                        bank._ires.data_ptr(), bank._pos.data_ptr(), bank._totals.data_ptr(), windows, fmt, flags, masks,
-                        x.data_ptr(), [w * per_crop for w in part], [per_crop] * len(part), d_res.data_ptr() + 32 * row,
-                        stream=st)
-                    row += len(part)
-            rows = (flacgpu.WindowResult * max(W, 1)).from_buffer_copy(d_res.cpu().numpy().tobytes())  # waits for st
-        res = [None] * W
-        for r, w in enumerate(order):
-            res[w] = rows[r]
-        n = [int(res[w].n_samples) for w in range(W)]
-        statuses = [int(res[w].status) for w in range(W)]
-        if strict:
-            for w, s in enumerate(statuses):
-                if s != flacgpu.WINDOW_OK:
-                    bad = f", frame {res[w].first_bad_frame}" if s == flacgpu.WINDOW_BAD_FRAME else ""
-                    raise flacgpu.FlacGpuError(-2, f"{who}.crops: crop {w} (file {int(file[w])}, start {int(start[w])}) is "
-                                                   f"{WINDOW_STATUS.get(s, s)}{bad}")
-            return x, n
-        return x, n, statuses
+
+        return _crops(who, self.device, len(self), self.channels, self._groups, self._where.__getitem__, check, file, start,
+                      length, dtype, planar, pad, out, strict)

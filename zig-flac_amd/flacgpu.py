@@ -598,6 +598,13 @@ class _DecodeOps:
             d_index_results, _u32s(stream_bits), _u32s(stream_rates), d_frame_first_sample, d_stream_samples,
             _stream(stream)), "flac_positions_streams_device")
 
+    def _window_args(self, d_data, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                     d_stream_samples, windows):
+        """The arguments the three window calls share: the context through the windows' counts."""
+        return (self.ctx, d_data, len(table_first), _u64s(table_first), d_frame_offsets, d_frame_bytes, d_index_results,
+                d_frame_first_sample, d_stream_samples, len(windows), _u32s([w[0] for w in windows]),
+                _u64s([w[1] for w in windows]), _u64s([w[2] for w in windows]))
+
     def decode_windows_device(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int, d_frame_bytes: int,
                               d_index_results: int, d_frame_first_sample: int, d_stream_samples: int,
                               windows: Sequence, d_pcm_out: int, pcm_offsets: Sequence[int], pcm_caps: Sequence[int],
@@ -605,10 +612,9 @@ class _DecodeOps:
         """flacgpu_decode_windows_device: windows = [(stream, start, count)] over resident tables and
         positions; window w's bytes to d_pcm_out + pcm_offsets[w], d_results: WindowResult per window."""
         _check(self.lib.flacgpu_decode_windows_device(
-            self.ctx, d_data, len(table_first), _u64s(table_first), d_frame_offsets, d_frame_bytes, d_index_results,
-            d_frame_first_sample, d_stream_samples, len(windows), _u32s([w[0] for w in windows]),
-            _u64s([w[1] for w in windows]), _u64s([w[2] for w in windows]), d_pcm_out, _u64s(pcm_offsets),
-            _u64s(pcm_caps), d_results, _stream(stream)), "decode_windows_device")
+            *self._window_args(d_data, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                               d_stream_samples, windows),
+            d_pcm_out, _u64s(pcm_offsets), _u64s(pcm_caps), d_results, _stream(stream)), "decode_windows_device")
 
     def decode_windows_device_as(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int, d_frame_bytes: int,
                                  d_index_results: int, d_frame_first_sample: int, d_stream_samples: int,
@@ -619,10 +625,10 @@ class _DecodeOps:
         sample_format (SAMPLE_*), laid out by flags (DELIVER_*); window w's elements from element
         out_offsets[w] of d_out on, out_caps in elements too."""
         _check(self.lib.flacgpu_decode_windows_device_as(
-            self.ctx, d_data, len(table_first), _u64s(table_first), d_frame_offsets, d_frame_bytes, d_index_results,
-            d_frame_first_sample, d_stream_samples, len(windows), _u32s([w[0] for w in windows]),
-            _u64s([w[1] for w in windows]), _u64s([w[2] for w in windows]), sample_format, flags, d_out,
-            _u64s(out_offsets), _u64s(out_caps), d_results, _stream(stream)), "decode_windows_device_as")
+            *self._window_args(d_data, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                               d_stream_samples, windows),
+            sample_format, flags, d_out, _u64s(out_offsets), _u64s(out_caps), d_results, _stream(stream)),
+            "decode_windows_device_as")
 
     def decode_windows_device_mix(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int, d_frame_bytes: int,
                                   d_index_results: int, d_frame_first_sample: int, d_stream_samples: int,
@@ -636,11 +642,10 @@ class _DecodeOps:
         if any(not 0 <= m <= 255 for m in masks):
             raise FlacGpuError(-2, "decode_windows_device_mix: a channel mask is not in 0..255")
         _check(self.lib.flacgpu_decode_windows_device_mix(
-            self.ctx, d_data, len(table_first), _u64s(table_first), d_frame_offsets, d_frame_bytes, d_index_results,
-            d_frame_first_sample, d_stream_samples, len(windows), _u32s([w[0] for w in windows]),
-            _u64s([w[1] for w in windows]), _u64s([w[2] for w in windows]), sample_format, flags, len(masks),
-            (ctypes.c_uint8 * max(len(masks), 1))(*masks), d_out, _u64s(out_offsets), _u64s(out_caps), d_results,
-            _stream(stream)), "decode_windows_device_mix")
+            *self._window_args(d_data, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                               d_stream_samples, windows),
+            sample_format, flags, len(masks), (ctypes.c_uint8 * max(len(masks), 1))(*masks), d_out, _u64s(out_offsets),
+            _u64s(out_caps), d_results, _stream(stream)), "decode_windows_device_mix")
 
     def decode_files_windows(self, flacs: Sequence[bytes], windows: Sequence, guard: int = 0,
                              pcm_caps: Optional[Sequence[int]] = None):
