@@ -678,6 +678,61 @@ int flacgpu_decode_windows_device_mix(flacgpu_ctx *ctx, const uint8_t *d_data,
                                       uint32_t out_channels, const uint8_t *channel_masks,
                                       void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
                                       flacgpu_window_result *d_results, void *hip_stream);
+/* The same delivery at another sample rate: a stream of rate src_rate is delivered at dst_rate by a
+ * polyphase windowed-sinc FIR that runs in the delivery pass, over the same decoded covering frames.
+ * With g = gcd(src_rate, dst_rate), L = dst_rate / g and M = src_rate / g, a ratio is valid when the
+ * rates differ, 1 <= L, M <= 1024 and M <= 12 * L.  The filter: Hw = 24 where L >= M, else
+ * ceil(24 * M / L); T = 2 * Hw taps (<= 576); for phase p < L and tap k < T, d = (k - Hw + 1) - p / L,
+ * c = 0.95 * min(1, L / M), h64(p, k) = c * sinc(c * d) * I0(9 * sqrt(max(0, 1 - (d / Hw)^2))) / I0(9),
+ * every phase divided by its own sum (DC gain 1), all in double (I0 by its power series), then
+ * h[p][k] = (float)h64(p, k).  flacgpu_resample_filter (host only, no device) gives *up = L,
+ * *down = M, *taps = T (each may be NULL) and the table h[p][k], row-major, L * T floats, in coeffs;
+ * *n = L * T, FLACGPU_ERR_OUTPUT_TOO_SMALL (with *n set) where cap is less, FLACGPU_ERR_INVALID_INPUT
+ * for an invalid ratio. */
+int flacgpu_resample_filter(uint32_t src_rate, uint32_t dst_rate, uint32_t *up, uint32_t *down, uint32_t *taps,
+                            float *coeffs, size_t cap, size_t *n);
+/* The sample rule.  A stream of `total` source samples has out_total = ceil(total * L / M) output
+ * samples; output sample j sits at source position j * M / L: i0 = j * M div L, p = j * M mod L.
+ * With x[i] the FLACGPU_SAMPLE_F32 element of a source sample (+0.0f for i < 0 or i >= total: the
+ * extension is zero), y = +0.0f, then for k = 0 .. T - 1 in this order
+ * y = fmaf(h[p][k], x[i0 - Hw + 1 + k], y): one accumulator, one correctly rounded fused
+ * multiply-add a tap.  flacgpu_resample_f32_host (host only) is this rule over one channel of F32
+ * elements x[0 .. total), total <= 2^40: output samples [start, start + count) clipped to out_total
+ * go to y (room for min(count, out_total - start) floats), *n of them.  It is a statement of the
+ * rule for callers and tests, bit for bit what the device delivers; it is NOT a decode path: there
+ * is no CPU fallback, a FLAC stream is decoded and resampled on the device only. */
+int flacgpu_resample_f32_host(const float *x, uint64_t total, uint32_t src_rate, uint32_t dst_rate, uint64_t start,
+                              uint64_t count, float *y, uint64_t *n);
+/* flacgpu_decode_windows_device_mix through that filter.  The context's streams have rate src_rate;
+ * window_start / window_count, out_offsets / out_caps and the results' n_samples are in OUTPUT samples
+ * and elements at dst_rate: window w is output samples [start, start + count) clipped to out_total of
+ * its stream, n of them delivered.  x[i] of output channel k is the F32 element the mix rule gives
+ * (one source channel, the exact mean of 2, 4 or 8, zero for an empty mask); channel_masks NULL is
+ * the identity of the context's C channels (out_channels is then ignored).  The element is y
+ * (FLACGPU_SAMPLE_F32) or y narrowed as above (F16, BF16; |y| can pass 1 and stays below 4);
+ * FLACGPU_SAMPLE_I32 is not offered.  The covering frames are those of the source samples
+ * [max(0, start * M div L - Hw + 1), min(total, (start + n - 1) * M div L + Hw + 1)): first_frame and
+ * n_frames of a result are theirs, and BAD_FRAME where any of them is bad, one that only the
+ * filter's reach touches included.  Layout, FLACGPU_DELIVER_PAD (zeros for [n, count)) and TOO_SMALL
+ * are those of _mix with the output count and n; a window that is not OK writes nothing.  An invalid
+ * ratio, equal rates, FLACGPU_SAMPLE_I32 and every argument error of _mix (a NULL channel_masks
+ * excepted): FLACGPU_ERR_INVALID_INPUT before any device work.  The coefficient table lives in
+ * device memory the context owns, one per ratio, built on the host and uploaded by the first call
+ * that needs it -- that call waits for hip_stream once more -- and freed by flacgpu_close.  The one
+ * wait for the covers, the 65535-window limit, the chunks and the stream semantics are those of
+ * flacgpu_decode_windows_device; the FIR kernel is not timed. */
+int flacgpu_decode_windows_device_resample(flacgpu_ctx *ctx, const uint8_t *d_data,
+                                           uint32_t n_streams, const uint64_t *table_first,
+                                           const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                           const flacgpu_index_result *d_index_results,
+                                           const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
+                                           uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
+                                           const uint64_t *window_count,
+                                           uint32_t sample_format, uint32_t flags,
+                                           uint32_t out_channels, const uint8_t *channel_masks,
+                                           uint32_t src_rate, uint32_t dst_rate,
+                                           void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
+                                           flacgpu_window_result *d_results, void *hip_stream);
 /* Windows of whole files in host memory: window w is samples [window_start[w], + window_count[w])
  * of file window_file[w] (< n_files), delivered to pcm_out[w] (capacity pcm_cap[w]) with
  * n_samples[w].  Metadata is parsed on the host as in flacgpu_decode_files; the good files' frames

@@ -59,6 +59,15 @@ events, the median).  The two tensors are compared; they may differ in the last 
 mix rounds the exact sum once and torch rounds each channel's element and then their mean.
 
     python tools/decode_rate.py --legs mix --mix-out profiles/decode_mix_rate.json
+
+The resample leg (--resample-out; opt-in, not part of `all`) takes the same files and source windows,
+both channels, f32, planar and padded: flacgpu_decode_windows_device_resample 44100 -> 48000 over the
+output samples that sit in each source window, against flacgpu_decode_windows_device_mix of the
+source window itself, alternated (HIP events, the median).  The difference is what the FIR pass adds
+to a call bound by the parse kernel.  The first outputs of the first and the last file are compared
+with flacgpu.resample_f32_host over the PCM, bit for bit.
+
+    python tools/decode_rate.py --legs resample --resample-out profiles/decode_resample_rate.json
 """
 import argparse
 import contextlib
@@ -727,6 +736,63 @@ def mix_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: 
     return res
 
 
+def resample_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: int, dst_rate: int = 48000) -> dict:
+    import numpy as np
+    import torch
+
+    import flacgpu
+
+    with resident_windows(n_files, frames_each, window) as r:
+        enc, ch, bits, per, dev, pcm, n_each, st, crops = r.enc, r.ch, r.bits, r.per, r.dev, r.pcm, r.n_each, r.st, r.crops
+        tables, d_wres, start = r.tables, r.d_wres, r.start
+        r.positions()
+        L, M, taps = flacgpu.resample_ratio(r.rate, dst_rate)
+        out_start, out_count = -(-start * L // M), window * L // M  # the output samples that sit in the source window
+        out_crops = [(i, out_start, out_count) for i in range(n_files)]
+        planar_pad = flacgpu.DELIVER_PLANAR | flacgpu.DELIVER_PAD
+        masks = [1 << c for c in range(ch)]
+        x_mix = torch.zeros((n_files, ch, window), dtype=torch.float32, device=dev)
+        x_res = torch.zeros((n_files, ch, out_count), dtype=torch.float32, device=dev)
+
+        def mix():
+            enc.decode_windows_device_mix(*tables, crops, flacgpu.SAMPLE_F32, planar_pad, masks, x_mix.data_ptr(),
+                                          [i * ch * window for i in range(n_files)], [ch * window] * n_files, d_wres.data_ptr(),
+                                          stream=st)
+            return x_mix
+
+        def resample():
+            enc.decode_windows_device_resample(*tables, out_crops, flacgpu.SAMPLE_F32, planar_pad, masks, r.rate, dst_rate,
+                                               x_res.data_ptr(), [i * ch * out_count for i in range(n_files)],
+                                               [ch * out_count] * n_files, d_wres.data_ptr(), stream=st)
+            return x_res
+
+        legs = {"resample_f32": (resample, out_count), "mix_f32": (mix, window)}
+        for _ in range(warmup):  # the first resample call also builds and uploads the coefficient table
+            for fn, n in legs.values():
+                fn()
+                enc.sync_check(st)
+                assert r.results() == [(0, n)] * n_files
+        # the expectation from the PCM: the host statement of the rule over channel 0's elements
+        check = 4096
+        v = np.frombuffer(pcm, dtype=np.int16).reshape(n_each, ch)[:, 0].astype(np.float32) * np.float32(2.0 ** -(bits - 1))
+        want = torch.from_numpy(flacgpu.resample_f32_host(v, r.rate, dst_rate, out_start, check))
+        got = resample().cpu()
+        assert torch.equal(got[0, 0, :check], want) and torch.equal(got[-1, 0, :check], want), "the device differs from the host rule"
+        ms = {k: [] for k in legs}
+        for _ in range(repeats):  # alternated
+            for k, (fn, _) in legs.items():
+                ms[k].append(event_ms(fn))
+        res = {"files": n_files, "frames_per_file": frames_each, "channels": ch, "bits": bits, "src_rate": r.rate,
+               "dst_rate": dst_rate, "L": L, "M": M, "taps": taps, "window_samples": window, "window_start": start,
+               "out_window_samples": out_count, "out_window_start": out_start, "layout": "f32, planar, padded", "warmup": warmup,
+               "repeats": repeats, "outputs_checked_against_the_host_rule": 2 * check}
+        for k in legs:
+            res[k] = summary(ms[k], keep=True)
+        res["resample_f32"]["ms_over_mix"] = res["resample_f32"]["ms_median"] - res["mix_f32"]["ms_median"]
+        res["resample_f32"]["x_mix"] = res["resample_f32"]["ms_median"] / res["mix_f32"]["ms_median"]
+    return res
+
+
 def bigblock_rate(blocks, n_streams: int, warmup: int, repeats: int) -> dict:
     import numpy as np
     import torch
@@ -800,7 +866,9 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix"), default="all")
+    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix", "resample"),
+                    default="all")
+    ap.add_argument("--resample-out", default=os.path.join(ROOT, "profiles", "decode_resample_rate.json"))
     ap.add_argument("--mix-out", default=os.path.join(ROOT, "profiles", "decode_mix_rate.json"))
     ap.add_argument("--bigblock-out", default=os.path.join(ROOT, "profiles", "decode_bigblock_rate.json"))
     ap.add_argument("--blocks", default="4096,4608,16384")
@@ -824,6 +892,13 @@ def main():
         print(json.dumps({"mix": mr}), flush=True)
         with open(a.mix_out, "w") as f:
             json.dump(mr, f, indent=1)
+            f.write("\n")
+        return
+    if a.legs == "resample":  # opt-in: `all` leaves it out
+        rr = {"c2": resample_rate(a.files, a.frames // a.files, a.window, a.warmup, a.repeats)}
+        print(json.dumps({"resample": rr}), flush=True)
+        with open(a.resample_out, "w") as f:
+            json.dump(rr, f, indent=1)
             f.write("\n")
         return
     if a.legs == "deliver":  # opt-in: `all` leaves it out

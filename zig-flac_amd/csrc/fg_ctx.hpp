@@ -148,6 +148,9 @@ struct WindowResult;
 namespace deliver {
 struct Delivery;
 }
+namespace resample {
+struct Ratio;
+}
 
 // shared by the translation units that include this header, not exported from libflacgpu.so
 #define FG_LOCAL __attribute__((visibility("hidden")))
@@ -197,6 +200,15 @@ hipError_t launch_window_elements(const window::Cover *recs, const streams::Stre
                                   const deliver::Delivery &dv, uint32_t n, uint64_t max_samples, hipStream_t st);
 hipError_t launch_window_results(const window::Cover *recs, const streams::StreamResult *res, window::WindowResult *out,
                                  uint32_t n, hipStream_t st);
+// fg_resample.hip: the cover and the delivery of windows stated at another sample rate
+hipError_t launch_resample_cover(const window::WindowArg *args, const idx::IndexResult *ires, const uint64_t *pos,
+                                 const uint64_t *totals, const resample::Ratio &rt, uint32_t unit, uint32_t flags,
+                                 window::Cover *recs, uint32_t n, hipStream_t st);
+// k_window_resample<dv.mix>: in place of k_window_elements, through the polyphase FIR of rt
+hipError_t launch_window_resample(const window::Cover *recs, const streams::StreamResult *res, const window::WindowArg *args,
+                                  const uint64_t *totals, const uint8_t *scratch, const uint64_t *src_base, uint8_t *out,
+                                  const uint64_t *dst_off, const deliver::Delivery &dv, const resample::Ratio &rt,
+                                  const float *coeffs, uint32_t n, uint64_t max_samples, hipStream_t st);
 // fg_misc.hip
 hipError_t launch_md5_streams(const uint8_t *base, const uint64_t *offs, const uint64_t *lens, const uint8_t *fin,
                               uint32_t n, Md5State *states, uint8_t *digests, hipStream_t st, int kernel, int prio);

@@ -3,7 +3,8 @@
 // the device index and decode (fg_dec_host.cpp decode_stream_resident), or, where the device index
 // refuses them, through the host index and flacgpu_decode_frames; flacgpu_decode_files does the
 // same for many files through one batch (fg_dec_host.cpp decode_files_resident).  Plain C++ over
-// include/flacgpu.h and the shared decode core.
+// include/flacgpu.h and the shared decode core.  And the host statement of the resampling rule
+// (fg_resample.hpp): the coefficient table of a ratio and the sample rule over F32 elements.
 #include <cstring>
 #include <vector>
 
@@ -12,6 +13,7 @@
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
 #include "fg_md5_host.hpp"
+#include "fg_resample.hpp"
 
 using namespace fg;
 
@@ -282,6 +284,49 @@ int flacgpu_decode_files_windows(flacgpu_ctx *ctx, uint32_t n_files, const void 
         n_samples[which[k]] = ns[k];
         status[which[k]] = st[k];
     }
+    return FLACGPU_OK;
+}
+
+int flacgpu_resample_filter(uint32_t src_rate, uint32_t dst_rate, uint32_t *up, uint32_t *down, uint32_t *taps, float *coeffs,
+                            size_t cap, size_t *n) {
+    resample::Ratio r;
+    if (!n || (cap && !coeffs) || !resample::valid_ratio(src_rate, dst_rate, &r)) return FLACGPU_ERR_INVALID_INPUT;
+    if (up) *up = r.L;
+    if (down) *down = r.M;
+    if (taps) *taps = r.T;
+    *n = (size_t)r.L * r.T;
+    if (*n > cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
+    double row64[resample::kMaxTaps];
+    for (uint32_t p = 0; p < r.L; p++) resample::filter_row(r, p, row64, coeffs + (size_t)p * r.T);
+    return FLACGPU_OK;
+}
+
+int flacgpu_resample_f32_host(const float *x, uint64_t total, uint32_t src_rate, uint32_t dst_rate, uint64_t start,
+                              uint64_t count, float *y, uint64_t *n) {
+    resample::Ratio r;
+    if (!n || (total && !x) || total > (1ull << 40) || !resample::valid_ratio(src_rate, dst_rate, &r))
+        return FLACGPU_ERR_INVALID_INPUT;
+    *n = 0;
+    const uint64_t got = resample::delivered(resample::out_total(r, total), start, count);
+    if (got == 0) return FLACGPU_OK;
+    if (!y) return FLACGPU_ERR_INVALID_INPUT;
+    std::vector<float> h;
+    try {
+        h.resize((size_t)r.L * r.T);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    double row64[resample::kMaxTaps];
+    for (uint32_t p = 0; p < r.L; p++) resample::filter_row(r, p, row64, h.data() + (size_t)p * r.T);
+    for (uint64_t t = 0; t < got; t++) {
+        uint32_t p;
+        const int64_t first = (int64_t)resample::source_index(r, start + t, &p) - (int64_t)r.Hw + 1;
+        y[t] = resample::fir(h.data() + (size_t)p * r.T, r.T, [&](uint32_t k) {
+            const int64_t i = first + (int64_t)k;
+            return i >= 0 && (uint64_t)i < total ? x[i] : 0.0f;
+        });
+    }
+    *n = got;
     return FLACGPU_OK;
 }
 

@@ -5,7 +5,8 @@
 // (fg_streams.hpp, fg_dec_streams.hip), and the device side of flacgpu_decode_files; and the
 // sample-window decode (fg_window.hpp, fg_window.hip): the positions of indexed streams, windows
 // over resident tables -- as PCM bytes or as tensor elements (fg_deliver.hpp) -- and the device
-// side of flacgpu_decode_files_windows.  The host-only side (metadata, the host index,
+// side of flacgpu_decode_files_windows; and the same windows stated and delivered at another
+// sample rate (fg_resample.hpp, fg_resample.hip).  The host-only side (metadata, the host index,
 // flacgpu_decode_file / _files) is fg_dec_api.cpp.
 #include <hip/hip_runtime.h>
 
@@ -19,6 +20,7 @@
 #include "fg_deliver.hpp"
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
+#include "fg_resample.hpp"
 #include "fg_streams.hpp"
 #include "fg_window.hpp"
 
@@ -59,19 +61,27 @@ struct DecScratch {
 // The window decode adds the stream table of a positions call (pos), the windows of a call as the
 // caller states them with their cover records (win_in), what the chunk loop over the covering
 // frames needs (win), those frames' PCM (win_pcm), and the delivered bytes and results of
-// flacgpu_decode_files_windows (win_out).
+// flacgpu_decode_files_windows (win_out).  The resampled delivery adds the coefficient tables of
+// the ratios it has served, one allocation each, kept until the context is closed (tables).
+struct ResampleTable {
+    uint32_t L, M;
+    float *d_coeffs;  // L rows of T
+};
 struct IdxScratch {
     uint8_t *buf = nullptr, *table = nullptr, *packed = nullptr, *files = nullptr;
     uint64_t cap = 0, table_cap = 0, packed_cap = 0, files_cap = 0;
     uint8_t *pos = nullptr, *win_in = nullptr, *win = nullptr, *win_pcm = nullptr, *win_out = nullptr;
     uint64_t pos_cap = 0, win_in_cap = 0, win_cap = 0, win_pcm_cap = 0, win_out_cap = 0;
+    std::vector<ResampleTable> tables;
 };
 
 void fg::dec_release(flacgpu_ctx *c) {
     if (DecScratch *d = c->dec)
         for (uint8_t *b : {d->buf, d->d_frames, d->d_pcm}) hipFree(b);
-    if (IdxScratch *x = c->idx)
+    if (IdxScratch *x = c->idx) {
         for (uint8_t *b : {x->buf, x->table, x->packed, x->files, x->pos, x->win_in, x->win, x->win_pcm, x->win_out}) hipFree(b);
+        for (const ResampleTable &t : x->tables) hipFree(t.d_coeffs);
+    }
     delete c->dec;
     delete c->idx;
     c->dec = nullptr;
@@ -447,6 +457,48 @@ int positions_core(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const uint
     return FLACGPU_OK;
 }
 
+// A window call that resamples: its ratio, the ratio's table on the device and the streams' totals.
+struct Resampling {
+    resample::Ratio rt;
+    const float *d_coeffs;
+    const uint64_t *d_totals;
+};
+
+// The device table of a ratio: built on the host by flacgpu_resample_filter and uploaded by the
+// first call of the context that needs it, which waits for st once more than the others; kept for
+// the context's life (dec_release).
+int resample_table(flacgpu_ctx *c, const resample::Ratio &rt, uint32_t src_rate, uint32_t dst_rate, const float **d_coeffs,
+                   hipStream_t st) {
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
+    for (const ResampleTable &t : x->tables)
+        if (t.L == rt.L && t.M == rt.M) {
+            *d_coeffs = t.d_coeffs;
+            return FLACGPU_OK;
+        }
+    std::vector<float> h;
+    size_t n = 0;
+    try {
+        h.resize((size_t)rt.L * rt.T);
+        x->tables.reserve(x->tables.size() + 1u);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    const int rc = flacgpu_resample_filter(src_rate, dst_rate, nullptr, nullptr, nullptr, h.data(), h.size(), &n);
+    if (rc) return rc;
+    float *d = nullptr;
+    HIPCHK(hipMalloc(&d, n * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(d, h.data(), n * sizeof(float), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);  // h goes out of scope
+    if (e != hipSuccess) {
+        hipFree(d);
+        return hip_err(e);
+    }
+    x->tables.push_back({rt.L, rt.M, d});
+    *d_coeffs = d;
+    return FLACGPU_OK;
+}
+
 // The windows of a call between its two halves: as uploaded, and their cover records on both sides.
 struct WindowsCall {
     uint32_t n = 0;
@@ -458,10 +510,12 @@ struct WindowsCall {
 // The first half of a window decode: the windows go to the device, k_window_cover finds their
 // covering frames, and the host waits for st ONCE to read the records.  caps[w]: the bytes of
 // window w's destination, or its elements where dv converts; TOO_SMALL is deliver::too_small's.
+// With `rs` the windows are stated in output samples of its ratio and k_resample_cover covers the
+// source samples their filter needs.
 int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexResult *d_ires, const uint64_t *d_pos,
                   const uint64_t *d_totals, uint32_t n, const uint32_t *window_stream, const uint64_t *window_start,
                   const uint64_t *window_count, const uint64_t *caps, const deliver::Delivery &dv, WindowsCall &wc,
-                  hipStream_t st) {
+                  hipStream_t st, const Resampling *rs = nullptr) {
     IdxScratch *x = idx_scratch(c);
     if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
     std::vector<window::WindowArg> args;
@@ -485,7 +539,8 @@ int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexR
     {
         Timed t(c, FLACGPU_K_SCAN, st);
         const uint32_t unit = dv.format == deliver::SAMPLE_BYTES ? dv.channels * dv.sample_bytes : dv.out_channels;
-        HIPCHK(launch_window_cover(wc.d_args, d_ires, d_pos, d_totals, unit, dv.flags, wc.d_recs, n, st));
+        if (rs) HIPCHK(launch_resample_cover(wc.d_args, d_ires, d_pos, d_totals, rs->rt, unit, dv.flags, wc.d_recs, n, st));
+        else HIPCHK(launch_window_cover(wc.d_args, d_ires, d_pos, d_totals, unit, dv.flags, wc.d_recs, n, st));
     }
     HIPCHK(hipMemcpyAsync(wc.recs.data(), wc.d_recs, (uint64_t)n * sizeof(window::Cover), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -498,11 +553,13 @@ int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexR
 // result is a scratch StreamResult.  After the last chunk k_window_copy moves each clean window's
 // bytes to d_pcm_out + out_offsets[w] -- or, where dv converts, k_window_elements (its mix
 // instantiation where dv mixes: dv.out_channels channels a sample) writes its elements from element
-// out_offsets[w] of d_pcm_out on -- and k_window_results writes d_results.
+// out_offsets[w] of d_pcm_out on -- and k_window_results writes d_results.  With `rs` a record's
+// n_samples counts output samples, its cover is that of the filter's source range, and
+// k_window_resample stands in place of k_window_elements.
 int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_first, const uint64_t *d_foff,
                    const uint32_t *d_fbytes, const WindowsCall &wc, const uint32_t *window_stream,
                    const uint64_t *window_count, const deliver::Delivery &dv, uint8_t *d_pcm_out, const uint64_t *out_offsets,
-                   window::WindowResult *d_results, hipStream_t st) {
+                   window::WindowResult *d_results, hipStream_t st, const Resampling *rs = nullptr) {
     IdxScratch *x = c->idx;
     const uint32_t n = wc.n;
     const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u);
@@ -525,7 +582,7 @@ int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_
         if (convert && r.status == window::WIN_OK)
             max_written = std::max(max_written, deliver::written_samples(r.n_samples, window_count[w], dv.flags));
         if (!decode) continue;
-        if (r.span > (1ull << 40) || r.n_samples > r.span) return FLACGPU_ERR_INVALID_INPUT;  // no stream's positions
+        if (r.span > (1ull << 40) || (!rs && r.n_samples > r.span)) return FLACGPU_ERR_INVALID_INPUT;  // no stream's positions
         frames[w] = r.n_frames;
         host[n + w] = r.span * per;
         whole += (r.span * per + 15u) & ~(uint64_t)15u;
@@ -541,7 +598,10 @@ int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_
     rc = run.run(c, d_data, d_foff, d_fbytes, x->win_pcm, whole, sres, st);
     if (rc) return rc;
     const uint64_t *d_base = run.row(0), *d_dst = run.row(3);
-    if (convert)
+    if (rs)
+        HIPCHK(launch_window_resample(wc.d_recs, sres, wc.d_args, rs->d_totals, x->win_pcm, d_base, d_pcm_out, d_dst, dv, rs->rt,
+                                      rs->d_coeffs, n, max_written, st));
+    else if (convert)
         HIPCHK(launch_window_elements(wc.d_recs, sres, wc.d_args, x->win_pcm, d_base, d_pcm_out, d_dst, dv, n, max_written, st));
     else
         HIPCHK(launch_window_copy(wc.d_recs, sres, x->win_pcm, d_base, d_pcm_out, d_dst, (uint32_t)per, n, max_bytes, st));
@@ -725,13 +785,15 @@ namespace {
 // flacgpu_decode_windows_device (format SAMPLE_BYTES, no flags: offsets and caps in bytes),
 // flacgpu_decode_windows_device_as (offsets and caps in elements) and
 // flacgpu_decode_windows_device_mix (`masks`: its out_channels channel masks, else NULL) behind
-// their own checks
+// their own checks; with src_rate != 0 flacgpu_decode_windows_device_resample: windows, offsets and
+// caps in output samples and elements at dst_rate
 int windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
                    const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes, const flacgpu_index_result *d_index_results,
                    const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples, uint32_t n_windows,
                    const uint32_t *window_stream, const uint64_t *window_start, const uint64_t *window_count,
                    uint32_t sample_format, uint32_t flags, uint32_t out_channels, const uint8_t *masks, void *d_out,
-                   const uint64_t *offsets, const uint64_t *caps, flacgpu_window_result *d_results, void *hip_stream) {
+                   const uint64_t *offsets, const uint64_t *caps, flacgpu_window_result *d_results, void *hip_stream,
+                   uint32_t src_rate = 0, uint32_t dst_rate = 0) {
     if (!c || !d_data || !table_first || !d_frame_offsets || !d_frame_bytes || !d_index_results || !d_frame_first_sample ||
         !d_stream_samples || n_windows > 65535u)
         return FLACGPU_ERR_INVALID_INPUT;
@@ -746,17 +808,23 @@ int windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, co
         dv.out_channels = out_channels;
         for (uint32_t k = 0; k < deliver::kMixMaxChannels; k++) dv.masks[k] = k < out_channels ? masks[k] : (uint8_t)0;
     }
+    Resampling rs{{0, 0, 0, 0}, nullptr, d_stream_samples};
+    if (src_rate && !resample::valid_ratio(src_rate, dst_rate, &rs.rt)) return FLACGPU_ERR_INVALID_INPUT;
     if (n_windows == 0) return FLACGPU_OK;
     HIPCHK(hipSetDevice(c->device));
     int rc = dec_scratch(c);
     if (rc) return rc;
     hipStream_t st = pick_stream(c, hip_stream);
+    if (src_rate) {
+        rc = resample_table(c, rs.rt, src_rate, dst_rate, &rs.d_coeffs, st);
+        if (rc) return rc;
+    }
     WindowsCall wc;
     rc = windows_cover(c, table_first, (const idx::IndexResult *)d_index_results, d_frame_first_sample, d_stream_samples,
-                       n_windows, window_stream, window_start, window_count, caps, dv, wc, st);
+                       n_windows, window_stream, window_start, window_count, caps, dv, wc, st, src_rate ? &rs : nullptr);
     if (rc) return rc;
     return windows_decode(c, d_data, table_first, d_frame_offsets, d_frame_bytes, wc, window_stream, window_count, dv,
-                          (uint8_t *)d_out, offsets, (window::WindowResult *)d_results, st);
+                          (uint8_t *)d_out, offsets, (window::WindowResult *)d_results, st, src_rate ? &rs : nullptr);
 }
 
 }  // namespace
@@ -804,6 +872,26 @@ int flacgpu_decode_windows_device_mix(flacgpu_ctx *c, const uint8_t *d_data, uin
                           d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
                           sample_format, flags, out_channels, channel_masks, d_out, out_offsets, out_caps, d_results,
                           hip_stream);
+}
+
+int flacgpu_decode_windows_device_resample(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams,
+                                           const uint64_t *table_first, const uint64_t *d_frame_offsets,
+                                           const uint32_t *d_frame_bytes, const flacgpu_index_result *d_index_results,
+                                           const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
+                                           uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
+                                           const uint64_t *window_count, uint32_t sample_format, uint32_t flags,
+                                           uint32_t out_channels, const uint8_t *channel_masks, uint32_t src_rate,
+                                           uint32_t dst_rate, void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
+                                           flacgpu_window_result *d_results, void *hip_stream) {
+    if (!c || sample_format >= deliver::SAMPLE_FORMATS || sample_format == deliver::SAMPLE_I32 ||
+        (flags & ~deliver::DELIVER_FLAGS) || ((uintptr_t)d_out & (deliver::elem_size(sample_format) - 1u)) ||
+        !resample::valid_ratio(src_rate, dst_rate, nullptr))
+        return FLACGPU_ERR_INVALID_INPUT;
+    if (channel_masks && (out_channels < 1u || out_channels > deliver::kMixMaxChannels)) return FLACGPU_ERR_INVALID_INPUT;
+    return windows_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results,
+                          d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
+                          sample_format, flags, out_channels, channel_masks, d_out, out_offsets, out_caps, d_results, hip_stream,
+                          src_rate, dst_rate);
 }
 
 // every chunk's frames and frame table are uploaded, its results land at results + f0

@@ -81,7 +81,8 @@ FG_HD uint32_t f32_bits(int32_t x, uint32_t bits) {
 FG_HD uint16_t bf16_bits(uint32_t f) { return (uint16_t)((f + 0x7FFFu + ((f >> 16) & 1u)) >> 16); }
 
 // f32 -> f16, round to nearest-even, subnormal results kept, by integer arithmetic on the bit
-// pattern; for |value| <= 1 (no overflow, no NaN).
+// pattern; for |value| < 65520, where the result is finite (no overflow, no NaN): a sample is at
+// most 1 in magnitude, a resampled one (fg_resample.hpp) below 4.
 FG_HD uint16_t f16_bits(uint32_t f) {
     const uint32_t sign = (f >> 16) & 0x8000u, a = f & 0x7FFFFFFFu, e = a >> 23;
     if (e >= 113u) {  // >= 2^-14, a normal f16: a rounding that carries goes into the exponent field, as it should

@@ -5,7 +5,9 @@ scanned once (flacgpu_flac_index_streams_device, flacgpu_flac_positions_streams_
 `crops` call then decodes only the frames that hold the requested samples and delivers them as
 [crop, channel, time] (or [crop, time, channel]) elements in one pass
 (flacgpu_decode_windows_device_as), on the caller's current torch stream.  Plumbing over the C ABI:
-there is no CPU path.  A bank takes no locks: one bank per thread, like a context.
+there is no CPU path.  A bank takes no locks: one bank per thread, like a context.  With a `rate`
+the crops are stated and delivered at that sample rate: those of files at another rate go through
+flacgpu_decode_windows_device_resample, one call per source rate.
 
 FlacBank holds files of one channel count and depth.  FlacMixBank holds any, as one FlacBank per
 (channels, bits), and delivers every crop with the bank's one channel count through
@@ -45,10 +47,28 @@ def _check_blocks(who: str, i: int, si) -> None:
                          f"at most {most} at {int(si.bit_depth)} bits")
 
 
-def _crops(who, device, n_files, K, groups, where, check, file, start, length, dtype, planar, pad, out, strict):
+def _rate_error(who: str, i: int, src: int, rate: int) -> Optional[str]:
+    """Why file i of rate src cannot be delivered at `rate`, or None (equal rates need no filter)."""
+    if src == rate or flacgpu.resample_ratio(src, rate) is not None:
+        return None
+    return (f"{who}: file {i} is at {src} Hz, and {src} -> {rate} is not a ratio the resampler serves "
+            f"(up and down factors of at most 1024, at most 12 to 1 down)")
+
+
+def _out_samples(samples: int, src: int, rate: int) -> int:
+    if src == rate:
+        return samples
+    L, M, _ = flacgpu.resample_ratio(src, rate)
+    return (samples * L + M - 1) // M
+
+
+def _crops(who, device, n_files, K, groups, where, check, file, start, length, dtype, planar, pad, out, strict,
+           rate=None, rate_of=None):
     """The one body of FlacBank.crops and FlacMixBank.crops: crops of K channels from `groups` =
     [(FlacBank, its channel masks or None)], file f being file where(f)[1] of group where(f)[0];
-    check(fmt): the caller's own refusals of a format, raised between the dtype's and the crops'."""
+    check(fmt): the caller's own refusals of a format, raised between the dtype's and the crops'.
+    rate: start and length are in samples at that rate, rate_of(f) being file f's own: the crops of
+    files at another rate are resampled, one call per group and source rate."""
     import torch
 
     dtype = torch.float32 if dtype is None else dtype
@@ -56,6 +76,8 @@ def _crops(who, device, n_files, K, groups, where, check, file, start, length, d
     if fmt is None:
         raise ValueError(f"{who}: dtype {dtype} is none of float32, float16, bfloat16, int32")
     check(fmt)
+    if rate is not None and fmt == flacgpu.SAMPLE_I32:
+        raise ValueError(f"{who}: int32 crops at a sample rate: a resampled sample has no integer value to deliver")
     W, length = len(file), int(length)
     if len(start) != W:
         raise ValueError(f"{who}: file and start differ in length")
@@ -65,7 +87,20 @@ def _crops(who, device, n_files, K, groups, where, check, file, start, length, d
     routed = [[] for _ in groups]  # group -> its crops, in the caller's order
     for w in range(W):
         routed[where(int(file[w]))[0]].append(w)
-    order = [w for ws in routed for w in ws]  # row r of d_res is crop order[r]
+    calls = []  # (bank, masks, the source rate to resample from or None, its crops): one library call per 65535
+    for (bank, masks), ws in zip(groups, routed):
+        if rate is None:
+            calls.append((bank, masks, None, ws))
+            continue
+        by_rate: dict = {}
+        for w in ws:
+            by_rate.setdefault(rate_of(int(file[w])), []).append(w)
+        for src, part in by_rate.items():
+            why = _rate_error(who, int(file[part[0]]), src, rate)
+            if why:
+                raise ValueError(why)
+            calls.append((bank, masks, None if src == rate else src, part))
+    order = [w for c in calls for w in c[3]]  # row r of d_res is crop order[r]
     with torch.cuda.device(device):
         if out is not None:
             if (tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous()):
@@ -79,14 +114,16 @@ def _crops(who, device, n_files, K, groups, where, check, file, start, length, d
         st = torch.cuda.current_stream(device).cuda_stream
         d_res = torch.empty(32 * max(W, 1), dtype=torch.uint8, device=device)
         per_crop, row = K * length, 0
-        for (bank, masks), ws in zip(groups, routed):
+        for bank, masks, src, ws in calls:
             for w0 in range(0, len(ws), MAX_WINDOWS):
                 part = ws[w0:w0 + MAX_WINDOWS]
                 windows = [(where(int(file[w]))[1], int(start[w]), length) for w in part]
                 tables = (bank._data.data_ptr(), bank._first, bank._off.data_ptr(), bank._fbytes.data_ptr(),
                           bank._ires.data_ptr(), bank._pos.data_ptr(), bank._totals.data_ptr(), windows, fmt, flags)
                 to = (x.data_ptr(), [w * per_crop for w in part], [per_crop] * len(part), d_res.data_ptr() + 32 * row)
-                if masks is None:
+                if src is not None:
+                    bank._dec.decode_windows_device_resample(*tables, masks, src, rate, *to, stream=st)
+                elif masks is None:
                     bank._dec.decode_windows_device_as(*tables, *to, stream=st)
                 else:
                     bank._dec.decode_windows_device_mix(*tables, masks, *to, stream=st)
@@ -200,8 +237,18 @@ class FlacBank:
     def __len__(self) -> int:
         return len(self.sample_rates)
 
+    def samples_at(self, rate: int) -> list:
+        """The samples every file holds when delivered at `rate` (ceil(samples * rate / its own rate));
+        ValueError naming the first file whose ratio to `rate` the resampler does not serve."""
+        rate = int(rate)
+        for i, src in enumerate(self.sample_rates):
+            why = _rate_error("FlacBank", i, src, rate)
+            if why:
+                raise ValueError(why)
+        return [_out_samples(n, src, rate) for n, src in zip(self.samples, self.sample_rates)]
+
     def crops(self, file: Sequence[int], start: Sequence[int], length: int, dtype=None, planar: bool = True,
-              pad: bool = True, out=None, strict: bool = True):
+              pad: bool = True, out=None, strict: bool = True, rate: Optional[int] = None):
         """Samples [start[w], start[w] + length) of file[w] for every w -> (x, n): x of shape
         [W, channels, length] (planar) or [W, length, channels] in dtype (torch.float32 -- the
         default --, float16, bfloat16: sample * 2^-(bits-1); int32: the sample), n[w] the samples
@@ -209,11 +256,17 @@ class FlacBank:
         written by the kernel with pad=True, by a memset before it with pad=False).  The work is
         queued on torch.cuda.current_stream(device); the call waits for it.  strict: raise
         FlacGpuError for the first crop whose status is not OK; strict=False returns
-        (x, n, statuses) instead.  out: a contiguous tensor of x's shape, dtype and device to fill."""
+        (x, n, statuses) instead.  out: a contiguous tensor of x's shape, dtype and device to fill.
+        rate: start and length are in samples at that sample rate (samples_at(rate) per file) and x is
+        at that rate: crops of files already at it are delivered as without it, bit for bit, the
+        others through the polyphase filter of flacgpu_decode_windows_device_resample, one call per
+        source rate (and per 65535 crops); float dtypes only; a file whose ratio to `rate` is not
+        served raises ValueError when a crop names it."""
         if self._dec is None:
             raise ValueError("FlacBank: closed")
         return _crops("FlacBank", self.device, len(self), self.channels, [(self, None)], lambda f: (0, f), lambda fmt: None,
-                      file, start, length, dtype, planar, pad, out, strict)
+                      file, start, length, dtype, planar, pad, out, strict,
+                      rate=None if rate is None else int(rate), rate_of=self.sample_rates.__getitem__)
 
 
 MIX_MAX_CHANNELS = 8
@@ -253,11 +306,14 @@ class FlacMixBank:
     flacgpu_decode_windows_device_mix with the group's channel masks: channel_map[C], a list of
     `channels` masks (bit c: source channel c; 0, 1, 2, 4 or 8 bits) for sources of C channels,
     or else the default: identity where C == channels, the one channel to every output where
-    C == 1, the mean of all where channels == 1 and C is 2, 4 or 8.  Rates are reported, never
-    converted.  A bank takes no locks: one bank per thread."""
+    C == 1, the mean of all where channels == 1 and C is 2, 4 or 8.  Without sample_rate, rates
+    are reported, never converted.  With it every crop is stated and delivered at that rate: files
+    at another rate go through flacgpu_decode_windows_device_resample (float dtypes only); `samples`
+    stays in source samples, `out_samples` counts them at sample_rate.  A bank takes no locks: one
+    bank per thread."""
 
     def __init__(self, files: Sequence[bytes], channels: int, device: int = 0, max_frames: int = 4096,
-                 channel_map: Optional[dict] = None):
+                 channel_map: Optional[dict] = None, sample_rate: Optional[int] = None):
         who, K = "FlacMixBank", int(channels)
         self._groups: list = []
         if len(files) == 0:
@@ -290,6 +346,12 @@ class FlacMixBank:
             masks_of[C] = masks
         for i, (si, _) in enumerate(parsed):
             _check_blocks(who, i, si)
+        self.sample_rate = None if sample_rate is None else int(sample_rate)
+        if self.sample_rate is not None:
+            for i, src in enumerate(self.sample_rates):
+                why = _rate_error(who, i, src, self.sample_rate)
+                if why:
+                    raise ValueError(why)
 
         # ---- everything below needs the device
         self._where = [None] * len(files)  # file -> (group, its index there)
@@ -307,6 +369,8 @@ class FlacMixBank:
             raise
         self.device = self._groups[0][0].device
         self.bits = sorted(set(self.file_bits))  # the depths the bank holds
+        if self.sample_rate is not None:
+            self.out_samples = [_out_samples(n, src, self.sample_rate) for n, src in zip(self.samples, self.sample_rates)]
 
     def close(self) -> None:
         for bank, _ in getattr(self, "_groups", []):
@@ -338,7 +402,8 @@ class FlacMixBank:
         format groups; every group queues its calls (at most 65535 windows each) on
         torch.cuda.current_stream(device) into the one x, and the call waits once per such call of
         a group that has crops, then once for the results.  A damaged frame in one file harms no
-        crop of another."""
+        crop of another.  In a bank with a sample_rate, start and length are in samples at that rate
+        (out_samples per file), a group's crops go in one call per source rate, and int32 is refused."""
         who = "FlacMixBank"
         if not self._groups:
             raise ValueError(f"{who}: closed")
@@ -355,4 +420,4 @@ class FlacMixBank:
                     raise ValueError(f"{who}: int32 crops of {bank.channels}-channel files: {why}")
 
         return _crops(who, self.device, len(self), self.channels, self._groups, self._where.__getitem__, check, file, start,
-                      length, dtype, planar, pad, out, strict)
+                      length, dtype, planar, pad, out, strict, rate=self.sample_rate, rate_of=self.sample_rates.__getitem__)

@@ -365,6 +365,11 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_decode_files_windows": (I32, [P, U32, P, P, U32, P, P, P, P, P, P, P]),
         "flacgpu_decode_windows_device_as": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, U32, P, P, P, P, P]),
         "flacgpu_decode_windows_device_mix": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, U32, U32, P, P, P, P, P, P]),
+        "flacgpu_resample_filter": (I32, [U32, U32, ctypes.POINTER(U32), ctypes.POINTER(U32), ctypes.POINTER(U32), P, SZ,
+                                          ctypes.POINTER(SZ)]),
+        "flacgpu_resample_f32_host": (I32, [P, U64, U32, U32, U64, U64, P, ctypes.POINTER(U64)]),
+        "flacgpu_decode_windows_device_resample": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, U32, U32, P, U32, U32,
+                                                         P, P, P, P, P]),
     }
     # an older build named by FLACGPU_LIB (same-box A/B runs, tools/ab.sh) may predate later entry
     # points: those stay unbound there; the in-tree library must export every one
@@ -403,6 +408,7 @@ def exported_symbols() -> list:
         "flacgpu_flac_index_streams_device", "flacgpu_decode_streams_device", "flacgpu_decode_files",
         "flacgpu_flac_positions_streams_device", "flacgpu_decode_windows_device", "flacgpu_decode_files_windows",
         "flacgpu_decode_windows_device_as", "flacgpu_open_decoder", "flacgpu_decode_windows_device_mix",
+        "flacgpu_resample_filter", "flacgpu_resample_f32_host", "flacgpu_decode_windows_device_resample",
     ]
 
 
@@ -543,6 +549,60 @@ def flac_index(buf: bytes, raw_frames: bool = False):
     return si, first.value, list(sizes)[: n.value]
 
 
+def resample_ratio(src_rate: int, dst_rate: int):
+    """(L, M, taps) of the filter that delivers src_rate at dst_rate, or None where the ratio is
+    not one flacgpu_resample_filter serves (equal rates included)."""
+    if not (0 < int(src_rate) <= 0xFFFFFFFF and 0 < int(dst_rate) <= 0xFFFFFFFF):
+        return None
+    L = load_library()
+    up, down, taps, n = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_size_t(0)
+    rc = L.flacgpu_resample_filter(int(src_rate), int(dst_rate), ctypes.byref(up), ctypes.byref(down), ctypes.byref(taps), None,
+                                   0, ctypes.byref(n))
+    return (up.value, down.value, taps.value) if rc == -4 else None  # FLACGPU_ERR_OUTPUT_TOO_SMALL: valid, and its size
+
+
+def resample_filter(src_rate: int, dst_rate: int):
+    """flacgpu_resample_filter (host only): (L, M, taps, table) of the polyphase filter that delivers
+    a stream of src_rate at dst_rate; table[p][k] a float32 numpy array of shape [L, taps].  An
+    invalid ratio (equal rates included) raises FlacGpuError."""
+    import numpy as np
+
+    r = resample_ratio(src_rate, dst_rate)
+    if r is None:
+        raise FlacGpuError(-2, f"resample_filter: {src_rate} -> {dst_rate} is not a ratio the filter serves")
+    up, down, taps = r
+    table, n = np.zeros(up * taps, dtype=np.float32), ctypes.c_size_t(0)
+    _check(load_library().flacgpu_resample_filter(src_rate, dst_rate, None, None, None, table.ctypes.data, table.size,
+                                                  ctypes.byref(n)), "resample_filter")
+    return up, down, taps, table.reshape(up, taps)
+
+
+def resample_f32_host(x, src_rate: int, dst_rate: int, start: int = 0, count: Optional[int] = None):
+    """flacgpu_resample_f32_host (host only): output samples [start, start + count) (count None: to
+    the end) of the float32 samples x of one channel at src_rate, delivered at dst_rate; a float32
+    numpy array of the samples delivered.  The statement of the rule the device follows bit for
+    bit, for callers and tests: not a decode path."""
+    import numpy as np
+
+    L = load_library()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 1:
+        raise ValueError("resample_f32_host: x is one channel of samples")
+    r = resample_ratio(src_rate, dst_rate)
+    if r is None:
+        raise FlacGpuError(-2, f"resample_f32_host: {src_rate} -> {dst_rate} is not a ratio the filter serves")
+    total = (len(x) * r[0] + r[1] - 1) // r[1]
+    if start < 0 or (count is not None and count < 0):
+        raise ValueError("resample_f32_host: start and count are not negative")
+    room = max(total - start, 0) if count is None else min(count, max(total - start, 0))
+    y = np.zeros(max(room, 1), dtype=np.float32)
+    got = ctypes.c_uint64(0)
+    _check(L.flacgpu_resample_f32_host(x.ctypes.data if len(x) else None, len(x), src_rate, dst_rate, start,
+                                       room if count is None else count, y.ctypes.data, ctypes.byref(got)),
+           "resample_f32_host")
+    return y[: got.value]
+
+
 class _DecodeOps:
     """The decode / verify entry points of a context (Encoder and Decoder share them)."""
 
@@ -646,6 +706,28 @@ class _DecodeOps:
                                d_stream_samples, windows),
             sample_format, flags, len(masks), (ctypes.c_uint8 * max(len(masks), 1))(*masks), d_out, _u64s(out_offsets),
             _u64s(out_caps), d_results, _stream(stream)), "decode_windows_device_mix")
+
+    def decode_windows_device_resample(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int,
+                                       d_frame_bytes: int, d_index_results: int, d_frame_first_sample: int,
+                                       d_stream_samples: int, windows: Sequence, sample_format: int, flags: int,
+                                       channel_masks: Optional[Sequence[int]], src_rate: int, dst_rate: int, d_out: int,
+                                       out_offsets: Sequence[int], out_caps: Sequence[int], d_results: int,
+                                       stream: Optional[int] = None) -> None:
+        """flacgpu_decode_windows_device_resample: decode_windows_device_mix at another sample rate.
+        The streams have src_rate; windows = [(stream, start, count)], offsets and caps are in output
+        samples and elements at dst_rate.  channel_masks None: the context's channels as they are."""
+        masks = None if channel_masks is None else [int(m) for m in channel_masks]
+        if masks is not None and any(not 0 <= m <= 255 for m in masks):
+            raise FlacGpuError(-2, "decode_windows_device_resample: a channel mask is not in 0..255")
+        for name, r in (("src_rate", src_rate), ("dst_rate", dst_rate)):
+            if not 0 <= int(r) <= 0xFFFFFFFF:
+                raise FlacGpuError(-2, f"decode_windows_device_resample: {name} is not in 0..2^32-1")
+        _check(self.lib.flacgpu_decode_windows_device_resample(
+            *self._window_args(d_data, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                               d_stream_samples, windows),
+            sample_format, flags, len(masks) if masks is not None else 0,
+            (ctypes.c_uint8 * max(len(masks), 1))(*masks) if masks is not None else None, int(src_rate), int(dst_rate), d_out,
+            _u64s(out_offsets), _u64s(out_caps), d_results, _stream(stream)), "decode_windows_device_resample")
 
     def decode_files_windows(self, flacs: Sequence[bytes], windows: Sequence, guard: int = 0,
                              pcm_caps: Optional[Sequence[int]] = None):
