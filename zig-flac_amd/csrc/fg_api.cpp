@@ -99,29 +99,29 @@ constexpr uint64_t kMd5ChunkBlocks = (64ull << 20) / 64;
 // overlapped encode: at most this many frame ranges per call (one ticket set of 4 u32 each)
 constexpr uint32_t kOvlMaxChunks = 64;
 
-hipEvent_t fg::get_event(flacgpu_ctx *c) {
-    if (!c->event_pool.empty()) {
-        hipEvent_t e = c->event_pool.back();
+Event fg::get_event(flacgpu_ctx *c) {
+    Event ev;
+    if (c->event_pool.empty()) {
+        ev.create();
+    } else {
+        ev = std::move(c->event_pool.back());
         c->event_pool.pop_back();
-        return e;
     }
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    return e;
+    return ev;
 }
 
 namespace {
 
 void resolve_timing(flacgpu_ctx *c) {
     for (auto &t : c->pending) {
-        hipEventSynchronize(t.stop);
+        hipEventSynchronize(t.stop.get());
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, t.start, t.stop) == hipSuccess) {
+        if (hipEventElapsedTime(&ms, t.start.get(), t.stop.get()) == hipSuccess) {
             c->launches[t.kernel]++;
             c->ms[t.kernel] += ms;
         }
-        c->event_pool.push_back(t.start);
-        c->event_pool.push_back(t.stop);
+        c->event_pool.push_back(std::move(t.start));
+        c->event_pool.push_back(std::move(t.stop));
     }
     c->pending.clear();
 }
@@ -141,6 +141,40 @@ int validate(const flacgpu_config *cfg) {
     return FLACGPU_OK;
 }
 
+// What flacgpu_open and flacgpu_open_decoder share: the device checks, then a context with its
+// shared part filled and its own stream.
+int open_shared(int device, const StreamFormat &fmt, uint32_t max_frames_per_call, std::unique_ptr<flacgpu_ctx> &c) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FLACGPU_ERR_DEVICE;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return FLACGPU_ERR_DEVICE;
+    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return FLACGPU_ERR_DEVICE;  // code objects are gfx950-only
+    HIPCHK(hipSetDevice(device));
+    c.reset(new (std::nothrow) flacgpu_ctx());
+    if (!c) return FLACGPU_ERR_OUT_OF_MEMORY;
+    c->device = device;
+    c->fmt = fmt;
+    c->max_frames = max_frames_per_call ? max_frames_per_call : 32768u;
+    c->k = knobs_from_env();
+    if (c->stream.create() != hipSuccess) return FLACGPU_ERR_DEVICE;
+    return flacgpu_md5_init(c.get());
+}
+
+// a device copy of a host table (none of an empty one)
+template <class T>
+hipError_t upload(DevBuf<T> &d, const std::vector<T> &h) {
+    if (h.empty()) return hipSuccess;
+    const hipError_t e = d.grow(h.size());
+    return e != hipSuccess ? e : hipMemcpy(d.get(), h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+// n zeroed elements
+template <class T>
+hipError_t zeroed(DevBuf<T> &d, uint64_t n) {
+    const hipError_t e = d.grow(n);
+    return e != hipSuccess ? e : hipMemset(d.get(), 0, n * sizeof(T));
+}
+
 uint64_t frames_for(uint64_t n_samples, uint32_t bs) { return (n_samples + bs - 1) / bs; }
 
 // Queue the encode of n_full full frames (jobs[0..n_full)) and n_tail short ones
@@ -148,9 +182,9 @@ uint64_t frames_for(uint64_t n_samples, uint32_t bs) { return (n_samples + bs - 
 // pack (frames written at their offsets in d_out).  full_slots: the slot of each full job
 // (NULL: slot == job index); full jobs are in increasing slot order.
 //
-// Overlapped schedule (c->ovl_chunks > 1 and enough full frames): the tail frames are analysed
+// Overlapped schedule (ovl_chunks > 1 and enough full frames): the tail frames are analysed
 // first, then the full frames in K ranges: the analysis of range i+1 runs on `st` while the scan
-// of range i's slot span (carried base: the bytes before it) and its pack run on c->ovl, each
+// of range i's slot span (carried base: the bytes before it) and its pack run on the `ovl` stream, each
 // persistent grid capped per CU so that an analysis grid and a pack grid share every CU (the
 // analysis is VALU/issue bound, the pack LDS/latency bound).  Each range has its own set of
 // frame-queue tickets.  Output bytes are identical to the serial schedule.
@@ -163,38 +197,39 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
         return FLACGPU_OK;
     }
     if (n_frames > 0xFFFFFFFFull) return FLACGPU_ERR_INVALID_INPUT;
+    EncState &e = *c->enc;
     EncodeArgs a{};
     a.pcm = d_pcm;
-    a.channels = c->g.C;
-    a.bits = c->g.bits;
-    a.bytes_per_sample = c->g.B;
-    a.sample_rate = c->cfg.sample_rate;
-    a.stereo = c->g.stereo;
-    a.max_part_order = c->cfg.max_rice_part_order;
-    a.max_param = c->cfg.max_rice_param;
-    a.lpc_order = c->cfg.prediction;
-    a.block_size = c->cfg.block_size;
+    a.channels = e.g.C;
+    a.bits = e.g.bits;
+    a.bytes_per_sample = e.g.B;
+    a.sample_rate = e.cfg.sample_rate;
+    a.stereo = e.g.stereo;
+    a.max_part_order = e.cfg.max_rice_part_order;
+    a.max_param = e.cfg.max_rice_param;
+    a.lpc_order = e.cfg.prediction;
+    a.block_size = e.cfg.block_size;
     a.desc = d_desc;
-    a.desc_stride = c->g.desc_stride;
-    a.image_bytes = c->g.image_bytes;
-    a.stage_dbuf = c->g.stage_dbuf ? 1u : 0u;
-    a.pack_dbuf = c->g.pack_dbuf ? 1u : 0u;
+    a.desc_stride = e.g.desc_stride;
+    a.image_bytes = e.g.image_bytes;
+    a.stage_dbuf = e.g.stage_dbuf ? 1u : 0u;
+    a.pack_dbuf = e.g.pack_dbuf ? 1u : 0u;
     a.enc_prio = c->k.enc_prio;
-    a.ana1_variant = c->g.ana1_variant;
+    a.ana1_variant = e.g.ana1_variant;
     a.frame_bytes = d_fbytes;
     a.offsets = d_offsets;
     a.out = d_out;
     a.out_cap = out_cap;
-    a.err = c->d_err;
-    a.work_ctr = c->d_ctr;
-    a.crc_pow = c->d_crc_pow;
-    a.crc_pow4 = c->d_crc_pow4;
-    a.crc_hmax4 = c->g.crc_hmax4;
-    a.crc_join = c->d_crc_join;
-    a.crc_hmax = c->g.crc_hmax;
-    a.records = c->records_on ? c->d_records : nullptr;
-    a.stamps = c->d_stamps;
-    a.crc_x8 = c->d_crc_x8;
+    a.err = e.d_err.get();
+    a.work_ctr = e.d_ctr.get();
+    a.crc_pow = e.d_crc_pow.get();
+    a.crc_pow4 = e.d_crc_pow4.get();
+    a.crc_hmax4 = e.g.crc_hmax4;
+    a.crc_join = e.d_crc_join.get();
+    a.crc_hmax = e.g.crc_hmax;
+    a.records = e.records_on ? e.d_records.get() : nullptr;
+    a.stamps = e.d_stamps.get();
+    a.crc_x8 = e.d_crc_x8.get();
 
     // full-frame analysis of jobs[j0, j0 + n) with ticket set `set`
     auto analyze_full = [&](uint64_t j0, uint64_t n, uint32_t set, uint32_t per_cu, hipStream_t s) -> int {
@@ -202,19 +237,19 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
         EncodeArgs h = a;
         h.jobs = d_jobs + j0;
         h.n_jobs = (uint32_t)n;
-        h.work_ctr = c->d_ctr + kCtrSet * set;
-        h.grid_reserve = c->grid_reserve;
+        h.work_ctr = e.d_ctr.get() + kCtrSet * set;
+        h.grid_reserve = e.grid_reserve;
         h.grid_per_cu = per_cu;
-        if (c->g.ana_split) {
-            h.channels = c->g.C / 2u;
+        if (e.g.ana_split) {
+            h.channels = e.g.C / 2u;
             h.ch_split = 1;
             h.xcd_queue = c->k.xcd_queue ? ((c->k.split_jit & 1u) ? 3u : 1u) : 0u;
-            HIPCHK(launch_stage(0, h, true, c->g.nt_split, c->g.lds_split, s));
+            HIPCHK(launch_stage(0, h, true, e.g.nt_split, e.g.lds_split, s));
             HIPCHK(launch_frame_totals(h, s));
-        } else if (c->g.ana1) {
+        } else if (e.g.ana1) {
             HIPCHK(launch_stage(3, h, true, 64u, (uint32_t)Ana1Layout::total, s));
         } else {
-            HIPCHK(launch_stage(0, h, true, c->g.nt, c->g.lds, s));
+            HIPCHK(launch_stage(0, h, true, e.g.nt, e.g.lds, s));
         }
         return FLACGPU_OK;
     };
@@ -223,21 +258,21 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
         EncodeArgs h = a;
         h.jobs = d_jobs + j0;
         h.n_jobs = (uint32_t)n;
-        h.work_ctr = c->d_ctr + kCtrSet * set;
-        h.grid_reserve = c->k.md5_reserve == 2 ? c->grid_reserve : 0u;
+        h.work_ctr = e.d_ctr.get() + kCtrSet * set;
+        h.grid_reserve = c->k.md5_reserve == 2 ? e.grid_reserve : 0u;
         h.grid_per_cu = per_cu;
-        if (c->g.pack_split) {
-            h.channels = c->g.C / 2u;
+        if (e.g.pack_split) {
+            h.channels = e.g.C / 2u;
             h.ch_split = 1;
-            h.image_bytes = c->g.image_split;
-            h.crc_pow4 = c->d_crc_pows;
-            h.crc_hmax4 = c->g.crc_hmaxs;
+            h.image_bytes = e.g.image_split;
+            h.crc_pow4 = e.d_crc_pows.get();
+            h.crc_hmax4 = e.g.crc_hmaxs;
             h.xcd_queue = c->k.pack_xcdq ? ((c->k.split_jit & 2u) ? 3u : 1u) : 0u;
-            HIPCHK(launch_stage(1, h, true, c->g.nt_psplit, c->g.lds_psplit, s));
-        } else if (c->g.nt_pack4) {
-            HIPCHK(launch_stage(1, h, true, c->g.nt_pack4, c->g.lds_pack4, s));
+            HIPCHK(launch_stage(1, h, true, e.g.nt_psplit, e.g.lds_psplit, s));
+        } else if (e.g.nt_pack4) {
+            HIPCHK(launch_stage(1, h, true, e.g.nt_pack4, e.g.lds_pack4, s));
         } else {
-            HIPCHK(launch_stage(1, h, true, c->g.nt_pack, c->g.lds_pack, s));
+            HIPCHK(launch_stage(1, h, true, e.g.nt_pack, e.g.lds_pack, s));
         }
         return FLACGPU_OK;
     };
@@ -246,7 +281,7 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
         EncodeArgs h = a;
         h.jobs = d_jobs + n_full;
         h.n_jobs = (uint32_t)n_tail;
-        HIPCHK(launch_stage(0, h, false, c->g.nt, c->g.lds_tail, s));
+        HIPCHK(launch_stage(0, h, false, e.g.nt, e.g.lds_tail, s));
         return FLACGPU_OK;
     };
     auto pack_tail = [&](hipStream_t s) -> int {
@@ -254,21 +289,21 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
         EncodeArgs h = a;
         h.jobs = d_jobs + n_full;
         h.n_jobs = (uint32_t)n_tail;
-        HIPCHK(launch_stage(1, h, false, c->g.nt_pack, c->g.lds_pack, s));
+        HIPCHK(launch_stage(1, h, false, e.g.nt_pack, e.g.lds_pack, s));
         return FLACGPU_OK;
     };
     // the multi-workgroup scan's per-block sums: a grow-only context buffer
     const uint32_t nb = (uint32_t)((n_frames + 4095u) / 4096u);
-    HIPCHK(grow(c->d_scan_part, c->scan_part_cap, nb));
+    HIPCHK(c->d_scan_part.grow(nb));
 
-    if (c->g.fused && n_full) {
+    if (e.g.fused && n_full) {
         // fused: the tail frames' analysis first (it publishes their sizes), then analysis + pack of
         // the full frames in one kernel whose frames find their offsets by look-back, then the scan
         // (offsets of every frame, the total) and the tail frames' pack
-        HIPCHK(grow(c->d_status, c->status_cap, n_frames));
-        HIPCHK(hipMemsetAsync(c->d_status, 0, (size_t)n_frames * 8u, st));
-        HIPCHK(hipMemsetAsync(c->d_ctr, 0, 4, st));  // the fused kernel's frame queue (ticket 0)
-        a.status = c->d_status;
+        HIPCHK(e.d_status.grow(n_frames));
+        HIPCHK(hipMemsetAsync(e.d_status.get(), 0, (size_t)n_frames * 8u, st));
+        HIPCHK(hipMemsetAsync(e.d_ctr.get(), 0, 4, st));  // the fused kernel's frame queue (ticket 0)
+        a.status = e.d_status.get();
         int rc;
         if (n_tail && (rc = analyze_tail(st))) return rc;
         {
@@ -277,59 +312,59 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
             h.jobs = d_jobs;
             h.n_jobs = (uint32_t)n_full;
             h.stage_dbuf = 0;
-            h.crc_pow4 = c->d_crc_powf;
-            h.crc_hmax4 = c->g.crc_hmaxf;
-            h.grid_reserve = c->grid_reserve;
-            HIPCHK(launch_stage(2, h, true, 256u, c->g.lds_fused, st));
+            h.crc_pow4 = e.d_crc_powf.get();
+            h.crc_hmax4 = e.g.crc_hmaxf;
+            h.grid_reserve = e.grid_reserve;
+            HIPCHK(launch_stage(2, h, true, 256u, e.g.lds_fused, st));
         }
         a.status = nullptr;
         {
             Timed t(c, FLACGPU_K_SCAN, st);
-            HIPCHK(launch_scan(d_fbytes, d_offsets, d_total, (uint32_t)n_frames, c->d_scan_part, st));
+            HIPCHK(launch_scan(d_fbytes, d_offsets, d_total, (uint32_t)n_frames, c->d_scan_part.get(), st));
         }
         if (n_tail && (rc = pack_tail(st))) return rc;
         return FLACGPU_OK;
     }
 
-    uint32_t K = c->ovl_chunks;
+    uint32_t K = e.ovl_chunks;
     if (K > kOvlMaxChunks) K = kOvlMaxChunks;
-    while (K > 1 && n_full / K < c->ovl_min_frames) K--;
+    while (K > 1 && n_full / K < e.ovl_min_frames) K--;
     if (K > 1) {
         int rc;
         if (n_tail && (rc = analyze_tail(st))) return rc;
         auto slot_of = [&](uint64_t j) -> uint64_t { return full_slots ? full_slots[j] : j; };
         auto j_begin = [&](uint32_t i) -> uint64_t { return n_full * i / K; };
-        std::vector<hipEvent_t> evs;
+        std::vector<Event> evs;
         auto release = [&]() {
-            for (auto e : evs) c->event_pool.push_back(e);
+            for (Event &ev : evs) c->event_pool.push_back(std::move(ev));
         };
         for (uint32_t i = 0; i < K; i++) {
             const uint64_t j0 = j_begin(i), j1 = j_begin(i + 1);
-            if ((rc = analyze_full(j0, j1 - j0, i, c->ovl_ana, st))) return release(), rc;
-            hipEvent_t ev = get_event(c);
+            if ((rc = analyze_full(j0, j1 - j0, i, e.ovl_ana, st))) return release(), rc;
+            evs.push_back(get_event(c));
+            const hipEvent_t ev = evs.back().get();
             if (!ev) return release(), FLACGPU_ERR_DEVICE;
-            evs.push_back(ev);
-            if (hipEventRecord(ev, st) != hipSuccess || hipStreamWaitEvent(c->ovl, ev, 0) != hipSuccess)
+            if (hipEventRecord(ev, st) != hipSuccess || hipStreamWaitEvent(e.ovl.get(), ev, 0) != hipSuccess)
                 return release(), FLACGPU_ERR_DEVICE;
             // the slot span of range i: from its first full job (0 for the first range) to the next
             // range's first full job (n_frames for the last); tail slots inside it were analysed first
             const uint64_t s0 = i == 0 ? 0 : slot_of(j0), s1 = i + 1 == K ? n_frames : slot_of(j1);
             {
-                Timed t(c, FLACGPU_K_SCAN, c->ovl);
-                if (i == 0 && hipMemsetAsync(c->d_cum, 0, sizeof(uint64_t), c->ovl) != hipSuccess)
+                Timed t(c, FLACGPU_K_SCAN, e.ovl.get());
+                if (i == 0 && hipMemsetAsync(e.d_cum.get(), 0, sizeof(uint64_t), e.ovl.get()) != hipSuccess)
                     return release(), FLACGPU_ERR_DEVICE;
-                const hipError_t e = launch_scan(d_fbytes + s0, d_offsets + s0, i + 1 == K ? d_total : c->d_cum + i + 1,
-                                                 (uint32_t)(s1 - s0), c->d_scan_part, c->ovl, c->d_cum + i);
-                if (e != hipSuccess) return release(), hip_err(e);
+                const hipError_t se = launch_scan(d_fbytes + s0, d_offsets + s0, i + 1 == K ? d_total : e.d_cum.get() + i + 1,
+                                                 (uint32_t)(s1 - s0), c->d_scan_part.get(), e.ovl.get(), e.d_cum.get() + i);
+                if (se != hipSuccess) return release(), hip_err(se);
             }
-            if ((rc = pack_full(j0, j1 - j0, i, c->ovl_pack, c->ovl))) return release(), rc;
+            if ((rc = pack_full(j0, j1 - j0, i, e.ovl_pack, e.ovl.get()))) return release(), rc;
         }
-        if (n_tail && (rc = pack_tail(c->ovl))) return release(), rc;
+        if (n_tail && (rc = pack_tail(e.ovl.get()))) return release(), rc;
         // st continues after the last pack
-        hipEvent_t done = get_event(c);
+        evs.push_back(get_event(c));
+        const hipEvent_t done = evs.back().get();
         if (!done) return release(), FLACGPU_ERR_DEVICE;
-        evs.push_back(done);
-        if (hipEventRecord(done, c->ovl) != hipSuccess || hipStreamWaitEvent(st, done, 0) != hipSuccess)
+        if (hipEventRecord(done, e.ovl.get()) != hipSuccess || hipStreamWaitEvent(st, done, 0) != hipSuccess)
             return release(), FLACGPU_ERR_DEVICE;
         release();  // the waits are enqueued: the events can be recorded again
         return FLACGPU_OK;
@@ -340,7 +375,7 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
     if (n_tail && (rc = analyze_tail(st))) return rc;
     {
         Timed t(c, FLACGPU_K_SCAN, st);
-        HIPCHK(launch_scan(d_fbytes, d_offsets, d_total, (uint32_t)n_frames, c->d_scan_part, st));
+        HIPCHK(launch_scan(d_fbytes, d_offsets, d_total, (uint32_t)n_frames, c->d_scan_part.get(), st));
     }
     if (n_full && (rc = pack_full(0, n_full, 0, 0, st))) return rc;
     if (n_tail && (rc = pack_tail(st))) return rc;
@@ -351,36 +386,38 @@ int encode_core(flacgpu_ctx *c, const uint8_t *d_pcm, const FrameJob *d_jobs, ui
 // set word is cleared for the next call.
 int device_error_code(flacgpu_ctx *c, uint32_t err) {
     if (!err) return FLACGPU_OK;
-    hipMemset(c->d_err, 0, 4);
+    hipMemset(c->enc->d_err.get(), 0, 4);
     return (err & 2u) && !(err & 1u) ? FLACGPU_ERR_OUTPUT_TOO_SMALL : FLACGPU_ERR_INTERNAL;
 }
 
 int check_device_error(flacgpu_ctx *c) {
     uint32_t err = 0;
-    HIPCHK(hipMemcpy(&err, c->d_err, 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&err, c->enc->d_err.get(), 4, hipMemcpyDeviceToHost));
     return device_error_code(c, err);
 }
 
 // Wait on the host for everything queued on st so far, through the context's event i (blocking
 // sync: the thread sleeps).
 hipError_t wait_host(flacgpu_ctx *c, hipStream_t st, int i) {
-    hipError_t e = hipEventRecord(c->hw[i], st);
-    return e != hipSuccess ? e : hipEventSynchronize(c->hw[i]);
+    const hipEvent_t ev = c->enc->hw[i].get();
+    const hipError_t e = hipEventRecord(ev, st);
+    return e != hipSuccess ? e : hipEventSynchronize(ev);
 }
 
 // check_device_error after a blocking wait on st (the pipelined path's end)
 int check_device_error_on(flacgpu_ctx *c, hipStream_t st) {
     uint32_t err = 0;
-    HIPCHK(hipMemcpyAsync(&err, c->d_err, 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(&err, c->enc->d_err.get(), 4, hipMemcpyDeviceToHost, st));
     HIPCHK(wait_host(c, st, 3));
     return device_error_code(c, err);
 }
 
 int fetch_records(flacgpu_ctx *c, uint64_t n_frames, hipStream_t st) {
-    if (!c->records_on) return FLACGPU_OK;
-    const size_t base = c->h_records.size();
-    c->h_records.resize(base + n_frames);
-    HIPCHK(hipMemcpyAsync(c->h_records.data() + base, c->d_records, n_frames * sizeof(FrameRec),
+    EncState &e = *c->enc;
+    if (!e.records_on) return FLACGPU_OK;
+    const size_t base = e.h_records.size();
+    e.h_records.resize(base + n_frames);
+    HIPCHK(hipMemcpyAsync(e.h_records.data() + base, e.d_records.get(), n_frames * sizeof(FrameRec),
                           hipMemcpyDeviceToHost, st));
     return FLACGPU_OK;
 }
@@ -391,40 +428,45 @@ int fetch_records(flacgpu_ctx *c, uint64_t n_frames, hipStream_t st) {
 // frames stay in the context's device output until ctx_download_chunk.
 int fg::ctx_encode_chunk(flacgpu_ctx *c, const uint8_t *src, uint64_t ns, uint64_t first_number, uint64_t *total,
                          uint32_t *frame_bytes) {
-    const uint32_t bs = c->cfg.block_size;
+    EncState &e = *c->enc;
+    const hipStream_t st = c->stream.get();
+    const uint32_t bs = e.cfg.block_size;
     const uint64_t nf = frames_for(ns, bs);
     if (nf > c->max_frames || !total) return FLACGPU_ERR_INVALID_INPUT;
     *total = 0;
     if (nf == 0) return FLACGPU_OK;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(c->d_pcm, src, ns * c->g.C * c->g.B, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(launch_make_jobs(c->d_jobs, ns, bs, (uint32_t)((uint64_t)bs * c->g.C * c->g.B), first_number, (uint32_t)nf,
-                            c->stream));
+    HIPCHK(hipMemcpyAsync(e.d_pcm.get(), src, ns * e.g.C * e.g.B, hipMemcpyHostToDevice, st));
+    HIPCHK(launch_make_jobs(e.d_jobs.get(), ns, bs, (uint32_t)((uint64_t)bs * e.g.C * e.g.B), first_number, (uint32_t)nf, st));
     // frames with n == 4096 take the lane-owned-partition kernel, the rest the general one
     const uint64_t n_full = (bs == (uint32_t)kBlock) ? ns / kBlock : 0;
-    int rc = encode_core(c, c->d_pcm, c->d_jobs, n_full, nf - n_full, c->d_desc, c->d_fbytes, c->d_out, c->out_cap,
-                         c->d_offsets, c->d_total, c->stream);
+    int rc = encode_core(c, e.d_pcm.get(), e.d_jobs.get(), n_full, nf - n_full, e.d_desc.get(), e.d_fbytes.get(),
+                         e.d_out.get(), e.d_out.cap(), e.d_offsets.get(), e.d_total.get(), st);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(total, c->d_total, 8, hipMemcpyDeviceToHost, c->stream));
-    if (frame_bytes) HIPCHK(hipMemcpyAsync(frame_bytes, c->d_fbytes, nf * 4, hipMemcpyDeviceToHost, c->stream));
-    if ((rc = fetch_records(c, nf, c->stream))) return rc;
-    HIPCHK(hipStreamSynchronize(c->stream));
+    HIPCHK(hipMemcpyAsync(total, e.d_total.get(), 8, hipMemcpyDeviceToHost, st));
+    if (frame_bytes) HIPCHK(hipMemcpyAsync(frame_bytes, e.d_fbytes.get(), nf * 4, hipMemcpyDeviceToHost, st));
+    if ((rc = fetch_records(c, nf, st))) return rc;
+    HIPCHK(hipStreamSynchronize(st));
     return check_device_error(c);
 }
 
 int fg::ctx_download_chunk(flacgpu_ctx *c, uint8_t *out, uint64_t total) {
     if (!total) return FLACGPU_OK;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpy(out, c->d_out, total, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, c->enc->d_out.get(), total, hipMemcpyDeviceToHost));
     return FLACGPU_OK;
 }
 
 uint32_t fg::ctx_max_frames(const flacgpu_ctx *c) { return c->max_frames; }
-bool fg::ctx_decode_only(const flacgpu_ctx *c) { return c->decode_only; }
-bool fg::ctx_plain(const flacgpu_ctx *c) { return !c->records_on && !c->timing && c->ovl_chunks <= 1 && !c->g.fused; }
+bool fg::ctx_decode_only(const flacgpu_ctx *c) { return !c->enc; }
+bool fg::ctx_plain(const flacgpu_ctx *c) {
+    const EncState &e = *c->enc;
+    return !e.records_on && !c->timing && e.ovl_chunks <= 1 && !e.g.fused;
+}
 fg::CtxDevice fg::ctx_device(const flacgpu_ctx *c) {
-    return {c->device, (void *)c->stream, c->d_out, c->d_fbytes, c->d_total, c->out_cap, c->g.C, c->g.B,
-            c->cfg.block_size};
+    const EncState &e = *c->enc;
+    return {c->device,      (void *)c->stream.get(), e.d_out.get(),           e.d_fbytes.get(), e.d_total.get(),
+            e.d_out.cap(),  c->fmt.channels,         c->fmt.bytes_per_sample, c->fmt.max_block};
 }
 void fg::ctx_finish(flacgpu_ctx *c) { resolve_timing(c); }
 
@@ -471,7 +513,9 @@ uint32_t flacgpu_build_flags(void) {
 
 int flacgpu_get_config(const flacgpu_ctx *c, flacgpu_config *out) {
     if (!c || !out) return FLACGPU_ERR_INVALID_INPUT;
-    *out = c->cfg;
+    // a decode-only context: its stream, block_size = max_block, the encode options zero
+    const flacgpu_config dec{c->fmt.sample_rate, (uint16_t)c->fmt.max_block, (uint8_t)c->fmt.channels, (uint8_t)c->fmt.bits};
+    *out = c->enc ? c->enc->cfg : dec;
     return FLACGPU_OK;
 }
 
@@ -493,174 +537,94 @@ int flacgpu_open(int device, const flacgpu_config *cfg, uint32_t max_frames_per_
     *out = nullptr;
     int rc = validate(cfg);
     if (rc) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FLACGPU_ERR_DEVICE;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return FLACGPU_ERR_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return FLACGPU_ERR_DEVICE;  // code objects are gfx950-only
-    HIPCHK(hipSetDevice(device));
+    std::unique_ptr<flacgpu_ctx> c;
+    const StreamFormat fmt{cfg->channels, cfg->bits_per_sample, cfg->bits_per_sample / 8u, cfg->sample_rate, cfg->block_size};
+    if ((rc = open_shared(device, fmt, max_frames_per_call, c))) return rc;
+    c->enc.reset(new (std::nothrow) EncState());
+    if (!c->enc) return FLACGPU_ERR_OUT_OF_MEMORY;
+    EncState &e = *c->enc;
+    e.cfg = *cfg;
+    if ((rc = enc_geometry(e.cfg, c->k, e.g))) return rc;  // a kernel's LDS does not fit
+    const EncGeom &g = e.g;
+    c->md5_kernel = g.md5_kernel;
+    e.ovl_chunks = c->k.ovl_chunks;
+    e.ovl_ana = c->k.ovl_ana;
+    e.ovl_pack = c->k.ovl_pack;
+    e.ovl_min_frames = c->k.ovl_min_frames;
 
-    auto *c = new (std::nothrow) flacgpu_ctx();
-    if (!c) return FLACGPU_ERR_OUT_OF_MEMORY;
-    c->device = device;
-    c->cfg = *cfg;
-    c->max_frames = max_frames_per_call ? max_frames_per_call : 32768u;
-    c->k = knobs_from_env();
-    if ((rc = enc_geometry(c->cfg, c->k, c->g))) {  // a kernel's LDS does not fit: no HIP resource yet
-        delete c;
-        return rc;
-    }
-    const EncGeom &g = c->g;
-    c->ovl_chunks = c->k.ovl_chunks;
-    c->ovl_ana = c->k.ovl_ana;
-    c->ovl_pack = c->k.ovl_pack;
-    c->ovl_min_frames = c->k.ovl_min_frames;
-
-    auto fail = [&](int code) {
-        flacgpu_close(c);
-        return code;
-    };
-    for (hipStream_t *s : {&c->stream, &c->aux, &c->dl, &c->up, &c->ovl})
-        if (hipStreamCreateWithFlags(s, hipStreamNonBlocking) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
+    for (Stream *s : {&e.aux, &e.dl, &e.up, &e.ovl})
+        if (s->create() != hipSuccess) return FLACGPU_ERR_DEVICE;
     const unsigned quiet = hipEventDisableTiming;
     const struct {
-        hipEvent_t *ev;
+        Event *ev;
         size_t n;
         unsigned flags;
-    } events[] = {{c->up_done, kPipeSets, quiet}, {c->set_done, kPipeSets, quiet}, {c->dl_done, kPipeSets, quiet},
-                  {&c->fork, 1, quiet},           {&c->join, 1, quiet},
-                  {c->hw, 4, c->k.spin_sync ? quiet : quiet | hipEventBlockingSync}};
+    } events[] = {{e.up_done, kPipeSets, quiet}, {e.set_done, kPipeSets, quiet}, {e.dl_done, kPipeSets, quiet},
+                  {&e.fork, 1, quiet},           {&e.join, 1, quiet},
+                  {e.hw, 4, c->k.spin_sync ? quiet : quiet | hipEventBlockingSync}};
     for (const auto &a : events)
         for (size_t i = 0; i < a.n; i++)
-            if (hipEventCreateWithFlags(&a.ev[i], a.flags) != hipSuccess) return fail(FLACGPU_ERR_DEVICE);
+            if (a.ev[i].create(a.flags) != hipSuccess) return FLACGPU_ERR_DEVICE;
 
     // the CRC fold's shifts for each pack kernel's thread count (an unused one: hmax = 0)
-    const std::vector<uint16_t> pw = crc_fold_shifts(g.nt_pack, g.crc_hmax), pw4 = crc_fold_shifts(g.nt_pack4, g.crc_hmax4),
-                                pws = crc_fold_shifts(g.nt_psplit, g.crc_hmaxs);
     std::vector<uint16_t> pj(g.crc_hmax), x8(24);
     for (uint32_t h = 1; h <= g.crc_hmax; h++) pj[h - 1] = (uint16_t)q_zpow(32ull * h);
     for (uint32_t i = 0; i < 24; i++) x8[i] = (uint16_t)crc_zpow(8ull << i);
-    if (g.crc_hmaxf) {
-        const std::vector<uint16_t> pwf = crc_fold_shifts(256u, g.crc_hmaxf);
-        if (hipMalloc(&c->d_crc_powf, pwf.size() * 2) ||
-            hipMemcpy(c->d_crc_powf, pwf.data(), pwf.size() * 2, hipMemcpyHostToDevice))
-            return fail(FLACGPU_ERR_DEVICE);
-    }
-    if (hipMalloc(&c->d_crc_pows, pws.size() * 2) || hipMalloc(&c->d_crc_x8, 48) ||
-        hipMemcpy(c->d_crc_pows, pws.data(), pws.size() * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(c->d_crc_x8, x8.data(), 48, hipMemcpyHostToDevice))
-        return fail(FLACGPU_ERR_DEVICE);
+    if (g.crc_hmaxf) HIPCHK(upload(e.d_crc_powf, crc_fold_shifts(256u, g.crc_hmaxf)));
+    HIPCHK(upload(e.d_crc_pows, crc_fold_shifts(g.nt_psplit, g.crc_hmaxs)));
+    HIPCHK(upload(e.d_crc_x8, x8));
+    HIPCHK(upload(e.d_crc_pow, crc_fold_shifts(g.nt_pack, g.crc_hmax)));
+    HIPCHK(upload(e.d_crc_pow4, crc_fold_shifts(g.nt_pack4, g.crc_hmax4)));
+    HIPCHK(upload(e.d_crc_join, pj));
 
     const uint64_t F = c->max_frames;
-    c->pcm_cap = F * (uint64_t)kBlock * g.C * g.B + 64;
-    c->out_cap = F * (uint64_t)g.image_bytes;
-    if (hipMalloc(&c->d_crc_pow, pw.size() * 2) ||
-        hipMalloc(&c->d_crc_pow4, pw4.size() * 2) ||
-        hipMalloc(&c->d_crc_join, pj.size() * 2) || hipMalloc(&c->d_err, 16) || hipMalloc(&c->d_ctr, 4u * kCtrSet * kOvlMaxChunks) ||
-        hipMalloc(&c->d_cum, 8u * (kOvlMaxChunks + 1u)) ||
-        hipMalloc(&c->d_jobs, F * sizeof(FrameJob)) || hipMalloc(&c->d_desc, F * (uint64_t)g.desc_stride) ||
-        hipMalloc(&c->d_fbytes, F * 4) || hipMalloc(&c->d_offsets, F * 8) || hipMalloc(&c->d_total, 8u * (kPipeSets + 1u)) ||
-        hipMalloc(&c->d_pcm, c->pcm_cap) || hipMalloc(&c->d_out, c->out_cap) || hipMalloc(&c->d_md5_state, 16) || hipMalloc(&c->d_stamps, 32 * 8))
-        return fail(FLACGPU_ERR_OUT_OF_MEMORY);
-    if (hipMemcpy(c->d_crc_pow, pw.data(), pw.size() * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(c->d_crc_pow4, pw4.data(), pw4.size() * 2, hipMemcpyHostToDevice) ||
-        hipMemcpy(c->d_crc_join, pj.data(), pj.size() * 2, hipMemcpyHostToDevice) || hipMemset(c->d_err, 0, 16) || hipMemset(c->d_ctr, 0, 4u * kCtrSet * kOvlMaxChunks) ||
-        hipMemset(c->d_stamps, 0, 32 * 8))
-        return fail(FLACGPU_ERR_DEVICE);
-    flacgpu_md5_init(c);
-    *out = c;
+    HIPCHK(zeroed(e.d_err, 4));
+    HIPCHK(zeroed(e.d_ctr, kCtrSet * kOvlMaxChunks));
+    HIPCHK(e.d_cum.grow(kOvlMaxChunks + 1u));
+    HIPCHK(e.d_jobs.grow(F));
+    HIPCHK(e.d_desc.grow(F * (uint64_t)g.desc_stride));
+    HIPCHK(e.d_fbytes.grow(F));
+    HIPCHK(e.d_offsets.grow(F));
+    HIPCHK(e.d_total.grow(kPipeSets + 1u));
+    HIPCHK(e.d_pcm.grow(F * (uint64_t)kBlock * g.C * g.B + 64));
+    HIPCHK(e.d_out.grow(F * (uint64_t)g.image_bytes));
+    HIPCHK(e.d_md5_state.grow(4));
+    HIPCHK(zeroed(e.d_stamps, 32));
+    *out = c.release();
     return FLACGPU_OK;
 }
 
-// A context that only decodes: the device and stream checks of flacgpu_open, its own stream, and
-// nothing else -- the decoder allocates its scratch on first use (fg_dec_host.cpp), sized by
-// cfg.block_size = max_block.  The limits are dec_geometry's: what k_dec_recon's planes hold.
+// A context that only decodes: the shared part and nothing else -- the decoder allocates its
+// scratch on first use (fg_dec_host.cpp), sized by max_block.  The limits are dec_geometry's: what
+// k_dec_recon's planes hold.
 int flacgpu_open_decoder(int device, uint32_t sample_rate, uint8_t channels, uint8_t bits_per_sample, uint32_t max_block,
                          uint32_t max_frames_per_call, flacgpu_ctx **out) {
     if (!out) return FLACGPU_ERR_INVALID_INPUT;
     *out = nullptr;
     if (sample_rate >= (1u << 20)) return FLACGPU_ERR_INVALID_CONFIG;  // u20, as flacgpu_open
     if (!dec_geometry(channels, bits_per_sample, max_block).ok) return FLACGPU_ERR_INVALID_CONFIG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return FLACGPU_ERR_DEVICE;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) != hipSuccess) return FLACGPU_ERR_DEVICE;
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return FLACGPU_ERR_DEVICE;  // code objects are gfx950-only
-    HIPCHK(hipSetDevice(device));
-    auto *c = new (std::nothrow) flacgpu_ctx();
-    if (!c) return FLACGPU_ERR_OUT_OF_MEMORY;
-    c->device = device;
-    c->decode_only = true;
-    c->cfg.sample_rate = sample_rate;
-    c->cfg.block_size = (uint16_t)max_block;  // <= FLACGPU_DECODER_MAX_BLOCK
-    c->cfg.channels = channels;
-    c->cfg.bits_per_sample = bits_per_sample;
-    c->max_frames = max_frames_per_call ? max_frames_per_call : 32768u;
-    c->k = knobs_from_env();
-    c->g.C = channels;
-    c->g.bits = bits_per_sample;
-    c->g.B = bits_per_sample / 8u;
+    std::unique_ptr<flacgpu_ctx> c;
+    const StreamFormat fmt{channels, bits_per_sample, bits_per_sample / 8u, sample_rate, max_block};
+    const int rc = open_shared(device, fmt, max_frames_per_call, c);
+    if (rc) return rc;
     // the batched MD5 of decoded streams: the kernel enc_geometry picks for this depth
-    c->g.md5_kernel = c->k.md5_kernel_set ? c->k.md5_kernel : (c->g.B == 4u ? 2 : 1);
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
-        flacgpu_close(c);
-        return FLACGPU_ERR_DEVICE;
-    }
-    flacgpu_md5_init(c);
-    *out = c;
+    c->md5_kernel = c->k.md5_kernel_set ? c->k.md5_kernel : (fmt.bytes_per_sample == 4u ? 2 : 1);
+    *out = c.release();
     return FLACGPU_OK;
 }
 
+// Deleting the context releases everything it owns, in the order its members state (fg_ctx.hpp).
 void flacgpu_close(flacgpu_ctx *c) {
     if (!c) return;
     hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
+    if (c->stream) hipStreamSynchronize(c->stream.get());
     resolve_timing(c);
-    for (auto e : c->event_pool) hipEventDestroy(e);
-    hipFree(c->d_crc_pow);
-    hipFree(c->d_crc_pow4);
-    hipFree(c->d_crc_powf);
-    hipFree(c->d_status);
-    hipFree(c->d_crc_join);
-    hipFree(c->d_scan_part);
-    dec_release(c);
-    hipFree(c->d_err);
-    hipFree(c->d_ctr);
-    hipFree(c->d_cum);
-    hipFree(c->d_jobs);
-    hipFree(c->d_desc);
-    hipFree(c->d_fbytes);
-    hipFree(c->d_offsets);
-    hipFree(c->d_total);
-    hipFree(c->d_pcm);
-    hipFree(c->d_out);
-    hipFree(c->d_records);
-    hipFree(c->d_stamps);
-    hipFree(c->d_crc_pows);
-    hipFree(c->d_crc_x8);
-    hipFree(c->d_md5_state);
-    hipFree(c->d_md5_blocks);
-    if (c->fork) hipEventDestroy(c->fork);
-    if (c->join) hipEventDestroy(c->join);
-    for (hipEvent_t e : c->hw)
-        if (e) hipEventDestroy(e);
-    if (c->aux) hipStreamDestroy(c->aux);
-    if (c->dl) hipStreamDestroy(c->dl);
-    if (c->up) hipStreamDestroy(c->up);
-    for (hipEvent_t e : c->up_done)
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->set_done)
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->dl_done)
-        if (e) hipEventDestroy(e);
-    if (c->ovl) hipStreamDestroy(c->ovl);
-    if (c->stream) hipStreamDestroy(c->stream);
     delete c;
 }
 
 // Host buffers in, host buffers out, with both PCIe directions and the encode overlapped: the
-// context's device buffers split into kPipeSets (3) chunk sets; chunk i+1 uploads on c->up while
-// chunk i encodes on c->stream and the frames of chunks i-1, i-2 download on c->dl, issued by one
+// context's device buffers split into kPipeSets (3) chunk sets; chunk i+1 uploads on `up` while
+// chunk i encodes on the context's stream and the frames of chunks i-1, i-2 download on `dl`, issued by one
 // worker thread (pageable copies block the issuing thread, so the download needs a thread of its own).
 // Output bytes and frame sizes are identical to the sequential loop; only the schedule differs.
 // The input is a list of segments (files, flacgpu_encode_files): chunks never span two, and the
@@ -677,17 +641,19 @@ struct PipeSeg {
 constexpr int kNoWorker = -1000;
 
 static int encode_pipelined(flacgpu_ctx *c, PipeSeg *segs, size_t nseg) {
-    const uint32_t bs = c->cfg.block_size;
-    const uint64_t stride = (uint64_t)bs * c->g.C * c->g.B;
+    EncState &e = *c->enc;
+    const hipStream_t st = c->stream.get();
+    const uint32_t bs = e.cfg.block_size;
+    const uint64_t stride = (uint64_t)bs * e.g.C * e.g.B;
     // chunks of at most 2048 frames (32 MiB of 16-bit stereo) so that long inputs keep both
     // PCIe directions busy; the thirds of the context's buffers hold one chunk each
     const uint32_t NS = c->k.pipe_sets;
     const uint64_t part = c->max_frames / NS;  // frames of one chunk set
     const uint64_t F = std::min<uint64_t>(part, 2048u);
-    const uint64_t pcm_half = part * kBlock * c->g.C * c->g.B;  // 16-B multiple
-    const uint64_t out_half = part * c->g.image_bytes;
+    const uint64_t pcm_half = part * kBlock * e.g.C * e.g.B;  // 16-B multiple
+    const uint64_t out_half = part * e.g.image_bytes;
     const uint64_t fb_half = part;
-    hipEvent_t *done = c->set_done;  // a chunk set's encode finished
+    const Event *done = e.set_done;  // a chunk set's encode finished
     struct Dl {
         int set;
         PipeSeg *sg;
@@ -708,16 +674,16 @@ static int encode_pipelined(flacgpu_ctx *c, PipeSeg *segs, size_t nseg) {
     auto download = [&](const Dl &d) -> int {
         PipeSeg *sg = d.sg;
         uint64_t total = 0;
-        if (hipSetDevice(c->device) != hipSuccess || hipStreamWaitEvent(c->dl, done[d.set], 0) != hipSuccess ||
-            hipMemcpyAsync(&total, c->d_total + d.set, 8, hipMemcpyDeviceToHost, c->dl) != hipSuccess ||
-            wait_host(c, c->dl, 2) != hipSuccess)
+        if (hipSetDevice(c->device) != hipSuccess || hipStreamWaitEvent(e.dl.get(), done[d.set].get(), 0) != hipSuccess ||
+            hipMemcpyAsync(&total, e.d_total.get() + d.set, 8, hipMemcpyDeviceToHost, e.dl.get()) != hipSuccess ||
+            wait_host(c, e.dl.get(), 2) != hipSuccess)
             return FLACGPU_ERR_DEVICE;
         if (sg->written + total > sg->out_cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
-        if ((sg->frame_bytes && hipMemcpyAsync(sg->frame_bytes + d.frame0, c->d_fbytes + d.set * fb_half, d.nf * 4,
-                                               hipMemcpyDeviceToHost, c->dl) != hipSuccess) ||
-            hipMemcpyAsync(sg->out + sg->written, c->d_out + d.set * out_half, total, hipMemcpyDeviceToHost, c->dl) !=
+        if ((sg->frame_bytes && hipMemcpyAsync(sg->frame_bytes + d.frame0, e.d_fbytes.get() + d.set * fb_half, d.nf * 4,
+                                               hipMemcpyDeviceToHost, e.dl.get()) != hipSuccess) ||
+            hipMemcpyAsync(sg->out + sg->written, e.d_out.get() + d.set * out_half, total, hipMemcpyDeviceToHost, e.dl.get()) !=
                 hipSuccess ||
-            hipEventRecord(c->dl_done[d.set], c->dl) != hipSuccess)
+            hipEventRecord(e.dl_done[d.set].get(), e.dl.get()) != hipSuccess)
             return FLACGPU_ERR_DEVICE;
         sg->written += total;
         return FLACGPU_OK;
@@ -764,31 +730,31 @@ static int encode_pipelined(flacgpu_ctx *c, PipeSeg *segs, size_t nseg) {
             const uint64_t nf = std::min<uint64_t>(F, total_frames - frame0);
             const uint64_t s0 = frame0 * bs;
             const uint64_t ns = std::min<uint64_t>(nf * bs, sg->n_samples - s0);
-            uint8_t *dp = c->d_pcm + set * pcm_half;
+            uint8_t *dp = e.d_pcm.get() + set * pcm_half;
             // upload: the PCM part was last read by chunk i-3's encode (its `done` event, a GPU-side
             // wait); it runs beside chunk i-1's encode and the downloads of chunks i-2, i-3
-            if ((chunk >= NS && hipStreamWaitEvent(c->up, done[set], 0) != hipSuccess) ||
-                hipMemcpyAsync(dp, sg->src + s0 * c->g.C * c->g.B, ns * c->g.C * c->g.B, hipMemcpyHostToDevice, c->up) !=
+            if ((chunk >= NS && hipStreamWaitEvent(e.up.get(), done[set].get(), 0) != hipSuccess) ||
+                hipMemcpyAsync(dp, sg->src + s0 * e.g.C * e.g.B, ns * e.g.C * e.g.B, hipMemcpyHostToDevice, e.up.get()) !=
                     hipSuccess ||
-                hipEventRecord(c->up_done[set], c->up) != hipSuccess) {
+                hipEventRecord(e.up_done[set].get(), e.up.get()) != hipSuccess) {
                 rc = FLACGPU_ERR_DEVICE;
                 break;
             }
             // the encode writes the output part chunk i-3's download reads: that download first
             // (issued by the worker: then the encode stream waits for its copies on the GPU)
             if (chunk >= NS && (rc = wait_done(chunk - NS + 1))) break;
-            if ((chunk >= NS && hipStreamWaitEvent(c->stream, c->dl_done[set], 0) != hipSuccess) ||
-                hipStreamWaitEvent(c->stream, c->up_done[set], 0) != hipSuccess ||
-                launch_make_jobs(c->d_jobs, ns, bs, (uint32_t)stride, sg->first_frame_number + frame0, (uint32_t)nf,
-                                 c->stream) != hipSuccess) {
+            if ((chunk >= NS && hipStreamWaitEvent(st, e.dl_done[set].get(), 0) != hipSuccess) ||
+                hipStreamWaitEvent(st, e.up_done[set].get(), 0) != hipSuccess ||
+                launch_make_jobs(e.d_jobs.get(), ns, bs, (uint32_t)stride, sg->first_frame_number + frame0, (uint32_t)nf,
+                                 st) != hipSuccess) {
                 rc = FLACGPU_ERR_DEVICE;
                 break;
             }
             const uint64_t n_full = (bs == (uint32_t)kBlock) ? ns / kBlock : 0;
-            if ((rc = encode_core(c, dp, c->d_jobs, n_full, nf - n_full, c->d_desc, c->d_fbytes + set * fb_half,
-                                  c->d_out + set * out_half, out_half, c->d_offsets, c->d_total + set, c->stream)))
+            if ((rc = encode_core(c, dp, e.d_jobs.get(), n_full, nf - n_full, e.d_desc.get(), e.d_fbytes.get() + set * fb_half,
+                                  e.d_out.get() + set * out_half, out_half, e.d_offsets.get(), e.d_total.get() + set, st)))
                 break;
-            if (hipEventRecord(done[set], c->stream) != hipSuccess) {
+            if (hipEventRecord(done[set].get(), st) != hipSuccess) {
                 rc = FLACGPU_ERR_DEVICE;
                 break;
             }
@@ -807,20 +773,21 @@ static int encode_pipelined(flacgpu_ctx *c, PipeSeg *segs, size_t nseg) {
     cv.notify_all();
     worker.join();
     if (rc == FLACGPU_OK) rc = wrc;
-    const hipError_t se = hipStreamSynchronize(c->dl);  // the last chunks' copies
+    const hipError_t se = hipStreamSynchronize(e.dl.get());  // the last chunks' copies
     if (rc == FLACGPU_OK && se != hipSuccess) rc = FLACGPU_ERR_DEVICE;
     if (rc) {
-        hipStreamSynchronize(c->up);
-        hipStreamSynchronize(c->stream);
+        hipStreamSynchronize(e.up.get());
+        hipStreamSynchronize(st);
         return rc;
     }
-    return check_device_error_on(c, c->stream);
+    return check_device_error_on(c, st);
 }
 
 }  // extern "C"
 
 int fg::ctx_encode_segments(flacgpu_ctx *c, uint32_t n, const uint8_t *const *src, const uint64_t *n_samples,
                             uint8_t *const *out, const size_t *out_cap, size_t *out_len, uint32_t *const *frame_bytes) {
+    EncState &e = *c->enc;
     HIPCHK(hipSetDevice(c->device));
     // contexts the pipeline cannot serve (one frame per call, decision records on), or no thread
     // for its downloads: each file through flacgpu_encode_frames, which is what
@@ -829,21 +796,21 @@ int fg::ctx_encode_segments(flacgpu_ctx *c, uint32_t n, const uint8_t *const *sr
         for (uint32_t i = 0; i < n; i++) out_len[i] = 0;
         // with decision records on, the records of EVERY file are kept, file after file in frame
         // order (flacgpu_get_records), not only the last file's
-        if (c->records_on) c->h_records.clear();
-        c->records_keep = true;
+        if (e.records_on) e.h_records.clear();
+        e.records_keep = true;
         for (uint32_t i = 0; i < n; i++) {
-            const int r = flacgpu_encode_frames(c, src[i], c->g.B, n_samples[i], 0, out[i], out_cap[i], &out_len[i],
+            const int r = flacgpu_encode_frames(c, src[i], e.g.B, n_samples[i], 0, out[i], out_cap[i], &out_len[i],
                                                 frame_bytes ? frame_bytes[i] : nullptr);
             if (r) {
-                c->records_keep = false;
+                e.records_keep = false;
                 for (uint32_t j = 0; j < n; j++) out_len[j] = 0;
                 return r;
             }
         }
-        c->records_keep = false;
+        e.records_keep = false;
         return FLACGPU_OK;
     };
-    if (c->max_frames < c->k.pipe_sets || c->records_on) return one_by_one();
+    if (c->max_frames < c->k.pipe_sets || e.records_on) return one_by_one();
     std::vector<PipeSeg> segs;
     try {
         segs.resize(n);
@@ -851,7 +818,7 @@ int fg::ctx_encode_segments(flacgpu_ctx *c, uint32_t n, const uint8_t *const *sr
         return FLACGPU_ERR_OUT_OF_MEMORY;
     }
     for (uint32_t i = 0; i < n; i++) {
-        const uint64_t nf = frames_for(n_samples[i], c->cfg.block_size);
+        const uint64_t nf = frames_for(n_samples[i], e.cfg.block_size);
         if (nf && nf - 1 > (1ull << 36) - 1) return FLACGPU_ERR_INVALID_INPUT;  // u36 frame numbers
         segs[i] = PipeSeg{src[i], n_samples[i], 0, out[i], out_cap[i], 0, frame_bytes ? frame_bytes[i] : nullptr};
     }
@@ -869,10 +836,11 @@ int flacgpu_encode_frames(flacgpu_ctx *c, const void *pcm, uint32_t bytes_per_sa
                           uint32_t *frame_bytes) {
     if (!c || (!pcm && n_samples) || !out_len) return FLACGPU_ERR_INVALID_INPUT;
     FG_ENCODER_ONLY(c);
-    if (bytes_per_sample != c->g.B) return FLACGPU_ERR_INVALID_INPUT;
+    EncState &e = *c->enc;
+    if (bytes_per_sample != e.g.B) return FLACGPU_ERR_INVALID_INPUT;
     HIPCHK(hipSetDevice(c->device));
     *out_len = 0;
-    const uint32_t bs = c->cfg.block_size;
+    const uint32_t bs = e.cfg.block_size;
     const uint64_t total_frames = frames_for(n_samples, bs);
     // frame numbers are u36 (frame_writer.zig:153, wav2flac.zig:75)
     if (total_frames && (first_frame_number >= (1ull << 36) || total_frames - 1 > (1ull << 36) - 1 - first_frame_number))
@@ -880,8 +848,8 @@ int flacgpu_encode_frames(flacgpu_ctx *c, const void *pcm, uint32_t bytes_per_sa
     const uint8_t *src = (const uint8_t *)pcm;
     uint64_t frame0 = 0;
     size_t written = 0;
-    if (c->records_on && !c->records_keep) c->h_records.clear();
-    if (!c->records_on && c->max_frames >= c->k.pipe_sets &&
+    if (e.records_on && !e.records_keep) e.h_records.clear();
+    if (!e.records_on && c->max_frames >= c->k.pipe_sets &&
         total_frames > std::min<uint64_t>(c->max_frames / c->k.pipe_sets, 2048u)) {
         PipeSeg seg{src, n_samples, first_frame_number, out, out_cap, 0, frame_bytes};
         const int rc = encode_pipelined(c, &seg, 1);
@@ -896,7 +864,7 @@ int flacgpu_encode_frames(flacgpu_ctx *c, const void *pcm, uint32_t bytes_per_sa
         const uint64_t s0 = frame0 * bs;
         const uint64_t ns = std::min<uint64_t>(nf * bs, n_samples - s0);
         uint64_t total = 0;
-        int rc = fg::ctx_encode_chunk(c, src + s0 * c->g.C * c->g.B, ns, first_frame_number + frame0, &total,
+        int rc = fg::ctx_encode_chunk(c, src + s0 * e.g.C * e.g.B, ns, first_frame_number + frame0, &total,
                                       frame_bytes ? frame_bytes + frame0 : nullptr);
         if (rc) return rc;
         if (written + total > out_cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
@@ -913,20 +881,21 @@ int flacgpu_encode_frame_planar(flacgpu_ctx *c, const int32_t *const planes[8], 
                                 uint8_t *out, size_t out_cap, uint32_t *frame_bytes) {
     if (!c) return FLACGPU_ERR_INVALID_INPUT;
     FG_ENCODER_ONLY(c);
-    if (!planes || !out || n == 0 || n > c->cfg.block_size) return FLACGPU_ERR_INVALID_INPUT;
-    for (uint32_t ch = 0; ch < c->g.C; ch++)
+    EncState &e = *c->enc;
+    if (!planes || !out || n == 0 || n > e.cfg.block_size) return FLACGPU_ERR_INVALID_INPUT;
+    for (uint32_t ch = 0; ch < e.g.C; ch++)
         if (!planes[ch]) return FLACGPU_ERR_INVALID_INPUT;
     // Encoder.samples[ch][0..n] -> the little-endian interleaved layout the kernels stage
-    std::vector<uint8_t> pcm((size_t)n * c->g.C * c->g.B + 4);
+    std::vector<uint8_t> pcm((size_t)n * e.g.C * e.g.B + 4);
     for (uint32_t i = 0; i < n; i++)
-        for (uint32_t ch = 0; ch < c->g.C; ch++) {
+        for (uint32_t ch = 0; ch < e.g.C; ch++) {
             const uint32_t v = (uint32_t)planes[ch][i];
-            uint8_t *d = &pcm[((size_t)i * c->g.C + ch) * c->g.B];
-            for (uint32_t k = 0; k < c->g.B; k++) d[k] = (uint8_t)(v >> (8 * k));
+            uint8_t *d = &pcm[((size_t)i * e.g.C + ch) * e.g.B];
+            for (uint32_t k = 0; k < e.g.B; k++) d[k] = (uint8_t)(v >> (8 * k));
         }
     size_t len = 0;
     uint32_t fb = 0;
-    int rc = flacgpu_encode_frames(c, pcm.data(), c->g.B, n, frame_number, out, out_cap, &len, &fb);
+    int rc = flacgpu_encode_frames(c, pcm.data(), e.g.B, n, frame_number, out, out_cap, &len, &fb);
     if (rc) return rc;
     if (frame_bytes) *frame_bytes = fb;
     return FLACGPU_OK;
@@ -945,27 +914,29 @@ int flacgpu_md5_get_engine(const flacgpu_ctx *c) { return c ? c->md5_engine : FL
 int flacgpu_md5_init(flacgpu_ctx *c) {
     if (!c) return FLACGPU_ERR_INVALID_INPUT;
     c->host_md5.reset();
-    c->md5_fill = 0;
-    c->md5_len = 0;
     if (c->md5_engine != FLACGPU_MD5_DEVICE) return FLACGPU_OK;
+    EncState &e = *c->enc;
+    e.md5_fill = 0;
+    e.md5_len = 0;
     const uint32_t iv[4] = {0x67452301u, 0xefcdab89u, 0x98badcfeu, 0x10325476u};
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpy(c->d_md5_state, iv, 16, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e.d_md5_state.get(), iv, 16, hipMemcpyHostToDevice));
     return FLACGPU_OK;
 }
 
 // device engine: whole blocks through one bounded buffer (kMd5ChunkBlocks per launch)
 static int md5_push_blocks(flacgpu_ctx *c, const uint8_t *p, uint64_t nblocks) {
     if (!nblocks) return FLACGPU_OK;
-    if (!c->d_md5_blocks) HIPCHK(hipMalloc(&c->d_md5_blocks, kMd5ChunkBlocks * 64));
+    EncState &e = *c->enc;
+    HIPCHK(e.d_md5_blocks.grow(kMd5ChunkBlocks * 16u));  // the first call allocates
     for (uint64_t b = 0; b < nblocks; b += kMd5ChunkBlocks) {
         const uint64_t nb = std::min<uint64_t>(kMd5ChunkBlocks, nblocks - b);
-        HIPCHK(hipMemcpyAsync(c->d_md5_blocks, p + b * 64, nb * 64, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(e.d_md5_blocks.get(), p + b * 64, nb * 64, hipMemcpyHostToDevice, c->stream.get()));
         {
-            Timed t(c, FLACGPU_K_MD5, c->stream);
-            HIPCHK(launch_md5_blocks(c->d_md5_state, c->d_md5_blocks, nb, c->stream));
+            Timed t(c, FLACGPU_K_MD5, c->stream.get());
+            HIPCHK(launch_md5_blocks(e.d_md5_state.get(), e.d_md5_blocks.get(), nb, c->stream.get()));
         }
-        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream.get()));
     }
     return FLACGPU_OK;
 }
@@ -976,19 +947,20 @@ int flacgpu_md5_update(flacgpu_ctx *c, const void *data, size_t len) {
         c->host_md5.update(data, len);
         return FLACGPU_OK;
     }
+    EncState &e = *c->enc;
     HIPCHK(hipSetDevice(c->device));
     const uint8_t *p = (const uint8_t *)data;
-    c->md5_len += len;
-    if (c->md5_fill) {
-        const size_t take = std::min<size_t>(64 - c->md5_fill, len);
-        std::memcpy(c->md5_buf + c->md5_fill, p, take);
-        c->md5_fill += (uint32_t)take;
+    e.md5_len += len;
+    if (e.md5_fill) {
+        const size_t take = std::min<size_t>(64 - e.md5_fill, len);
+        std::memcpy(e.md5_buf + e.md5_fill, p, take);
+        e.md5_fill += (uint32_t)take;
         p += take;
         len -= take;
-        if (c->md5_fill == 64) {
-            int rc = md5_push_blocks(c, c->md5_buf, 1);
+        if (e.md5_fill == 64) {
+            int rc = md5_push_blocks(c, e.md5_buf, 1);
             if (rc) return rc;
-            c->md5_fill = 0;
+            e.md5_fill = 0;
         }
     }
     const uint64_t nb = len / 64;
@@ -996,8 +968,8 @@ int flacgpu_md5_update(flacgpu_ctx *c, const void *data, size_t len) {
     if (rc) return rc;
     p += nb * 64;
     len -= nb * 64;
-    std::memcpy(c->md5_buf, p, len);
-    c->md5_fill = (uint32_t)len;
+    std::memcpy(e.md5_buf, p, len);
+    e.md5_fill = (uint32_t)len;
     return FLACGPU_OK;
 }
 
@@ -1007,17 +979,18 @@ int flacgpu_md5_final(flacgpu_ctx *c, uint8_t digest[16]) {
         c->host_md5.final(digest);
         return FLACGPU_OK;
     }
+    EncState &e = *c->enc;
     HIPCHK(hipSetDevice(c->device));
     uint8_t tail[128] = {};
-    std::memcpy(tail, c->md5_buf, c->md5_fill);
-    tail[c->md5_fill] = 0x80;
-    const uint32_t nb = c->md5_fill < 56 ? 1 : 2;
-    const uint64_t bits = c->md5_len * 8;
+    std::memcpy(tail, e.md5_buf, e.md5_fill);
+    tail[e.md5_fill] = 0x80;
+    const uint32_t nb = e.md5_fill < 56 ? 1 : 2;
+    const uint64_t bits = e.md5_len * 8;
     for (int i = 0; i < 8; i++) tail[nb * 64 - 8 + i] = (uint8_t)(bits >> (8 * i));
     int rc = md5_push_blocks(c, tail, nb);
     if (rc) return rc;
     uint32_t st[4];
-    HIPCHK(hipMemcpy(st, c->d_md5_state, 16, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(st, e.d_md5_state.get(), 16, hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; i++)
         for (int j = 0; j < 4; j++) digest[4 * i + j] = (uint8_t)(st[i] >> (8 * j));
     resolve_timing(c);
@@ -1209,10 +1182,11 @@ int flacgpu_plan_create_segments(flacgpu_ctx *c, uint32_t n_streams, const uint6
     if (!c || !out) return FLACGPU_ERR_INVALID_INPUT;
     *out = nullptr;
     FG_ENCODER_ONLY(c);  // no plan exists on a decode-only context, so nothing that takes one runs on it
-    if ((n_streams && (!offs || !samples)) || bytes_per_sample != c->g.B) return FLACGPU_ERR_INVALID_INPUT;
+    EncState &e = *c->enc;
+    if ((n_streams && (!offs || !samples)) || bytes_per_sample != e.g.B) return FLACGPU_ERR_INVALID_INPUT;
     HIPCHK(hipSetDevice(c->device));
-    const uint32_t bs = c->cfg.block_size;
-    const uint64_t fbytes_in = (uint64_t)c->g.C * c->g.B;
+    const uint32_t bs = e.cfg.block_size;
+    const uint64_t fbytes_in = (uint64_t)e.g.C * e.g.B;
     std::vector<FrameJob> full, tail;
     std::vector<uint64_t> lens(n_streams);
     uint64_t max_number = 0;
@@ -1228,7 +1202,7 @@ int flacgpu_plan_create_segments(flacgpu_ctx *c, uint32_t n_streams, const uint6
         if (final_segment && !final_segment[s] && (samples[s] % bs || (samples[s] * fbytes_in) % 64))
             return FLACGPU_ERR_INVALID_INPUT;
     }
-    auto *p = new (std::nothrow) flacgpu_plan();
+    std::unique_ptr<flacgpu_plan> p(new (std::nothrow) flacgpu_plan());
     if (!p) return FLACGPU_ERR_OUT_OF_MEMORY;
     p->ctx = c;
     p->n_streams = n_streams;
@@ -1259,37 +1233,25 @@ int flacgpu_plan_create_segments(flacgpu_ctx *c, uint32_t n_streams, const uint6
         p->h_md5_lens = lens;
         if (final_segment) p->h_md5_fin.assign(final_segment, final_segment + n_streams);
     } catch (...) {
-        delete p;
         return FLACGPU_ERR_OUT_OF_MEMORY;
     }
     p->n_frames = slot;
     p->n_full = full.size() - tail.size();
     p->n_tail = tail.size();
-    p->out_bound = slot * (uint64_t)c->g.image_bytes;
-    auto fail = [&](int code) {
-        flacgpu_plan_destroy(p);
-        return code;
-    };
-    if (slot > 0xFFFFFFFFull) return fail(FLACGPU_ERR_INVALID_INPUT);
-    if (slot) {
-        if (hipMalloc(&p->d_jobs, slot * sizeof(FrameJob))) return fail(FLACGPU_ERR_OUT_OF_MEMORY);
-        if (hipMemcpy(p->d_jobs, full.data(), slot * sizeof(FrameJob), hipMemcpyHostToDevice))
-            return fail(FLACGPU_ERR_DEVICE);
-    }
+    p->out_bound = slot * (uint64_t)e.g.image_bytes;
+    if (slot > 0xFFFFFFFFull) return FLACGPU_ERR_INVALID_INPUT;
+    HIPCHK(upload(p->d_jobs, full));
     if (n_streams) {
-        if (hipMalloc(&p->d_md5_offs, n_streams * 8) || hipMalloc(&p->d_md5_lens, n_streams * 8))
-            return fail(FLACGPU_ERR_OUT_OF_MEMORY);
-        if (hipMemcpy(p->d_md5_offs, offs, n_streams * 8, hipMemcpyHostToDevice) ||
-            hipMemcpy(p->d_md5_lens, lens.data(), n_streams * 8, hipMemcpyHostToDevice))
-            return fail(FLACGPU_ERR_DEVICE);
+        HIPCHK(p->d_md5_offs.grow(n_streams));
+        HIPCHK(hipMemcpy(p->d_md5_offs.get(), offs, n_streams * 8, hipMemcpyHostToDevice));
+        HIPCHK(upload(p->d_md5_lens, lens));
         if (final_segment) {
-            if (hipMalloc(&p->d_md5_fin, n_streams)) return fail(FLACGPU_ERR_OUT_OF_MEMORY);
-            if (hipMemcpy(p->d_md5_fin, final_segment, n_streams, hipMemcpyHostToDevice)) return fail(FLACGPU_ERR_DEVICE);
+            HIPCHK(p->d_md5_fin.grow(n_streams));
+            HIPCHK(hipMemcpy(p->d_md5_fin.get(), final_segment, n_streams, hipMemcpyHostToDevice));
         }
     }
-    if (slot > c->max_frames && hipMalloc(&p->d_desc, slot * (uint64_t)c->g.desc_stride))
-        return fail(FLACGPU_ERR_OUT_OF_MEMORY);
-    *out = p;
+    if (slot > c->max_frames) HIPCHK(p->d_desc.grow(slot * (uint64_t)e.g.desc_stride));
+    *out = p.release();
     return FLACGPU_OK;
 }
 
@@ -1298,15 +1260,7 @@ int flacgpu_plan_create(flacgpu_ctx *c, uint32_t n_streams, const uint64_t *offs
     return flacgpu_plan_create_segments(c, n_streams, offs, samples, bytes_per_sample, nullptr, nullptr, out);
 }
 
-void flacgpu_plan_destroy(flacgpu_plan *p) {
-    if (!p) return;
-    hipFree(p->d_jobs);
-    hipFree(p->d_md5_offs);
-    hipFree(p->d_md5_lens);
-    hipFree(p->d_md5_fin);
-    hipFree(p->d_desc);
-    delete p;
-}
+void flacgpu_plan_destroy(flacgpu_plan *p) { delete p; }
 
 uint64_t flacgpu_plan_frames(const flacgpu_plan *p) { return p ? p->n_frames : 0; }
 uint64_t flacgpu_plan_out_bound(const flacgpu_plan *p) { return p ? p->out_bound : 0; }
@@ -1321,7 +1275,7 @@ int flacgpu_plan_advance(flacgpu_plan *p, uint64_t frames, void *hip_stream) {
     flacgpu_ctx *c = p->ctx;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick_stream(c, hip_stream);
-    HIPCHK(launch_advance_jobs(p->d_jobs, p->n_frames, frames, st));
+    HIPCHK(launch_advance_jobs(p->d_jobs.get(), p->n_frames, frames, st));
     p->max_number += frames;
     return FLACGPU_OK;
 }
@@ -1332,43 +1286,45 @@ int flacgpu_encode_plan_device_ex(flacgpu_ctx *c, const flacgpu_plan *p, const v
                                   void *md5_stream) {
     if (!c) return FLACGPU_ERR_INVALID_INPUT;
     FG_ENCODER_ONLY(c);
+    EncState &e = *c->enc;
     if (!p || p->ctx != c || !d_pcm || !d_out || !d_frame_bytes || !d_frame_offsets || !d_total)
         return FLACGPU_ERR_INVALID_INPUT;
     // a stream that continues past this segment has no digest yet: its state must be carried
-    if (p->d_md5_fin && d_md5 && !d_md5_state) return FLACGPU_ERR_INVALID_INPUT;
+    if (p->d_md5_fin.get() && d_md5 && !d_md5_state) return FLACGPU_ERR_INVALID_INPUT;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick_stream(c, hip_stream);
-    if (c->records_on && p->n_frames > c->max_frames) return FLACGPU_ERR_INVALID_INPUT;
-    uint8_t *desc = p->d_desc ? p->d_desc : c->d_desc;
+    if (e.records_on && p->n_frames > c->max_frames) return FLACGPU_ERR_INVALID_INPUT;
+    uint8_t *desc = p->d_desc.get() ? p->d_desc.get() : e.d_desc.get();
     // MD5 of every stream on a second stream, overlapping the encode kernels (joined back into
     // st unless the caller owns the MD5 stream)
     const bool join = md5_stream == nullptr;
-    hipStream_t ms = join ? c->aux : pick_stream(c, md5_stream);
+    hipStream_t ms = join ? e.aux.get() : pick_stream(c, md5_stream);
     const bool md5 = (d_md5 || d_md5_state) && p->n_streams;
     if (md5) {
-        hipEvent_t fork = join ? c->fork : get_event(c);
+        Event pooled = join ? Event() : get_event(c);
+        const hipEvent_t fork = join ? e.fork.get() : pooled.get();
         if (!fork) return FLACGPU_ERR_DEVICE;
         HIPCHK(hipEventRecord(fork, st));
         HIPCHK(hipStreamWaitEvent(ms, fork, 0));
-        if (!join) c->event_pool.push_back(fork);  // recycled: the wait is already enqueued
+        if (!join) c->event_pool.push_back(std::move(pooled));  // recycled: the wait is already enqueued
         {
             Timed t(c, FLACGPU_K_MD5, ms);
-            HIPCHK(launch_md5_streams((const uint8_t *)d_pcm, p->d_md5_offs, p->d_md5_lens, p->d_md5_fin, p->n_streams,
-                                      (Md5State *)d_md5_state, d_md5, ms, c->g.md5_kernel, c->k.md5_prio));
+            HIPCHK(launch_md5_streams((const uint8_t *)d_pcm, p->d_md5_offs.get(), p->d_md5_lens.get(), p->d_md5_fin.get(),
+                                      p->n_streams, (Md5State *)d_md5_state, d_md5, ms, c->md5_kernel, c->k.md5_prio));
         }
-        if (join) HIPCHK(hipEventRecord(c->join, ms));
+        if (join) HIPCHK(hipEventRecord(e.join.get(), ms));
     }
     // the MD5 workgroups were queued first: the encode kernels' persistent grids leave their slots
     // auto: only for long chains (>= 4096 blocks per stream per call, e.g. c4's 4 x 96-KiB frames).  A
     // persistent grid cannot grow back, so the reserved slots idle once the MD5 is done; a shorter
     // chain started late (after the analysis) still ends before the pack
     const bool reserve = c->k.md5_reserve > 0 || (c->k.md5_reserve < 0 && p->md5_max_len >= (256u << 10));
-    c->grid_reserve = (md5 && reserve) ? md5_workgroups(p->n_streams, c->g.md5_kernel) : 0u;
-    int rc = encode_core(c, (const uint8_t *)d_pcm, p->d_jobs, p->n_full, p->n_tail, desc, d_frame_bytes, d_out,
+    e.grid_reserve = (md5 && reserve) ? md5_workgroups(p->n_streams, c->md5_kernel) : 0u;
+    int rc = encode_core(c, (const uint8_t *)d_pcm, p->d_jobs.get(), p->n_full, p->n_tail, desc, d_frame_bytes, d_out,
                          out_cap, d_frame_offsets, d_total, st, p->full_slots.data());
-    c->grid_reserve = 0;
+    e.grid_reserve = 0;
     if (rc) return rc;
-    if (join && md5) HIPCHK(hipStreamWaitEvent(st, c->join, 0));
+    if (join && md5) HIPCHK(hipStreamWaitEvent(st, e.join.get(), 0));
     return FLACGPU_OK;
 }
 
@@ -1399,7 +1355,7 @@ int flacgpu_sync_check(flacgpu_ctx *c, void *hip_stream) {
     if (!c) return FLACGPU_ERR_INVALID_INPUT;
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(pick_stream(c, hip_stream)));
-    if (c->decode_only) return FLACGPU_OK;  // the error word is the encode kernels': decode statuses are per frame
+    if (!c->enc) return FLACGPU_OK;  // the error word is the encode kernels': decode statuses are per frame
     return check_device_error(c);
 }
 
@@ -1433,30 +1389,32 @@ int flacgpu_set_overlap(flacgpu_ctx *c, uint32_t ranges, uint32_t ana_per_cu, ui
                         uint32_t min_frames) {
     if (!c || ranges > kOvlMaxChunks || min_frames == 0) return FLACGPU_ERR_INVALID_INPUT;
     FG_ENCODER_ONLY(c);
+    EncState &e = *c->enc;
     // the overlapped schedule measured slower: diagnostic builds only
     if (!FG_DIAG && ranges > 1) return FLACGPU_ERR_INVALID_CONFIG;
-    c->ovl_chunks = ranges;
-    c->ovl_ana = ana_per_cu;
-    c->ovl_pack = pack_per_cu;
-    c->ovl_min_frames = min_frames;
+    e.ovl_chunks = ranges;
+    e.ovl_ana = ana_per_cu;
+    e.ovl_pack = pack_per_cu;
+    e.ovl_min_frames = min_frames;
     return FLACGPU_OK;
 }
 
 int flacgpu_set_records(flacgpu_ctx *c, int enable) {
     if (!c) return FLACGPU_ERR_INVALID_INPUT;
     FG_ENCODER_ONLY(c);
+    EncState &e = *c->enc;
     HIPCHK(hipSetDevice(c->device));
-    if (enable && !c->d_records) HIPCHK(hipMalloc(&c->d_records, (uint64_t)c->max_frames * sizeof(FrameRec)));
-    if (enable) HIPCHK(hipMemset(c->d_records, 0, (uint64_t)c->max_frames * sizeof(FrameRec)));
-    c->records_on = enable != 0;
+    if (enable) HIPCHK(zeroed(e.d_records, c->max_frames));  // the first call allocates
+    e.records_on = enable != 0;
     return FLACGPU_OK;
 }
 
 int flacgpu_get_records(flacgpu_ctx *c, flacgpu_frame_record *out, uint64_t max_frames, uint64_t *n_frames) {
     if (!c || !n_frames) return FLACGPU_ERR_INVALID_INPUT;
-    const uint64_t n = std::min<uint64_t>(max_frames, c->h_records.size());
-    if (out && n) std::memcpy(out, c->h_records.data(), n * sizeof(FrameRec));
-    *n_frames = c->h_records.size();
+    const std::vector<FrameRec> none, &recs = c->enc ? c->enc->h_records : none;  // a decode-only context has none
+    const uint64_t n = std::min<uint64_t>(max_frames, recs.size());
+    if (out && n) std::memcpy(out, recs.data(), n * sizeof(FrameRec));
+    *n_frames = recs.size();
     return FLACGPU_OK;
 }
 
@@ -1464,9 +1422,10 @@ int flacgpu_get_records(flacgpu_ctx *c, flacgpu_frame_record *out, uint64_t max_
 int flacgpu_debug_stamps(flacgpu_ctx *c, uint64_t *out32, int reset) {
     if (!c || !out32) return FLACGPU_ERR_INVALID_INPUT;
     FG_ENCODER_ONLY(c);
+    EncState &e = *c->enc;
     HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpy(out32, c->d_stamps, 32 * 8, hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(hipMemset(c->d_stamps, 0, 32 * 8));
+    HIPCHK(hipMemcpy(out32, e.d_stamps.get(), 32 * 8, hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(e.d_stamps.get(), 0, 32 * 8));
     return FLACGPU_OK;
 }
 

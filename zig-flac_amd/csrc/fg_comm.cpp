@@ -77,17 +77,16 @@ enum { kFrames = 0, kBytes, kErr, kRecvCap, kRecvSizesCap, kWords = 8 };
 
 }  // namespace
 
-struct flacgpu_comm {
+struct FG_LOCAL flacgpu_comm {
     ncclComm_t nc = nullptr;
     int world = 0, rank = 0, device = 0;
-    uint64_t *d_cnt = nullptr;  // kWords u64: this rank's entry
-    uint64_t *d_all = nullptr;  // world x kWords u64
-    uint64_t *h_all = nullptr;  // pinned host copy of d_all
-    uint64_t *h_cnt = nullptr;  // pinned staging of this rank's entry
+    fg::DevBuf<uint64_t> d_cnt;  // kWords u64: this rank's entry
+    fg::DevBuf<uint64_t> d_all;  // world x kWords u64
+    uint64_t *h_all = nullptr;   // pinned host copy of d_all
+    uint64_t *h_cnt = nullptr;   // pinned staging of this rank's entry
     // encode_frames_sharded: rank 0's receive buffers (grow-only)
-    uint8_t *d_recv = nullptr;
-    uint32_t *d_recv_sizes = nullptr;
-    uint64_t recv_cap = 0, recv_sizes_cap = 0;
+    fg::DevBuf<uint8_t> d_recv;
+    fg::DevBuf<uint32_t> d_recv_sizes;
     // FLACGPU_COMM_SELF_P2P=1 (read at init; output-invariant): rank 0 moves its own slice into the
     // receive buffer by RCCL send/recv to itself instead of a device copy, so that a one-GPU box runs
     // the grouped point-to-point code the other ranks' slices take
@@ -100,10 +99,10 @@ namespace {
 int exchange_counts(flacgpu_comm *m, const uint64_t entry[kWords], const uint64_t *d_nbytes, hipStream_t st) {
     const Rccl &r = rccl();
     std::memcpy(m->h_cnt, entry, kWords * sizeof(uint64_t));
-    HIPCHK(hipMemcpyAsync(m->d_cnt, m->h_cnt, kWords * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (d_nbytes) HIPCHK(hipMemcpyAsync(m->d_cnt + kBytes, d_nbytes, sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    CHK_NCCL(r.all_gather(m->d_cnt, m->d_all, kWords, ncclUint64, m->nc, st));
-    HIPCHK(hipMemcpyAsync(m->h_all, m->d_all, (size_t)m->world * kWords * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(m->d_cnt.get(), m->h_cnt, kWords * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    if (d_nbytes) HIPCHK(hipMemcpyAsync(m->d_cnt.get() + kBytes, d_nbytes, sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+    CHK_NCCL(r.all_gather(m->d_cnt.get(), m->d_all.get(), kWords, ncclUint64, m->nc, st));
+    HIPCHK(hipMemcpyAsync(m->h_all, m->d_all.get(), (size_t)m->world * kWords * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return FLACGPU_OK;
 }
@@ -201,8 +200,7 @@ int flacgpu_comm_init(const uint8_t id[FLACGPU_COMM_ID_BYTES], int world, int ra
         flacgpu_comm_destroy(m);
         return rc;
     };
-    if (hipMalloc(&m->d_cnt, kWords * sizeof(uint64_t)) != hipSuccess ||
-        hipMalloc(&m->d_all, (size_t)world * kWords * sizeof(uint64_t)) != hipSuccess ||
+    if (m->d_cnt.grow(kWords) != hipSuccess || m->d_all.grow((uint64_t)world * kWords) != hipSuccess ||
         hipHostMalloc(&m->h_all, (size_t)world * kWords * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess ||
         hipHostMalloc(&m->h_cnt, kWords * sizeof(uint64_t), hipHostMallocDefault) != hipSuccess)
         return fail(FLACGPU_ERR_OUT_OF_MEMORY);
@@ -220,12 +218,8 @@ void flacgpu_comm_destroy(flacgpu_comm *m) {
     if (!m) return;
     hipSetDevice(m->device);
     if (m->nc) rccl().comm_destroy(m->nc);
-    hipFree(m->d_cnt);
-    hipFree(m->d_all);
     hipHostFree(m->h_all);
     hipHostFree(m->h_cnt);
-    hipFree(m->d_recv);
-    hipFree(m->d_recv_sizes);
     delete m;
 }
 
@@ -296,8 +290,8 @@ int flacgpu_encode_frames_sharded(flacgpu_ctx *ctx, flacgpu_comm *m, const void 
     // rank 0's receive buffers: one window of every rank's frames
     if (m->rank == 0) {
         // a failure leaves a null buffer: reported to every rank as out of memory by the first window
-        (void)fg::grow(m->d_recv, m->recv_cap, (uint64_t)m->world * d.out_cap);
-        (void)fg::grow(m->d_recv_sizes, m->recv_sizes_cap, wf);
+        (void)m->d_recv.grow((uint64_t)m->world * d.out_cap);
+        (void)m->d_recv_sizes.grow(wf);
     }
     uint64_t written = 0, frames_out = 0;
     int err = FLACGPU_OK;
@@ -307,7 +301,7 @@ int flacgpu_encode_frames_sharded(flacgpu_ctx *ctx, flacgpu_comm *m, const void 
         const uint64_t nf = std::min(frames, f0 + per) - f0;
         uint64_t total = 0;
         int lrc = err;
-        if (!lrc && m->rank == 0 && (!m->d_recv || !m->d_recv_sizes)) lrc = FLACGPU_ERR_OUT_OF_MEMORY;
+        if (!lrc && m->rank == 0 && (!m->d_recv.get() || !m->d_recv_sizes.get())) lrc = FLACGPU_ERR_OUT_OF_MEMORY;
         if (!lrc && nf) {
             const uint64_t s0 = f0 * bs, ns = std::min<uint64_t>(nf * bs, n_samples - s0);
             lrc = fg::ctx_encode_chunk(ctx, (const uint8_t *)pcm + s0 * isz, ns, first_frame_number + f0, &total, nullptr);
@@ -316,11 +310,11 @@ int flacgpu_encode_frames_sharded(flacgpu_ctx *ctx, flacgpu_comm *m, const void 
         ge[kFrames] = lrc ? 0 : nf;
         ge[kBytes] = lrc ? 0 : total;
         ge[kErr] = (uint64_t)(-lrc);
-        ge[kRecvCap] = m->recv_cap;
-        ge[kRecvSizesCap] = m->recv_sizes_cap;
+        ge[kRecvCap] = m->d_recv.cap();
+        ge[kRecvSizesCap] = m->d_recv_sizes.cap();
         if ((rc = exchange_counts(m, ge, nullptr, st))) return rc;  // the collective itself failed
         uint64_t tb = 0, tf = 0;
-        rc = transfer(m, d.d_out, d.d_fbytes, m->d_recv, m->d_recv_sizes, &tb, &tf, st);
+        rc = transfer(m, d.d_out, d.d_fbytes, m->d_recv.get(), m->d_recv_sizes.get(), &tb, &tf, st);
         if (rc) {
             err = rc;
             break;  // every rank took the same decision (the counts are shared): all leave here
@@ -329,9 +323,9 @@ int flacgpu_encode_frames_sharded(flacgpu_ctx *ctx, flacgpu_comm *m, const void 
             if (written + tb > out_cap) {
                 err = FLACGPU_ERR_OUTPUT_TOO_SMALL;  // rank 0 only: reported to the others next window
             } else {
-                if (tb) HIPCHK(hipMemcpyAsync(out + written, m->d_recv, tb, hipMemcpyDeviceToHost, st));
+                if (tb) HIPCHK(hipMemcpyAsync(out + written, m->d_recv.get(), tb, hipMemcpyDeviceToHost, st));
                 if (tf && frame_bytes)
-                    HIPCHK(hipMemcpyAsync(frame_bytes + frames_out, m->d_recv_sizes, tf * 4, hipMemcpyDeviceToHost, st));
+                    HIPCHK(hipMemcpyAsync(frame_bytes + frames_out, m->d_recv_sizes.get(), tf * 4, hipMemcpyDeviceToHost, st));
                 HIPCHK(hipStreamSynchronize(st));
                 written += tb;
                 frames_out += tf;

@@ -1,120 +1,165 @@
 // fg_ctx.hpp -- the context and plan behind the C ABI's opaque handles, and the small host
 // helpers every device-driving translation unit uses: error mapping, stream choice, kernel timing
-// brackets, the grow-only device buffer.  Private to fg_api.cpp, fg_dec_host.cpp and fg_comm.cpp;
-// fg_file.cpp and fg_multi.cpp see a context only through the accessors of fg_internal.hpp.
+// brackets.  What they hold is held in the owners of fg_own.hpp.  Private to fg_api.cpp,
+// fg_dec_host.cpp and fg_comm.cpp; fg_file.cpp and fg_multi.cpp see a context only through the
+// accessors of fg_internal.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <vector>
 
 #include "../../include/flacgpu.h"
 #include "fg_common.hpp"
 #include "fg_geom.hpp"
 #include "fg_md5_host.hpp"
-
-struct DecScratch;  // fg_dec_host.cpp: decode scratch of a context
-struct IdxScratch;  // fg_dec_host.cpp: index scratch of a context
+#include "fg_own.hpp"
 
 namespace fg {
 
-struct TimedLaunch {
+namespace dec {
+struct Result;
+struct DecSub;
+}
+
+struct FG_LOCAL TimedLaunch {
     int kernel;
-    hipEvent_t start, stop;
+    Event start, stop;
 };
 
-}  // namespace fg
+// What the streams of a context hold.  An encoder's max_block is its block size; a decode-only
+// context's is the largest block it accepts.
+struct StreamFormat {
+    uint32_t channels, bits, bytes_per_sample, sample_rate, max_block;
+};
 
-struct flacgpu_ctx {
-    int device = 0;
+// Everything only an encoder has (flacgpu_open).  Members are destroyed last to first: the buffers,
+// then the events, then the streams.
+struct FG_LOCAL EncState {
     flacgpu_config cfg{};
-    uint32_t max_frames = 0;
-    // flacgpu_open_decoder: cfg holds the stream and block_size = max_block (the encode options zero),
-    // g only C, B, bits and md5_kernel; of everything below only `stream`, the event pool, the timing
-    // and host MD5 state and the decoder scratch exist.  Every encode entry point refuses it.
-    bool decode_only = false;
-    fg::Knobs k;    // the environment's knobs when the context was opened
-    fg::EncGeom g;  // kernel variants, thread counts, LDS and image sizes: enc_geometry(cfg, k)
+    EncGeom g;  // kernel variants, thread counts, LDS and image sizes: enc_geometry(cfg, k)
 
     // ---- streams and events ----
-    hipStream_t stream = nullptr, aux = nullptr;
-    hipStream_t dl = nullptr;  // download stream of the pipelined host-buffer path
-    hipStream_t up = nullptr;  // its upload stream (chunk i+1's upload beside chunk i's encode)
-    hipStream_t ovl = nullptr;  // overlapped encode: scan + pack of range i
-    hipEvent_t fork = nullptr, join = nullptr;
-    std::vector<hipEvent_t> event_pool;
-
-    // ---- encode buffers ----
-    uint16_t *d_crc_pow = nullptr, *d_crc_join = nullptr, *d_crc_pow4 = nullptr;
-    uint16_t *d_crc_pows = nullptr;  // CRC fold shifts for the split pack's thread count
-    uint16_t *d_crc_powf = nullptr;  // CRC fold shifts for the fused kernel's 256 threads
-    uint16_t *d_crc_x8 = nullptr;    // z^(8 * 2^i) mod P, i < 24
-    uint32_t *d_err = nullptr, *d_ctr = nullptr;
-    fg::FrameJob *d_jobs = nullptr;
-    uint8_t *d_desc = nullptr;
-    uint32_t *d_fbytes = nullptr;
-    uint64_t *d_offsets = nullptr, *d_total = nullptr;
-    uint8_t *d_pcm = nullptr;
-    uint64_t pcm_cap = 0;
-    uint8_t *d_out = nullptr;
-    uint64_t out_cap = 0;
-    uint64_t *d_scan_part = nullptr;  // per-4096-frame block sums of the multi-workgroup scan
-    uint32_t scan_part_cap = 0;
-    uint64_t *d_status = nullptr;  // fused encode: per-slot status words, grow-only
-    uint64_t status_cap = 0;
-    uint64_t *d_cum = nullptr;  // [chunk] bytes of the frames before the chunk's slot range
-    uint32_t grid_reserve = 0;  // per call: slots the next analysis / pack launches leave free
-    // overlapped encode (encode_core): the full frames in `ovl_chunks` ranges, the analysis of
-    // range i+1 on `stream` beside the scan + pack of range i on `ovl`, each grid capped to
-    // ovl_ana / ovl_pack workgroups per CU so both are resident on every CU (flacgpu_set_overlap)
-    uint32_t ovl_chunks = 0, ovl_ana = 2, ovl_pack = 2, ovl_min_frames = 4096;
-
-    // ---- pipelined host-buffer path (encode_pipelined) ----
-    hipEvent_t up_done[kPipeSets] = {};  // a chunk set's upload landed (GPU-side waits)
-    hipEvent_t set_done[kPipeSets] = {};  // a chunk set's encode finished (GPU-side waits)
-    hipEvent_t dl_done[kPipeSets] = {};   // a chunk set's frames downloaded (GPU-side waits)
+    Stream aux;
+    Stream dl;   // download stream of the pipelined host-buffer path
+    Stream up;   // its upload stream (chunk i+1's upload beside chunk i's encode)
+    Stream ovl;  // overlapped encode: scan + pack of range i
+    Event fork, join;
+    // pipelined host-buffer path (encode_pipelined), GPU-side waits
+    Event up_done[kPipeSets];   // a chunk set's upload landed
+    Event set_done[kPipeSets];  // a chunk set's encode finished
+    Event dl_done[kPipeSets];   // a chunk set's frames downloaded
     // host waits of the pipelined host-buffer path (the download stream, the end; the chunk sets'
     // own events are set_done above):
     // blocking-sync events, so a waiting thread sleeps instead of spinning on a core the MD5 pool
     // and the other files' threads need (FLACGPU_SPIN_SYNC=1: spinning events, A/B)
-    hipEvent_t hw[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event hw[4];
 
-    // ---- decision records, kernel timing, clock stamps ----
-    fg::FrameRec *d_records = nullptr;
+    // ---- encode buffers ----
+    DevBuf<uint16_t> d_crc_pow, d_crc_join, d_crc_pow4;
+    DevBuf<uint16_t> d_crc_pows;  // CRC fold shifts for the split pack's thread count
+    DevBuf<uint16_t> d_crc_powf;  // CRC fold shifts for the fused kernel's 256 threads
+    DevBuf<uint16_t> d_crc_x8;    // z^(8 * 2^i) mod P, i < 24
+    DevBuf<uint32_t> d_err, d_ctr;
+    DevBuf<FrameJob> d_jobs;
+    DevBuf<uint8_t> d_desc;
+    DevBuf<uint32_t> d_fbytes;
+    DevBuf<uint64_t> d_offsets, d_total;
+    DevBuf<uint8_t> d_pcm, d_out;
+    DevBuf<uint64_t> d_status;  // fused encode: per-slot status words, grow-only
+    DevBuf<uint64_t> d_cum;     // [chunk] bytes of the frames before the chunk's slot range
+    uint32_t grid_reserve = 0;  // per call: slots the next analysis / pack launches leave free
+    // overlapped encode (encode_core): the full frames in `ovl_chunks` ranges, the analysis of
+    // range i+1 on the context's stream beside the scan + pack of range i on `ovl`, each grid capped
+    // to ovl_ana / ovl_pack workgroups per CU so both are resident on every CU (flacgpu_set_overlap)
+    uint32_t ovl_chunks = 0, ovl_ana = 2, ovl_pack = 2, ovl_min_frames = 4096;
+
+    // ---- decision records, clock stamps ----
+    DevBuf<FrameRec> d_records;
     bool records_on = false;
     bool records_keep = false;  // encode_files with records: every file's records, concatenated
-    std::vector<fg::FrameRec> h_records;
+    std::vector<FrameRec> h_records;
+    DevBuf<unsigned long long> d_stamps;
+
+    // ---- the device MD5 engine (FLACGPU_MD5_DEVICE, opt-in): one GPU lane fed by bounded chunks ----
+    DevBuf<uint32_t> d_md5_state, d_md5_blocks;
+    uint8_t md5_buf[64] = {};
+    uint32_t md5_fill = 0;
+    uint64_t md5_len = 0;
+};
+
+// Decode scratch of a context (allocated by its first decode call, max_frames frames), one
+// allocation: the subframe descriptors k_dec_parse leaves for k_dec_recon, the parsed block sizes
+// and their scan, the expected frame table of a verify, and a chunk's frame table and results in
+// the host-buffer decodes (decode_chunk).  Those decodes' frames and PCM are grow-only.
+struct FG_LOCAL DecScratch {
+    DevBuf<uint8_t> buf;
+    uint64_t *samp_off, *total, *exp_off, *exp_number, *d_foff;
+    dec::Result *d_results;
+    dec::DecSub *subs;
+    uint32_t *blocks, *body, *exp_n, *d_fbytes, *ctl, *d_bad;  // ctl: [0] ticket
+    DevBuf<uint8_t> d_frames, d_pcm;
+};
+
+// Index scratch of a context, grow-only: the arrays of idx::IdxArgs, sized from the call's len and
+// cap (buf); and the frame table and result of the whole-file decode, which indexes the file it
+// uploaded (table).  The many-streams decode adds the packed frame table with the per-stream arrays
+// and segment table of a call (packed), and the per-file results and digests of
+// flacgpu_decode_files (files).  The window decode adds the stream table of a positions call (pos),
+// the windows of a call as the caller states them with their cover records (win_in), what the chunk
+// loop over the covering frames needs (win), those frames' PCM (win_pcm), and the delivered bytes
+// and results of flacgpu_decode_files_windows (win_out).  The resampled delivery adds the
+// coefficient tables of the ratios it has served, kept until the context is closed (tables).
+struct FG_LOCAL ResampleTable {
+    uint32_t L, M;
+    DevBuf<float> coeffs;  // L rows of T
+};
+struct FG_LOCAL IdxScratch {
+    DevBuf<uint8_t> buf, table, packed, files, pos, win_in, win, win_pcm, win_out;
+    std::vector<ResampleTable> tables;
+};
+
+}  // namespace fg
+
+// A context: the shared part, which is all the decode layer reads, and three parts that are there
+// or not -- `enc` on an encoder (decode-only: !enc), `dec` and `idx` once a decode or index call
+// has needed them.  flacgpu_close deletes the context and the owners release everything.  Members
+// are destroyed last to first, so the order of declaration is the teardown order read upwards: the
+// three parts (each its buffers, then its events, then its streams), d_scan_part, the timing events
+// and the event pool, and the context's own stream last.
+struct FG_LOCAL flacgpu_ctx {
+    int device = 0;
+    fg::StreamFormat fmt{};
+    uint32_t max_frames = 0;
+    fg::Knobs k;  // the environment's knobs when the context was opened
+    fg::Stream stream;
+    std::vector<fg::Event> event_pool;
+    // kernel timing
     bool timing = false;
     std::vector<fg::TimedLaunch> pending;
     uint64_t launches[FLACGPU_K_COUNT] = {};
     double ms[FLACGPU_K_COUNT] = {};
-    unsigned long long *d_stamps = nullptr;
-
-    // ---- MD5 ----
-    // streaming MD5 (one stream): a host core by default (FLACGPU_MD5_HOST), or one GPU
-    // lane fed by bounded chunks (FLACGPU_MD5_DEVICE, opt-in)
+    // streaming MD5 (one stream): a host core by default (FLACGPU_MD5_HOST), or EncState's device engine
     int md5_engine = FLACGPU_MD5_HOST;
     fg::HostMd5 host_md5;
-    uint32_t *d_md5_state = nullptr;
-    uint32_t *d_md5_blocks = nullptr;
-    uint8_t md5_buf[64] = {};
-    uint32_t md5_fill = 0;
-    uint64_t md5_len = 0;
+    int md5_kernel = 1;  // the batched stream MD5 (plans, decoded streams): EncGeom::md5_kernel's rule
+    fg::DevBuf<uint64_t> d_scan_part;  // per-4096-frame block sums of the multi-workgroup scan, grow-only
 
-    // ---- decoder scratch ----
-    DecScratch *dec = nullptr;  // frame decoder / verifier: allocated by the first decode call
-    IdxScratch *idx = nullptr;  // device frame index: allocated by the first index call
+    std::unique_ptr<fg::EncState> enc;    // flacgpu_open; NULL on a decode-only context (flacgpu_open_decoder)
+    std::unique_ptr<fg::DecScratch> dec;  // frame decoder / verifier: allocated by the first decode call
+    std::unique_ptr<fg::IdxScratch> idx;  // device frame index: allocated by the first index call
 };
 
-struct flacgpu_plan {
+struct FG_LOCAL flacgpu_plan {
     flacgpu_ctx *ctx = nullptr;
     uint32_t n_streams = 0;
     uint32_t B = 0;
     uint64_t n_frames = 0, n_full = 0, n_tail = 0;
-    fg::FrameJob *d_jobs = nullptr;  // full jobs first, then tail jobs
-    uint64_t *d_md5_offs = nullptr, *d_md5_lens = nullptr;
-    uint8_t *d_md5_fin = nullptr;  // per-stream final-segment flags (NULL: all final)
-    uint64_t md5_max_len = 0;      // longest stream segment (bytes): the MD5 chain of one call
-    uint64_t max_number = 0;       // largest frame number in the table (u36 check on advance)
+    fg::DevBuf<fg::FrameJob> d_jobs;  // full jobs first, then tail jobs
+    fg::DevBuf<uint64_t> d_md5_offs, d_md5_lens;
+    fg::DevBuf<uint8_t> d_md5_fin;  // per-stream final-segment flags (empty: all final)
+    uint64_t md5_max_len = 0;       // longest stream segment (bytes): the MD5 chain of one call
+    uint64_t max_number = 0;        // largest frame number in the table (u36 check on advance)
     std::vector<uint64_t> first_frame;
     std::vector<uint32_t> full_slots;  // slot of each full job (host copy: ranges of the overlapped encode)
     // host copies of the MD5 segments (the host engine, flacgpu_md5_plan_host)
@@ -122,7 +167,7 @@ struct flacgpu_plan {
     std::vector<uint8_t> h_md5_fin;  // empty: all final
     uint64_t md5_total = 0;          // bytes of all segments
     uint64_t out_bound = 0;
-    uint8_t *d_desc = nullptr;  // per-plan descriptor area when larger than the context's
+    fg::DevBuf<uint8_t> d_desc;  // per-plan descriptor area when larger than the context's
 };
 
 namespace fg {
@@ -152,12 +197,8 @@ namespace resample {
 struct Ratio;
 }
 
-// shared by the translation units that include this header, not exported from libflacgpu.so
-#define FG_LOCAL __attribute__((visibility("hidden")))
-// fg_api.cpp
-FG_LOCAL hipEvent_t get_event(flacgpu_ctx *c);
-// fg_dec_host.cpp: free the decode and index scratch of a context (flacgpu_close)
-FG_LOCAL void dec_release(flacgpu_ctx *c);
+// fg_api.cpp: an event of the context's pool, or a new one (empty: none could be created)
+FG_LOCAL Event get_event(flacgpu_ctx *c);
 // fg_misc.hip
 hipError_t launch_scan(const uint32_t *sizes, uint64_t *offsets, uint64_t *total, uint32_t n, uint64_t *part,
                        hipStream_t st, const uint64_t *base = nullptr);
@@ -217,18 +258,18 @@ struct FG_LOCAL Timed {
     flacgpu_ctx *c;
     int k;
     hipStream_t st;
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     Timed(flacgpu_ctx *c_, int k_, hipStream_t st_) : c(c_), k(k_), st(st_) {
         if (c->timing) {
             a = get_event(c);
             b = get_event(c);
-            if (a) hipEventRecord(a, st);
+            if (a) hipEventRecord(a.get(), st);
         }
     }
     ~Timed() {
         if (c->timing && a && b) {
-            hipEventRecord(b, st);
-            c->pending.push_back({k, a, b});
+            hipEventRecord(b.get(), st);
+            c->pending.push_back({k, std::move(a), std::move(b)});
         }
     }
 };
@@ -238,7 +279,7 @@ FG_LOCAL inline int hip_err(hipError_t e) { return e == hipSuccess ? FLACGPU_OK 
 // first statement of every entry point that encodes or needs an encode buffer, after its NULL checks
 #define FG_ENCODER_ONLY(c)                                        \
     do {                                                          \
-        if ((c)->decode_only) return FLACGPU_ERR_INVALID_CONFIG;  \
+        if (!(c)->enc) return FLACGPU_ERR_INVALID_CONFIG;      \
     } while (0)
 
 #define HIPCHK(x)                               \
@@ -250,30 +291,9 @@ FG_LOCAL inline int hip_err(hipError_t e) { return e == hipSuccess ? FLACGPU_OK 
 // The C ABI's hip_stream: NULL = the context's own stream, FLACGPU_STREAM_LEGACY = the HIP null
 // stream (legacy default-stream semantics: the handle-0 stream of a framework), else a hipStream_t.
 FG_LOCAL inline hipStream_t pick_stream(const flacgpu_ctx *c, void *hip_stream) {
-    if (!hip_stream) return c->stream;
+    if (!hip_stream) return c->stream.get();
     if (hip_stream == FLACGPU_STREAM_LEGACY) return (hipStream_t)0;
     return (hipStream_t)hip_stream;
-}
-
-// The library's grow-only device buffers: p holds cap elements.  Nothing to do where `need` of
-// them fit; otherwise the old buffer is freed and one of `need` elements allocated, after *sync has
-// drained where work queued on that stream may still use the old one (NULL: the caller knows that
-// none does).  On failure p and cap are left {nullptr, 0}.
-template <class T, class N>
-FG_LOCAL inline hipError_t grow(T *&p, N &cap, uint64_t need, const hipStream_t *sync = nullptr) {
-    if (need <= cap) return hipSuccess;
-    hipError_t e = sync ? hipStreamSynchronize(*sync) : hipSuccess;
-    if (e != hipSuccess) return e;
-    hipFree(p);
-    p = nullptr;
-    cap = 0;
-    e = hipMalloc(&p, need * sizeof(T));
-    if (e != hipSuccess) {
-        p = nullptr;
-        return e;
-    }
-    cap = (N)need;
-    return hipSuccess;
 }
 
 }  // namespace fg

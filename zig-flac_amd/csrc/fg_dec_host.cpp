@@ -40,99 +40,30 @@ static_assert(sizeof(streams::StreamResult) == sizeof(flacgpu_stream_result), "s
 static_assert(FLACGPU_INDEX_INVALID == (int)idx::IDX_INVALID && FLACGPU_INDEX_TOO_SMALL == (int)idx::IDX_TOO_SMALL,
               "index status codes");
 
-// Decode scratch of a context (allocated by its first decode call, max_frames frames), one
-// allocation: the subframe descriptors k_dec_parse leaves for k_dec_recon, the parsed block sizes
-// and their scan, the expected frame table of a verify, and a chunk's frame table and results in
-// the host-buffer decodes (decode_chunk).  Those decodes' frames and PCM are grow-only.
-struct DecScratch {
-    uint8_t *buf = nullptr;
-    uint64_t *samp_off, *total, *exp_off, *exp_number, *d_foff;
-    dec::Result *d_results;
-    dec::DecSub *subs;
-    uint32_t *blocks, *body, *exp_n, *d_fbytes, *ctl, *d_bad;  // ctl: [0] ticket
-    uint8_t *d_frames = nullptr, *d_pcm = nullptr;
-    uint64_t frames_cap = 0, pcm_cap = 0;
-};
-
-// Index scratch of a context, grow-only: the arrays of idx::IdxArgs, sized from the call's len and
-// cap; and the frame table and result of the whole-file decode, which indexes the file it uploaded.
-// The many-streams decode adds the packed frame table with the per-stream arrays and segment table
-// of a call (packed), and the per-file results and digests of flacgpu_decode_files (files).
-// The window decode adds the stream table of a positions call (pos), the windows of a call as the
-// caller states them with their cover records (win_in), what the chunk loop over the covering
-// frames needs (win), those frames' PCM (win_pcm), and the delivered bytes and results of
-// flacgpu_decode_files_windows (win_out).  The resampled delivery adds the coefficient tables of
-// the ratios it has served, one allocation each, kept until the context is closed (tables).
-struct ResampleTable {
-    uint32_t L, M;
-    float *d_coeffs;  // L rows of T
-};
-struct IdxScratch {
-    uint8_t *buf = nullptr, *table = nullptr, *packed = nullptr, *files = nullptr;
-    uint64_t cap = 0, table_cap = 0, packed_cap = 0, files_cap = 0;
-    uint8_t *pos = nullptr, *win_in = nullptr, *win = nullptr, *win_pcm = nullptr, *win_out = nullptr;
-    uint64_t pos_cap = 0, win_in_cap = 0, win_cap = 0, win_pcm_cap = 0, win_out_cap = 0;
-    std::vector<ResampleTable> tables;
-};
-
-void fg::dec_release(flacgpu_ctx *c) {
-    if (DecScratch *d = c->dec)
-        for (uint8_t *b : {d->buf, d->d_frames, d->d_pcm}) hipFree(b);
-    if (IdxScratch *x = c->idx) {
-        for (uint8_t *b : {x->buf, x->table, x->packed, x->files, x->pos, x->win_in, x->win, x->win_pcm, x->win_out}) hipFree(b);
-        for (const ResampleTable &t : x->tables) hipFree(t.d_coeffs);
-    }
-    delete c->dec;
-    delete c->idx;
-    c->dec = nullptr;
-    c->idx = nullptr;
-}
-
 namespace {
-
-// Carves one allocation into arrays, each aligned like an allocation of its own: take() hands the
-// next n elements to each of its pointers and returns the bytes used so far.  A carve is written
-// once, as a function of the base, and run twice: on NULL for the size, then on the allocation.
-struct Carve {
-    uint8_t *base;
-    uint64_t at = 0;
-    template <class T, class... R>
-    uint64_t take(uint64_t n, T *&p, R &...rest) {
-        p = base ? (T *)(base + at) : nullptr;
-        at += (n * sizeof(T) + 255u) & ~(uint64_t)255u;
-        if constexpr (sizeof...(rest) > 0) take(n, rest...);
-        return at;
-    }
-};
 
 // All or nothing: c->dec is set only once its allocation is there, so a call that fails here
 // leaves the context as it was and the next one tries again.
 int dec_scratch(flacgpu_ctx *c) {
     if (c->dec) return FLACGPU_OK;
-    DecScratch *d = new (std::nothrow) DecScratch();
+    std::unique_ptr<DecScratch> d(new (std::nothrow) DecScratch());
     if (!d) return FLACGPU_ERR_OUT_OF_MEMORY;
-    auto carve = [&](uint8_t *base) {  // 8-byte members first
+    HIPCHK(fit(d->buf, [&](uint8_t *base) {  // 8-byte members first
         Carve v{base};
         v.take(c->max_frames, d->samp_off, d->exp_off, d->exp_number, d->d_foff, d->d_results);
         v.take(1, d->total);
-        v.take((uint64_t)c->max_frames * c->g.C, d->subs);
+        v.take((uint64_t)c->max_frames * c->fmt.channels, d->subs);
         v.take(c->max_frames, d->blocks, d->body, d->exp_n, d->d_fbytes);
         v.take(16, d->ctl);
         return v.take(1, d->d_bad);
-    };
-    const hipError_t e = hipMalloc(&d->buf, carve(nullptr));
-    if (e != hipSuccess) {
-        delete d;
-        return hip_err(e);
-    }
-    carve(d->buf);
-    c->dec = d;  // freed by dec_release
+    }));
+    c->dec = std::move(d);
     return FLACGPU_OK;
 }
 
 IdxScratch *idx_scratch(flacgpu_ctx *c) {
-    if (!c->idx) c->idx = new (std::nothrow) IdxScratch();  // freed by dec_release
-    return c->idx;
+    if (!c->idx) c->idx.reset(new (std::nothrow) IdxScratch());
+    return c->idx.get();
 }
 
 // a chunk that holds frames of several streams: its segments and the per-stream arrays (device)
@@ -150,18 +81,18 @@ struct ChunkStreams {
 int dec_core(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff, const uint32_t *d_fbytes, uint32_t n,
              const uint64_t *d_pcm_off, uint8_t *d_out, uint64_t cap, const uint8_t *d_expect, bool verify,
              flacgpu_decode_result *d_results, uint32_t *d_bad, hipStream_t st, const ChunkStreams *cs = nullptr) {
-    DecScratch *d = c->dec;
+    DecScratch *d = c->dec.get();
     if (cs) d_pcm_off = d->exp_off;
     dec::Args a{};
     a.frames = d_frames;
     a.frame_off = d_foff;
     a.frame_bytes = d_fbytes;
     a.n_frames = n;
-    a.channels = c->g.C;
-    a.bits = c->g.bits;
-    a.bps = c->g.bits / 8u;
-    a.rate = c->cfg.sample_rate;
-    a.block = c->cfg.block_size;
+    a.channels = c->fmt.channels;
+    a.bits = c->fmt.bits;
+    a.bps = c->fmt.bytes_per_sample;
+    a.rate = c->fmt.sample_rate;
+    a.block = c->fmt.max_block;
     a.subs = d->subs;
     a.blocks = d->blocks;
     a.body = d->body;
@@ -181,13 +112,13 @@ int dec_core(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff, co
     }
     if (cs) {
         Timed t(c, FLACGPU_K_SCAN, st);
-        HIPCHK(launch_seg_offsets(cs->segs, cs->n_segs, d->blocks, cs->pcm_base, cs->pcm_cap, cs->carried, c->g.C * a.bps,
+        HIPCHK(launch_seg_offsets(cs->segs, cs->n_segs, d->blocks, cs->pcm_base, cs->pcm_cap, cs->carried, c->fmt.channels * a.bps,
                                   d->exp_off, st));
     } else if (!d_pcm_off) {
         // consecutive blocks of one stream: sample offsets from the scan of the parsed block sizes
-        HIPCHK(grow(c->d_scan_part, c->scan_part_cap, (n + 4095u) / 4096u, &st));
+        HIPCHK(c->d_scan_part.grow((n + 4095u) / 4096u, &st));
         Timed t(c, FLACGPU_K_SCAN, st);
-        HIPCHK(launch_scan(d->blocks, d->samp_off, d->total, n, c->d_scan_part, st));
+        HIPCHK(launch_scan(d->blocks, d->samp_off, d->total, n, c->d_scan_part.get(), st));
     }
     {
         Timed t(c, FLACGPU_K_DEC_RECON, st);
@@ -218,8 +149,7 @@ int index_core(flacgpu_ctx *c, const uint8_t *d_data, uint64_t len, uint32_t str
         v.take(g.spos_cap, g.spos);
         return v.take(g.n_chunks, g.terms);
     };
-    HIPCHK(grow(x->buf, x->cap, carve(nullptr), &st));  // an earlier index on this stream may still use the old one
-    carve(x->buf);
+    HIPCHK(fit(x->buf, carve, &st));  // an earlier index on this stream may still use the old one
     Timed t(c, FLACGPU_K_INDEX, st);
     HIPCHK(launch_index(g, st));
     return FLACGPU_OK;
@@ -263,8 +193,7 @@ int index_streams_core(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const 
         v.take(tot.spos, pool.spos);
         return v.take(tot.chunks, pool.terms);
     };
-    HIPCHK(grow(x->buf, x->cap, carve(nullptr), &st));  // an earlier index on this stream may still use the old one
-    carve(x->buf);
+    HIPCHK(fit(x->buf, carve, &st));  // an earlier index on this stream may still use the old one
     idx::IdxTotals at;
     for (uint32_t s = 0; s < n; s++) idx::carve_stream(tab[s], pool, at);
     HIPCHK(hipMemcpyAsync(d_tab, tab.data(), (uint64_t)n * sizeof(idx::IdxArgs), hipMemcpyHostToDevice, st));
@@ -318,8 +247,7 @@ int streams_index(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const uint6
         v.take(n, tb.d_ires);
         return v.take(total, tb.f_bytes);
     };
-    HIPCHK(grow(x->table, x->table_cap, table(nullptr), &st));
-    table(x->table);
+    HIPCHK(fit(x->table, table, &st));
     const int rc = index_streams_core(c, d_data, n, offs, lens, bits, rates, tb.first.data(), tb.caps.data(), tb.f_off,
                                       tb.f_bytes, tb.d_ires, st);
     if (rc) return rc;
@@ -347,8 +275,8 @@ struct ChunkRun {
     uint64_t *row(uint32_t r) const { return meta + (uint64_t)r * n; }
 
     template <class Extra>
-    int prepare(flacgpu_ctx *c, const std::vector<uint64_t> &frames, const std::vector<uint64_t> &host, uint8_t *&buf,
-                uint64_t &cap, Extra extra, hipStream_t st) {
+    int prepare(flacgpu_ctx *c, const std::vector<uint64_t> &frames, const std::vector<uint64_t> &host,
+                DevBuf<uint8_t> &buf, Extra extra, hipStream_t st) {
         n = (uint32_t)frames.size();
         try {
             streams::cut_segments(frames, c->max_frames, segs, chunk_seg);
@@ -365,8 +293,7 @@ struct ChunkRun {
             v.take(segs.size(), d_segs);
             return v.take(n_packed, p_bytes);
         };
-        HIPCHK(grow(buf, cap, carve(nullptr), &st));
-        carve(buf);
+        HIPCHK(fit(buf, carve, &st));
         HIPCHK(hipMemcpyAsync(meta, host.data(), host.size() * 8u, hipMemcpyHostToDevice, st));
         if (!segs.empty())
             HIPCHK(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(streams::Segment), hipMemcpyHostToDevice, st));
@@ -414,16 +341,16 @@ int streams_decode(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const Stre
     }
     ChunkRun run;
     uint64_t *md5_lens = nullptr;
-    int rc = run.prepare(c, frames, host, c->idx->packed, c->idx->packed_cap, [&](Carve &v) { v.take(n, md5_lens); }, st);
+    int rc = run.prepare(c, frames, host, c->idx->packed, [&](Carve &v) { v.take(n, md5_lens); }, st);
     if (rc) return rc;
     HIPCHK(launch_streams_init(tb.d_ires, d_results, run.carried, n, st));
     rc = run.run(c, d_data, tb.f_off, tb.f_bytes, d_pcm_out, whole, d_results, st);
     if (rc) return rc;
     if (d_md5) {
-        HIPCHK(launch_streams_md5_lens(d_results, c->g.C * (c->g.bits / 8u), md5_lens, n, st));
+        HIPCHK(launch_streams_md5_lens(d_results, c->fmt.channels * c->fmt.bytes_per_sample, md5_lens, n, st));
         {
             Timed t(c, FLACGPU_K_MD5, st);
-            HIPCHK(launch_md5_streams(d_pcm_out, run.row(0), md5_lens, nullptr, n, nullptr, d_md5, st, c->g.md5_kernel,
+            HIPCHK(launch_md5_streams(d_pcm_out, run.row(0), md5_lens, nullptr, n, nullptr, d_md5, st, c->md5_kernel,
                                       c->k.md5_prio));
         }
         HIPCHK(launch_streams_md5_mask(d_results, d_md5, n, st));
@@ -450,10 +377,10 @@ int positions_core(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n, const uint
         tab[s] = {table_first[s], table_caps[s], bits ? bits[s] : 16u, rates ? rates[s] : 0u};
         max_cap = std::max(max_cap, table_caps[s]);
     }
-    HIPCHK(grow(x->pos, x->pos_cap, (uint64_t)n * sizeof(window::PosStream), &st));  // an earlier call may still use the old one
-    HIPCHK(hipMemcpyAsync(x->pos, tab.data(), (uint64_t)n * sizeof(window::PosStream), hipMemcpyHostToDevice, st));
+    HIPCHK(x->pos.grow((uint64_t)n * sizeof(window::PosStream), &st));  // an earlier call may still use the old one
+    HIPCHK(hipMemcpyAsync(x->pos.get(), tab.data(), (uint64_t)n * sizeof(window::PosStream), hipMemcpyHostToDevice, st));
     Timed t(c, FLACGPU_K_SCAN, st);
-    HIPCHK(launch_positions(d_data, (const window::PosStream *)x->pos, n, max_cap, d_off, d_bytes, d_res, d_pos, d_totals, st));
+    HIPCHK(launch_positions(d_data, (const window::PosStream *)x->pos.get(), n, max_cap, d_off, d_bytes, d_res, d_pos, d_totals, st));
     return FLACGPU_OK;
 }
 
@@ -466,14 +393,14 @@ struct Resampling {
 
 // The device table of a ratio: built on the host by flacgpu_resample_filter and uploaded by the
 // first call of the context that needs it, which waits for st once more than the others; kept for
-// the context's life (dec_release).
+// the context's life.
 int resample_table(flacgpu_ctx *c, const resample::Ratio &rt, uint32_t src_rate, uint32_t dst_rate, const float **d_coeffs,
                    hipStream_t st) {
     IdxScratch *x = idx_scratch(c);
     if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
     for (const ResampleTable &t : x->tables)
         if (t.L == rt.L && t.M == rt.M) {
-            *d_coeffs = t.d_coeffs;
+            *d_coeffs = t.coeffs.get();
             return FLACGPU_OK;
         }
     std::vector<float> h;
@@ -486,16 +413,12 @@ int resample_table(flacgpu_ctx *c, const resample::Ratio &rt, uint32_t src_rate,
     }
     const int rc = flacgpu_resample_filter(src_rate, dst_rate, nullptr, nullptr, nullptr, h.data(), h.size(), &n);
     if (rc) return rc;
-    float *d = nullptr;
-    HIPCHK(hipMalloc(&d, n * sizeof(float)));
-    hipError_t e = hipMemcpyAsync(d, h.data(), n * sizeof(float), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);  // h goes out of scope
-    if (e != hipSuccess) {
-        hipFree(d);
-        return hip_err(e);
-    }
-    x->tables.push_back({rt.L, rt.M, d});
-    *d_coeffs = d;
+    DevBuf<float> d;
+    HIPCHK(d.grow(n));
+    HIPCHK(hipMemcpyAsync(d.get(), h.data(), n * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));  // h goes out of scope
+    *d_coeffs = d.get();
+    x->tables.push_back({rt.L, rt.M, std::move(d)});
     return FLACGPU_OK;
 }
 
@@ -532,8 +455,7 @@ int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexR
         v.take(n, wc.d_args);
         return v.take(n, wc.d_recs);
     };
-    HIPCHK(grow(x->win_in, x->win_in_cap, carve(nullptr), &st));  // an earlier call may still use the old one
-    carve(x->win_in);
+    HIPCHK(fit(x->win_in, carve, &st));  // an earlier call may still use the old one
     wc.n = n;
     HIPCHK(hipMemcpyAsync(wc.d_args, args.data(), (uint64_t)n * sizeof(window::WindowArg), hipMemcpyHostToDevice, st));
     {
@@ -560,9 +482,9 @@ int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_
                    const uint32_t *d_fbytes, const WindowsCall &wc, const uint32_t *window_stream,
                    const uint64_t *window_count, const deliver::Delivery &dv, uint8_t *d_pcm_out, const uint64_t *out_offsets,
                    window::WindowResult *d_results, hipStream_t st, const Resampling *rs = nullptr) {
-    IdxScratch *x = c->idx;
+    IdxScratch *x = c->idx.get();
     const uint32_t n = wc.n;
-    const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u);
+    const uint64_t per = (uint64_t)c->fmt.channels * c->fmt.bytes_per_sample;
     std::vector<uint64_t> frames, host;  // host: scratch base, scratch cap, table first, destination
     const bool convert = dv.format != deliver::SAMPLE_BYTES;
     uint64_t whole = 0, max_bytes = 0;  // whole: the end of the last region
@@ -589,22 +511,22 @@ int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_
         if (whole > (1ull << 47)) return FLACGPU_ERR_OUT_OF_MEMORY;
         max_bytes = std::max(max_bytes, r.n_samples * per);
     }
-    HIPCHK(grow(x->win_pcm, x->win_pcm_cap, whole + 16u, &st));
+    HIPCHK(x->win_pcm.grow(whole + 16u, &st));
     ChunkRun run;
     streams::StreamResult *sres = nullptr;
-    int rc = run.prepare(c, frames, host, x->win, x->win_cap, [&](Carve &v) { v.take(n, sres); }, st);
+    int rc = run.prepare(c, frames, host, x->win, [&](Carve &v) { v.take(n, sres); }, st);
     if (rc) return rc;
     HIPCHK(launch_window_init(wc.d_recs, sres, run.carried, n, st));
-    rc = run.run(c, d_data, d_foff, d_fbytes, x->win_pcm, whole, sres, st);
+    rc = run.run(c, d_data, d_foff, d_fbytes, x->win_pcm.get(), whole, sres, st);
     if (rc) return rc;
     const uint64_t *d_base = run.row(0), *d_dst = run.row(3);
     if (rs)
-        HIPCHK(launch_window_resample(wc.d_recs, sres, wc.d_args, rs->d_totals, x->win_pcm, d_base, d_pcm_out, d_dst, dv, rs->rt,
+        HIPCHK(launch_window_resample(wc.d_recs, sres, wc.d_args, rs->d_totals, x->win_pcm.get(), d_base, d_pcm_out, d_dst, dv, rs->rt,
                                       rs->d_coeffs, n, max_written, st));
     else if (convert)
-        HIPCHK(launch_window_elements(wc.d_recs, sres, wc.d_args, x->win_pcm, d_base, d_pcm_out, d_dst, dv, n, max_written, st));
+        HIPCHK(launch_window_elements(wc.d_recs, sres, wc.d_args, x->win_pcm.get(), d_base, d_pcm_out, d_dst, dv, n, max_written, st));
     else
-        HIPCHK(launch_window_copy(wc.d_recs, sres, x->win_pcm, d_base, d_pcm_out, d_dst, (uint32_t)per, n, max_bytes, st));
+        HIPCHK(launch_window_copy(wc.d_recs, sres, x->win_pcm.get(), d_base, d_pcm_out, d_dst, (uint32_t)per, n, max_bytes, st));
     HIPCHK(launch_window_results(wc.d_recs, sres, d_results, n, st));
     return FLACGPU_OK;
 }
@@ -613,7 +535,7 @@ int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_
 // 64-byte aligned offs[i], lens[i] bytes, uploaded on st.
 int upload_files(flacgpu_ctx *c, uint32_t n, const uint8_t *const *p, const size_t *len, std::vector<uint64_t> &offs,
                  std::vector<uint64_t> &lens, hipStream_t st) {
-    DecScratch *d = c->dec;
+    DecScratch *d = c->dec.get();
     try {
         offs.resize(n);
         lens.resize(n);
@@ -627,9 +549,9 @@ int upload_files(flacgpu_ctx *c, uint32_t n, const uint8_t *const *p, const size
         lens[i] = len[i];
         total += (len[i] + 63u) & ~(uint64_t)63u;
     }
-    HIPCHK(grow(d->d_frames, d->frames_cap, total + 16u, &st));
+    HIPCHK(d->d_frames.grow(total + 16u, &st));
     for (uint32_t i = 0; i < n; i++)
-        if (len[i]) HIPCHK(hipMemcpyAsync(d->d_frames + offs[i], p[i], len[i], hipMemcpyHostToDevice, st));
+        if (len[i]) HIPCHK(hipMemcpyAsync(d->d_frames.get() + offs[i], p[i], len[i], hipMemcpyHostToDevice, st));
     return FLACGPU_OK;
 }
 
@@ -642,13 +564,13 @@ template <class F>
 int decode_chunk(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff, const uint32_t *d_fbytes, uint32_t n,
                  uint8_t *pcm_out, uint64_t pcm_cap, uint64_t *written, uint64_t *n_samples, dec::Result *results,
                  F overlap) {
-    DecScratch *d = c->dec;
-    hipStream_t st = c->stream;
+    DecScratch *d = c->dec.get();
+    hipStream_t st = c->stream.get();
     // (a decode-only context's block_size is its max_block, up to 16384: 64-bit products)
-    const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u), need = (uint64_t)n * (uint64_t)c->cfg.block_size * per;
-    HIPCHK(grow(d->d_pcm, d->pcm_cap, need));  // the chunk before this one was waited for
-    HIPCHK(hipMemsetAsync(d->d_pcm, 0, need, st));
-    const int rc = dec_core(c, d_frames, d_foff, d_fbytes, n, nullptr, d->d_pcm, need, nullptr, false,
+    const uint64_t per = (uint64_t)c->fmt.channels * c->fmt.bytes_per_sample, need = (uint64_t)n * (uint64_t)c->fmt.max_block * per;
+    HIPCHK(d->d_pcm.grow(need));  // the chunk before this one was waited for
+    HIPCHK(hipMemsetAsync(d->d_pcm.get(), 0, need, st));
+    const int rc = dec_core(c, d_frames, d_foff, d_fbytes, n, nullptr, d->d_pcm.get(), need, nullptr, false,
                             (flacgpu_decode_result *)d->d_results, nullptr, st);
     if (rc) return rc;
     uint64_t total = 0;
@@ -659,7 +581,7 @@ int decode_chunk(flacgpu_ctx *c, const uint8_t *d_frames, const uint64_t *d_foff
     const uint64_t out_bytes = total * per;
     if (out_bytes > need) return FLACGPU_ERR_INTERNAL;
     if (*written + out_bytes > pcm_cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
-    if (out_bytes) HIPCHK(hipMemcpy(pcm_out + *written, d->d_pcm, out_bytes, hipMemcpyDeviceToHost));
+    if (out_bytes) HIPCHK(hipMemcpy(pcm_out + *written, d->d_pcm.get(), out_bytes, hipMemcpyDeviceToHost));
     *written += out_bytes;
     *n_samples += total;
     return FLACGPU_OK;
@@ -703,9 +625,9 @@ int flacgpu_verify_plan_device(flacgpu_ctx *c, const flacgpu_plan *p, const void
         HIPCHK(hipMemsetAsync(d_bad_count, 0, 4, st));
         return FLACGPU_OK;
     }
-    DecScratch *d = c->dec;
+    DecScratch *d = c->dec.get();
     // the plan's frame table (full jobs, then tail jobs) by output slot
-    HIPCHK(launch_dec_expect(p->d_jobs, p->n_frames, d->exp_off, d->exp_number, d->exp_n, st));
+    HIPCHK(launch_dec_expect(p->d_jobs.get(), p->n_frames, d->exp_off, d->exp_number, d->exp_n, st));
     return dec_core(c, d_out, d_frame_offsets, d_frame_bytes, (uint32_t)p->n_frames, d->exp_off, nullptr, 0,
                     (const uint8_t *)d_pcm, true, d_results, d_bad_count, st);
 }
@@ -801,9 +723,9 @@ int windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, co
         return FLACGPU_ERR_INVALID_INPUT;
     for (uint32_t w = 0; w < n_windows; w++)
         if (window_stream[w] >= n_streams || offsets[w] + caps[w] < offsets[w]) return FLACGPU_ERR_INVALID_INPUT;
-    deliver::Delivery dv = deliver::identity_delivery(sample_format, flags, c->g.C, c->g.bits / 8u);
+    deliver::Delivery dv = deliver::identity_delivery(sample_format, flags, c->fmt.channels, c->fmt.bytes_per_sample);
     if (masks) {
-        if (!deliver::mix_valid(c->g.C, out_channels, masks, sample_format)) return FLACGPU_ERR_INVALID_INPUT;
+        if (!deliver::mix_valid(c->fmt.channels, out_channels, masks, sample_format)) return FLACGPU_ERR_INVALID_INPUT;
         dv.mix = 1u;
         dv.out_channels = out_channels;
         for (uint32_t k = 0; k < deliver::kMixMaxChannels; k++) dv.masks[k] = k < out_channels ? masks[k] : (uint8_t)0;
@@ -904,8 +826,8 @@ int flacgpu_decode_frames(flacgpu_ctx *c, const uint8_t *frames, const uint32_t 
     HIPCHK(hipSetDevice(c->device));
     int rc = dec_scratch(c);
     if (rc) return rc;
-    DecScratch *d = c->dec;
-    hipStream_t st = c->stream;
+    DecScratch *d = c->dec.get();
+    hipStream_t st = c->stream.get();
     std::vector<uint64_t> foff;
     uint64_t src = 0, written = 0;
     for (uint64_t f0 = 0; f0 < n_frames; f0 += c->max_frames) {
@@ -916,11 +838,11 @@ int flacgpu_decode_frames(flacgpu_ctx *c, const uint8_t *frames, const uint32_t 
             foff[i] = bytes;
             bytes += frame_bytes[f0 + i];
         }
-        HIPCHK(grow(d->d_frames, d->frames_cap, bytes + 16u));  // the chunk before this one was waited for
-        HIPCHK(hipMemcpyAsync(d->d_frames, frames + src, bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(d->d_frames.grow(bytes + 16u));  // the chunk before this one was waited for
+        HIPCHK(hipMemcpyAsync(d->d_frames.get(), frames + src, bytes, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d->d_foff, foff.data(), (uint64_t)n * 8u, hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(d->d_fbytes, frame_bytes + f0, (uint64_t)n * 4u, hipMemcpyHostToDevice, st));
-        rc = decode_chunk(c, d->d_frames, d->d_foff, d->d_fbytes, n, pcm_out, pcm_cap, &written, n_samples,
+        rc = decode_chunk(c, d->d_frames.get(), d->d_foff, d->d_fbytes, n, pcm_out, pcm_cap, &written, n_samples,
                           (dec::Result *)results + f0, [] {});
         if (rc) return rc;
         src += bytes;
@@ -940,8 +862,8 @@ int fg::decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uin
     HIPCHK(hipSetDevice(c->device));
     int rc = dec_scratch(c);
     if (rc) return rc;
-    DecScratch *d = c->dec;
-    hipStream_t st = c->stream;
+    DecScratch *d = c->dec.get();
+    hipStream_t st = c->stream.get();
     IdxScratch *x = idx_scratch(c);
     if (!x) return 1;
     const uint64_t fcap = table_cap_for(len);
@@ -953,11 +875,10 @@ int fg::decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uin
         v.take(fcap, f_off, f_bytes);
         return v.take(1, d_res);
     };
-    if (grow(x->table, x->table_cap, table(nullptr), &st) != hipSuccess) return 1;
-    table(x->table);
-    if (grow(d->d_frames, d->frames_cap, len + 16u, &st) != hipSuccess) return 1;
-    HIPCHK(hipMemcpyAsync(d->d_frames, p, len, hipMemcpyHostToDevice, st));
-    rc = index_core(c, d->d_frames, len, stream_bits, stream_rate, f_off, f_bytes, fcap, d_res, st);
+    if (fit(x->table, table, &st) != hipSuccess) return 1;
+    if (d->d_frames.grow(len + 16u, &st) != hipSuccess) return 1;
+    HIPCHK(hipMemcpyAsync(d->d_frames.get(), p, len, hipMemcpyHostToDevice, st));
+    rc = index_core(c, d->d_frames.get(), len, stream_bits, stream_rate, f_off, f_bytes, fcap, d_res, st);
     if (rc == FLACGPU_ERR_OUT_OF_MEMORY) return 1;
     if (rc) return rc;
     idx::IndexResult ir{};
@@ -975,7 +896,7 @@ int fg::decode_stream_resident(flacgpu_ctx *c, const uint8_t *p, size_t len, uin
     };
     for (uint64_t f0 = 0; f0 < n_frames; f0 += c->max_frames) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(c->max_frames, n_frames - f0);
-        rc = decode_chunk(c, d->d_frames, f_off + f0, f_bytes + f0, n, pcm_out, pcm_cap, &written, n_samples, res.data(),
+        rc = decode_chunk(c, d->d_frames.get(), f_off + f0, f_bytes + f0, n, pcm_out, pcm_cap, &written, n_samples, res.data(),
                           hash);
         if (rc) return rc;
         for (uint32_t i = 0; i < n; i++)
@@ -1002,11 +923,11 @@ int fg::decode_files_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *
     HIPCHK(hipSetDevice(c->device));
     int rc = dec_scratch(c);
     if (rc) return rc;
-    DecScratch *d = c->dec;
-    hipStream_t st = c->stream;
+    DecScratch *d = c->dec.get();
+    hipStream_t st = c->stream.get();
     IdxScratch *x = idx_scratch(c);
     if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
-    const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u);
+    const uint64_t per = (uint64_t)c->fmt.channels * c->fmt.bytes_per_sample;
     std::vector<uint64_t> offs, lens, pcm_offs, pcm_caps;
     std::vector<idx::IndexResult> ires;
     std::vector<streams::StreamResult> res;
@@ -1020,20 +941,20 @@ int fg::decode_files_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *
     }
     rc = upload_files(c, n, p, len, offs, lens, st);
     if (rc) return rc;
-    rc = streams_index(c, d->d_frames, n, offs.data(), lens.data(), bits, rates, tb, ires, st);
+    rc = streams_index(c, d->d_frames.get(), n, offs.data(), lens.data(), bits, rates, tb, ires, st);
     if (rc) return rc;
     // the regions: what the file's frames can hold at most, cut to the caller's capacity
     uint64_t pcm_total = 0, longest = 0;
     for (uint32_t i = 0; i < n; i++) {
         const bool ok = ires[i].status == idx::IDX_OK && ires[i].n_frames <= tb.caps[i];
-        const uint64_t most = ok ? ires[i].n_frames * (uint64_t)c->cfg.block_size * per : 0u;
+        const uint64_t most = ok ? ires[i].n_frames * (uint64_t)c->fmt.max_block * per : 0u;
         pcm_offs[i] = pcm_total;
         pcm_caps[i] = std::min<uint64_t>(most, pcm_cap[i]);
         pcm_total += (pcm_caps[i] + 63u) & ~(uint64_t)63u;
         longest = std::max(longest, pcm_caps[i]);
     }
     const bool device_md5 = flacgpu_md5_engine_for(n, longest, pcm_total) == FLACGPU_MD5_DEVICE;
-    HIPCHK(grow(d->d_pcm, d->pcm_cap, pcm_total + 16u, &st));
+    HIPCHK(d->d_pcm.grow(pcm_total + 16u, &st));
     streams::StreamResult *d_res = nullptr;
     uint8_t *d_dig = nullptr;
     auto carve = [&](uint8_t *base) {
@@ -1041,9 +962,8 @@ int fg::decode_files_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *
         v.take(n, d_res);
         return v.take(16u * (uint64_t)n, d_dig);
     };
-    HIPCHK(grow(x->files, x->files_cap, carve(nullptr), &st));
-    carve(x->files);
-    rc = streams_decode(c, d->d_frames, n, tb, ires, d->d_pcm, pcm_offs.data(), pcm_caps.data(), d_res,
+    HIPCHK(fit(x->files, carve, &st));
+    rc = streams_decode(c, d->d_frames.get(), n, tb, ires, d->d_pcm.get(), pcm_offs.data(), pcm_caps.data(), d_res,
                         device_md5 ? d_dig : nullptr, st);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(res.data(), d_res, (uint64_t)n * sizeof(streams::StreamResult), hipMemcpyDeviceToHost, st));
@@ -1058,7 +978,7 @@ int fg::decode_files_resident(flacgpu_ctx *c, uint32_t n, const uint8_t *const *
         take_single[i] = clean ? 0 : 1;
         if (!clean) continue;
         n_samples[i] = res[i].n_samples;
-        if (bytes) HIPCHK(hipMemcpyAsync(pcm_out[i], d->d_pcm + pcm_offs[i], bytes, hipMemcpyDeviceToHost, st));
+        if (bytes) HIPCHK(hipMemcpyAsync(pcm_out[i], d->d_pcm.get() + pcm_offs[i], bytes, hipMemcpyDeviceToHost, st));
         if (!device_md5) {
             hp.push_back(pcm_out[i]);
             hl.push_back(bytes);
@@ -1089,11 +1009,11 @@ int fg::decode_files_windows_resident(flacgpu_ctx *c, uint32_t n, const uint8_t 
     HIPCHK(hipSetDevice(c->device));
     int rc = dec_scratch(c);
     if (rc) return rc;
-    DecScratch *d = c->dec;
-    hipStream_t st = c->stream;
+    DecScratch *d = c->dec.get();
+    hipStream_t st = c->stream.get();
     IdxScratch *x = idx_scratch(c);
     if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
-    const uint64_t per = (uint64_t)c->g.C * (c->g.bits / 8u);
+    const uint64_t per = (uint64_t)c->fmt.channels * c->fmt.bytes_per_sample;
     std::vector<uint64_t> offs, lens, first, caps, out_offs;
     std::vector<window::WindowResult> res;
     try {
@@ -1121,14 +1041,13 @@ int fg::decode_files_windows_resident(flacgpu_ctx *c, uint32_t n, const uint8_t 
         v.take(n, d_totals, d_ires);
         return v.take(entries, f_bytes);
     };
-    HIPCHK(grow(x->table, x->table_cap, table(nullptr), &st));
-    table(x->table);
-    rc = index_streams_core(c, d->d_frames, n, offs.data(), lens.data(), bits, rates, first.data(), caps.data(), f_off, f_bytes,
+    HIPCHK(fit(x->table, table, &st));
+    rc = index_streams_core(c, d->d_frames.get(), n, offs.data(), lens.data(), bits, rates, first.data(), caps.data(), f_off, f_bytes,
                             d_ires, st);
     if (rc) return rc;
-    rc = positions_core(c, d->d_frames, n, first.data(), caps.data(), f_off, f_bytes, d_ires, bits, rates, f_pos, d_totals, st);
+    rc = positions_core(c, d->d_frames.get(), n, first.data(), caps.data(), f_off, f_bytes, d_ires, bits, rates, f_pos, d_totals, st);
     if (rc) return rc;
-    const deliver::Delivery bytes = deliver::identity_delivery(deliver::SAMPLE_BYTES, 0u, c->g.C, c->g.bits / 8u);
+    const deliver::Delivery bytes = deliver::identity_delivery(deliver::SAMPLE_BYTES, 0u, c->fmt.channels, c->fmt.bytes_per_sample);
     WindowsCall wc;
     rc = windows_cover(c, first.data(), d_ires, f_pos, d_totals, n_windows, window_file, window_start, window_count, pcm_cap,
                        bytes, wc, st);
@@ -1148,9 +1067,8 @@ int fg::decode_files_windows_resident(flacgpu_ctx *c, uint32_t n, const uint8_t 
         v.take(n_windows, d_wres);
         return v.take(out_total + 16u, d_out);
     };
-    HIPCHK(grow(x->win_out, x->win_out_cap, carve(nullptr), &st));
-    carve(x->win_out);
-    rc = windows_decode(c, d->d_frames, first.data(), f_off, f_bytes, wc, window_file, window_count, bytes, d_out,
+    HIPCHK(fit(x->win_out, carve, &st));
+    rc = windows_decode(c, d->d_frames.get(), first.data(), f_off, f_bytes, wc, window_file, window_count, bytes, d_out,
                         out_offs.data(), d_wres, st);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(res.data(), d_wres, (uint64_t)n_windows * sizeof(window::WindowResult), hipMemcpyDeviceToHost, st));
