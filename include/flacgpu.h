@@ -733,6 +733,70 @@ int flacgpu_decode_windows_device_resample(flacgpu_ctx *ctx, const uint8_t *d_da
                                            uint32_t src_rate, uint32_t dst_rate,
                                            void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
                                            flacgpu_window_result *d_results, void *hip_stream);
+/* The same delivery as short-time power spectra, bare or folded onto the rows of a filter bank (mel
+ * bands, for one).  N = n_fft is even, 16 <= N <= 2048; H = hop, 1 <= H <= N; B = N / 2 + 1 bins;
+ * R = n_rows, 0 <= R <= 256, R = 0 meaning no filter bank: the rows are the B bins.  The table, in
+ * double, rounded once to float: w[n] = 0.5 - 0.5 cos(2 pi n / N) (the periodic Hann window),
+ * c[b][n] = (float)(w[n] cos(2 pi ((b n) mod N) / N)), s[b][n] = (float)(-w[n] sin(2 pi ((b n) mod N) / N)),
+ * b n reduced in integers.  flacgpu_features_table (host only, no device) gives it as [2][B][N], the
+ * cos plane then the sin plane; *n = 2 B N, FLACGPU_ERR_OUTPUT_TOO_SMALL (with *n set) where cap is
+ * less, FLACGPU_ERR_INVALID_INPUT for an invalid n_fft. */
+typedef struct { uint32_t n_fft, hop, n_rows; } flacgpu_features;
+int flacgpu_features_table(uint32_t n_fft, float *table, size_t cap, size_t *n);
+/* The rule.  x is one output channel of the delivery as FLACGPU_SAMPLE_F32 elements at the delivered
+ * rate -- what flacgpu_decode_windows_device_mix delivers, or _resample where the rates differ --
+ * `total` samples, +0.0f outside [0, total).  Frame t of a window that starts at sample `start` is
+ * centred at q = start + t H and reads xf[n] = x[q - N / 2 + n].  re_b = +0.0f, then for n = 0 .. N - 1
+ * in this order re_b = fmaf(c[b][n], xf[n], re_b); im_b the same chain with s;
+ * P_b = fmaf(im_b, im_b, re_b * re_b), the product rounded to float first.  Row r is P_r (R = 0), or
+ * with the caller's F[R][B] (float32, finite, host memory) m_r = +0.0f, then for b = 0 .. B - 1 in
+ * this order m_r = fmaf(F[r][b], P_b, m_r).  The elements are linear power: no logarithm is applied
+ * (two libraries' logf do not agree bit for bit).  Every frame t < frames is computed by this rule:
+ * a frame that reaches past either end of the stream reads zeros there, one wholly outside is +0.0f
+ * in every row; there is no other padding.  *n counts the frames whose centre lies inside the
+ * stream: 0 where start >= total, else min(frames, ceil((total - start) / H)).
+ * flacgpu_features_f32_host (host only) is this rule over one channel x[0 .. total), total <= 2^40,
+ * (frames - 1) H + N < 2^31: y is [rows][frames].  It passes over zero entries of F, which changes
+ * no bit (P is finite, so fmaf(0, P, m) = m).  It is a statement of the rule for callers and tests,
+ * bit for bit what the device delivers; it is NOT a decode path. */
+int flacgpu_features_f32_host(const float *x, uint64_t total, const flacgpu_features *ft, const float *filters,
+                              uint64_t start, uint64_t frames, float *y, uint64_t *n);
+/* The call.  window_start is in samples at the delivered rate, window_frames[w] the frame count;
+ * src_rate = dst_rate = 0 is no rate change, otherwise the ratio rules of _resample hold;
+ * channel_masks NULL is the identity of the context's C channels (K = C), else K = out_channels.
+ * Row r, frame t of channel k is element (k rows + r) frames + t from d_out + out_offsets[w] *
+ * element size; an OK window fills exactly K rows frames elements.  sample_format is
+ * FLACGPU_SAMPLE_F32, or F16 / BF16: the F32 value narrowed as every other element is (linear power
+ * can pass 65504: F16 then rounds to infinity; BF16 keeps the range).  n_samples of a result is the
+ * rule's n (frames); first_frame and n_frames are those of the covering frames of the samples
+ * [start - N / 2, start + (frames - 1) H + N / 2) inside the stream -- through the resampler's own
+ * reach where the rates differ -- and BAD_INDEX and BAD_FRAME are as in _resample over them.
+ * TOO_SMALL where K rows frames exceeds out_caps[w] (no product overflows), decided before anything
+ * is decoded.  A window that is not OK writes nothing, and nothing is ever written outside a
+ * window's elements.  FLACGPU_ERR_INVALID_INPUT before any device work: an invalid *ft, a NULL
+ * filters with R > 0, a non-finite entry of filters, FLACGPU_SAMPLE_I32 or an unknown format, an
+ * invalid ratio, a span (frames - 1) H + N of 2^31 or more, and every argument error of _mix (a
+ * NULL channel_masks excepted).  The call runs in two stages: the window delivery itself leaves
+ * every window's span as F32 in scratch the context owns (freed by flacgpu_close), then one kernel
+ * computes the frames on the f32-input matrix instructions, whose accumulation is the chain above
+ * bit for bit.  The STFT table (one per n_fft, kept) and the filter bank (found again by its
+ * content; the context keeps the last 16) live in device memory the context owns, uploaded by the
+ * first call that needs them -- that call waits for hip_stream once more for each.  The one wait for
+ * the covers, the 65535-window limit, the chunks and the stream semantics are those of
+ * flacgpu_decode_windows_device; the feature kernel is not timed. */
+int flacgpu_decode_windows_device_features(flacgpu_ctx *ctx, const uint8_t *d_data,
+                                           uint32_t n_streams, const uint64_t *table_first,
+                                           const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                           const flacgpu_index_result *d_index_results,
+                                           const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
+                                           uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
+                                           const uint64_t *window_frames,
+                                           uint32_t sample_format,
+                                           uint32_t out_channels, const uint8_t *channel_masks,
+                                           uint32_t src_rate, uint32_t dst_rate,
+                                           const flacgpu_features *ft, const float *filters,
+                                           void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
+                                           flacgpu_window_result *d_results, void *hip_stream);
 /* Windows of whole files in host memory: window w is samples [window_start[w], + window_count[w])
  * of file window_file[w] (< n_files), delivered to pcm_out[w] (capacity pcm_cap[w]) with
  * n_samples[w].  Metadata is parsed on the host as in flacgpu_decode_files; the good files' frames

@@ -68,6 +68,16 @@ to a call bound by the parse kernel.  The first outputs of the first and the las
 with flacgpu.resample_f32_host over the PCM, bit for bit.
 
     python tools/decode_rate.py --legs resample --resample-out profiles/decode_resample_rate.json
+
+The features leg (--features-out; opt-in, not part of `all`) takes the resample leg's files and windows, both
+channels, at n_fft 400, hop 160 and 80 mel rows, f32: flacgpu_decode_windows_device_features at the
+files' own rate and 44100 -> 48000, each beside the call a caller had before it -- the _mix or
+_resample delivery of the same samples, then torch.stft (zero padding at the crop's edges) and the
+matmul with the same mel matrix -- alternated in one run.  It records the medians and their ratio; no
+ratio is claimed in advance.  The first frames of the first and last window are compared with
+flacgpu.features_f32_host bit for bit, and the interior frames of the two paths with each other.
+
+    python tools/decode_rate.py --legs features --features-out profiles/decode_features_rate.json
 """
 import argparse
 import contextlib
@@ -793,6 +803,80 @@ def resample_rate(n_files: int, frames_each: int, window: int, warmup: int, repe
     return res
 
 
+def features_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: int, dst_rate: int = 48000) -> dict:
+    import numpy as np
+    import torch
+
+    import flacbank
+    import flacgpu
+
+    n_fft, hop, n_mels = 400, 160, 80
+    with resident_windows(n_files, frames_each, window) as r:
+        enc, ch, bits, dev, pcm, n_each, st, crops = r.enc, r.ch, r.bits, r.dev, r.pcm, r.n_each, r.st, r.crops
+        tables, d_wres, start = r.tables, r.d_wres, r.start
+        r.positions()
+        L, M, _ = flacgpu.resample_ratio(r.rate, dst_rate)
+        out_start, out_count = -(-start * L // M), window * L // M
+        planar_pad = flacgpu.DELIVER_PLANAR | flacgpu.DELIVER_PAD
+        masks = [1 << c for c in range(ch)]
+        mel = flacbank.mel_filters(16000, n_fft, n_mels)
+        d_mel = torch.from_numpy(mel).to(dev)
+        hann = torch.hann_window(n_fft, periodic=True, device=dev)
+        v = np.frombuffer(pcm, dtype=np.int16).reshape(n_each, ch)[:, 0].astype(np.float32) * np.float32(2.0 ** -(bits - 1))
+        res = {"files": n_files, "frames_per_file": frames_each, "channels": ch, "bits": bits, "n_fft": n_fft, "hop": hop,
+               "rows": n_mels, "layout": "f32, [window, channel, row, frame]", "warmup": warmup, "repeats": repeats}
+        for name, src, dst, w_start, w_count in (("own_rate", 0, 0, start, window), ("resampled", r.rate, dst_rate, out_start, out_count)):
+            frames = w_count // hop + 1  # torch.stft's count with center=True
+            per = ch * n_mels * frames
+            wins = [(i, w_start, frames) for i in range(n_files)]
+            samp = [(i, w_start, w_count) for i in range(n_files)]
+            x_feat = torch.zeros((n_files, ch, n_mels, frames), dtype=torch.float32, device=dev)
+            x_pcm = torch.zeros((n_files, ch, w_count), dtype=torch.float32, device=dev)
+
+            def features():
+                enc.decode_windows_device_features(*tables, wins, flacgpu.SAMPLE_F32, masks, src, dst, n_fft, hop, mel,
+                                                   x_feat.data_ptr(), [i * per for i in range(n_files)], [per] * n_files,
+                                                   d_wres.data_ptr(), stream=st)
+                return x_feat
+
+            def deliver_then_torch():
+                to = (x_pcm.data_ptr(), [i * ch * w_count for i in range(n_files)], [ch * w_count] * n_files, d_wres.data_ptr())
+                if src:
+                    enc.decode_windows_device_resample(*tables, samp, flacgpu.SAMPLE_F32, planar_pad, masks, src, dst, *to, stream=st)
+                else:
+                    enc.decode_windows_device_mix(*tables, samp, flacgpu.SAMPLE_F32, planar_pad, masks, *to, stream=st)
+                z = torch.stft(x_pcm.reshape(n_files * ch, w_count), n_fft, hop, window=hann, center=True, pad_mode="constant",
+                               return_complex=True)
+                return torch.matmul(d_mel, z.real * z.real + z.imag * z.imag).reshape(n_files, ch, n_mels, frames)
+
+            legs = {"features_f32": features, "deliver_then_stft_matmul": deliver_then_torch}
+            for _ in range(warmup):  # the first features call also builds and uploads the two tables
+                for fn in legs.values():
+                    fn()
+                    enc.sync_check(st)
+            got, other = features().cpu(), deliver_then_torch().cpu()
+            check = 8
+            sig = v if not src else flacgpu.resample_f32_host(v, src, dst)
+            want, _ = flacgpu.features_f32_host(sig, n_fft, hop, w_start, check, mel)
+            assert torch.equal(got[0, 0, :, :check], torch.from_numpy(want)) and torch.equal(got[-1, 0, :, :check], torch.from_numpy(want)), \
+                "the device differs from the host rule"
+            inner = slice(2, frames - 3)  # the crop's edge frames differ by design: the stream's samples against zero padding
+            rel = ((got[..., inner] - other[..., inner]).abs().max() / other[..., inner].abs().max()).item()
+            assert rel < 1e-4, rel
+            ms = {k: [] for k in legs}
+            for _ in range(repeats):  # alternated
+                for k, fn in legs.items():
+                    ms[k].append(event_ms(fn))
+            row = {"src_rate": src or r.rate, "dst_rate": dst or r.rate, "window_start": w_start, "window_samples": w_count,
+                   "frames": frames, "frames_checked_against_the_host_rule": 2 * check, "interior_max_rel_diff_of_the_two_paths": rel}
+            for k in legs:
+                row[k] = summary(ms[k], keep=True)
+            row["features_f32"]["x_deliver_then_stft_matmul"] = (row["deliver_then_stft_matmul"]["ms_median"] /
+                                                                 row["features_f32"]["ms_median"])
+            res[name] = row
+    return res
+
+
 def bigblock_rate(blocks, n_streams: int, warmup: int, repeats: int) -> dict:
     import numpy as np
     import torch
@@ -866,9 +950,10 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix", "resample"),
+    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix", "resample", "features"),
                     default="all")
     ap.add_argument("--resample-out", default=os.path.join(ROOT, "profiles", "decode_resample_rate.json"))
+    ap.add_argument("--features-out", default=os.path.join(ROOT, "profiles", "decode_features_rate.json"))
     ap.add_argument("--mix-out", default=os.path.join(ROOT, "profiles", "decode_mix_rate.json"))
     ap.add_argument("--bigblock-out", default=os.path.join(ROOT, "profiles", "decode_bigblock_rate.json"))
     ap.add_argument("--blocks", default="4096,4608,16384")
@@ -899,6 +984,13 @@ def main():
         print(json.dumps({"resample": rr}), flush=True)
         with open(a.resample_out, "w") as f:
             json.dump(rr, f, indent=1)
+            f.write("\n")
+        return
+    if a.legs == "features":  # opt-in: `all` leaves it out
+        fr = {"c2": features_rate(a.files, a.frames // a.files, a.window, a.warmup, a.repeats)}
+        print(json.dumps({"features": fr}), flush=True)
+        with open(a.features_out, "w") as f:
+            json.dump(fr, f, indent=1)
             f.write("\n")
         return
     if a.legs == "deliver":  # opt-in: `all` leaves it out

@@ -91,7 +91,9 @@ struct FG_LOCAL EncState {
 // Decode scratch of a context (allocated by its first decode call, max_frames frames), one
 // allocation: the subframe descriptors k_dec_parse leaves for k_dec_recon, the parsed block sizes
 // and their scan, the expected frame table of a verify, and a chunk's frame table and results in
-// the host-buffer decodes (decode_chunk).  Those decodes' frames and PCM are grow-only.
+// the host-buffer decodes (decode_chunk).  Those decodes' frames and PCM are grow-only.  The feature
+// delivery (fg_features.hpp) adds what its first stage leaves for k_features: the windows' extended
+// spans as planar F32 (feat_x) and their records and stage-1 results (feat_win), grow-only.
 struct FG_LOCAL DecScratch {
     DevBuf<uint8_t> buf;
     uint64_t *samp_off, *total, *exp_off, *exp_number, *d_foff;
@@ -99,6 +101,8 @@ struct FG_LOCAL DecScratch {
     dec::DecSub *subs;
     uint32_t *blocks, *body, *exp_n, *d_fbytes, *ctl, *d_bad;  // ctl: [0] ticket
     DevBuf<uint8_t> d_frames, d_pcm;
+    DevBuf<float> feat_x;
+    DevBuf<uint8_t> feat_win;
 };
 
 // Index scratch of a context, grow-only: the arrays of idx::IdxArgs, sized from the call's len and
@@ -109,14 +113,29 @@ struct FG_LOCAL DecScratch {
 // the windows of a call as the caller states them with their cover records (win_in), what the chunk
 // loop over the covering frames needs (win), those frames' PCM (win_pcm), and the delivered bytes
 // and results of flacgpu_decode_files_windows (win_out).  The resampled delivery adds the
-// coefficient tables of the ratios it has served, kept until the context is closed (tables).
+// coefficient tables of the ratios it has served, kept until the context is closed (tables).  The
+// feature delivery adds, in k_features' operand layout, the STFT tables of the n_fft it has served
+// (feat_tables, kept as the resampler's) and the filter banks, found again by their content
+// (feat_filters: the last kMaxFeatFilters of them).
 struct FG_LOCAL ResampleTable {
     uint32_t L, M;
     DevBuf<float> coeffs;  // L rows of T
 };
+struct FG_LOCAL FeatTable {
+    uint32_t n_fft;
+    DevBuf<float> blocks;
+};
+struct FG_LOCAL FeatFilter {
+    uint32_t rows, bins;
+    std::vector<float> host;  // [rows][bins], what the caller passed
+    DevBuf<float> blocks;
+};
+constexpr size_t kMaxFeatFilters = 16;
 struct FG_LOCAL IdxScratch {
     DevBuf<uint8_t> buf, table, packed, files, pos, win_in, win, win_pcm, win_out;
     std::vector<ResampleTable> tables;
+    std::vector<FeatTable> feat_tables;
+    std::vector<FeatFilter> feat_filters;
 };
 
 }  // namespace fg
@@ -196,6 +215,10 @@ struct Delivery;
 namespace resample {
 struct Ratio;
 }
+namespace feat {
+struct Params;
+}
+struct FeatWindow;
 
 // fg_api.cpp: an event of the context's pool, or a new one (empty: none could be created)
 FG_LOCAL Event get_event(flacgpu_ctx *c);
@@ -250,6 +273,11 @@ hipError_t launch_window_resample(const window::Cover *recs, const streams::Stre
                                   const uint64_t *totals, const uint8_t *scratch, const uint64_t *src_base, uint8_t *out,
                                   const uint64_t *dst_off, const deliver::Delivery &dv, const resample::Ratio &rt,
                                   const float *coeffs, uint32_t n, uint64_t max_samples, hipStream_t st);
+// fg_features.hip: stage 2 of the feature delivery, over the planar F32 spans stage 1 left in x
+hipError_t launch_features(const FeatWindow *wins, const window::WindowResult *stage1, const uint64_t *totals,
+                           const resample::Ratio &rt, const float *x, const float *table, const float *filters, uint8_t *out,
+                           window::WindowResult *results, const feat::Params &ft, uint32_t K, uint32_t format, uint32_t n,
+                           uint64_t max_items, hipStream_t st);
 // fg_misc.hip
 hipError_t launch_md5_streams(const uint8_t *base, const uint64_t *offs, const uint64_t *lens, const uint8_t *fin,
                               uint32_t n, Md5State *states, uint8_t *digests, hipStream_t st, int kernel, int prio);

@@ -4,12 +4,15 @@
 // refuses them, through the host index and flacgpu_decode_frames; flacgpu_decode_files does the
 // same for many files through one batch (fg_dec_host.cpp decode_files_resident).  Plain C++ over
 // include/flacgpu.h and the shared decode core.  And the host statement of the resampling rule
-// (fg_resample.hpp): the coefficient table of a ratio and the sample rule over F32 elements.
+// (fg_resample.hpp): the coefficient table of a ratio and the sample rule over F32 elements; and of
+// the feature rule (fg_features.hpp): the STFT table and the rule over one channel of F32 elements.
+#include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "../../include/flacgpu.h"
 #include "fg_dec.hpp"
+#include "fg_features.hpp"
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
 #include "fg_md5_host.hpp"
@@ -327,6 +330,71 @@ int flacgpu_resample_f32_host(const float *x, uint64_t total, uint32_t src_rate,
         });
     }
     *n = got;
+    return FLACGPU_OK;
+}
+
+int flacgpu_features_table(uint32_t n_fft, float *table, size_t cap, size_t *n) {
+    const feat::Params p{n_fft, 1u, 0u};
+    if (!n || (cap && !table) || !feat::valid(p)) return FLACGPU_ERR_INVALID_INPUT;
+    const uint32_t N = n_fft, B = feat::bins(p);
+    *n = (size_t)2u * B * N;
+    if (*n > cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
+    // feat::table_entry with the N window values and the N angles' cosines and sines computed once
+    double w[feat::kMaxFft], cv[feat::kMaxFft], sv[feat::kMaxFft];
+    for (uint32_t m = 0; m < N; m++) {
+        const double a = feat::kTwoPi * (double)m / (double)N;
+        w[m] = feat::hann(N, m);
+        cv[m] = cos(a);
+        sv[m] = sin(a);
+    }
+    for (uint32_t b = 0; b < B; b++)
+        for (uint32_t k = 0; k < N; k++) {
+            const uint32_t m = (uint32_t)(((uint64_t)b * k) % N);
+            table[(size_t)b * N + k] = (float)(w[k] * cv[m]);
+            table[((size_t)B + b) * N + k] = (float)(-w[k] * sv[m]);
+        }
+    return FLACGPU_OK;
+}
+
+int flacgpu_features_f32_host(const float *x, uint64_t total, const flacgpu_features *ft, const float *filters, uint64_t start,
+                              uint64_t frames, float *y, uint64_t *n) {
+    if (!n || !ft || (total && !x) || total > (1ull << 40)) return FLACGPU_ERR_INVALID_INPUT;
+    const feat::Params p{ft->n_fft, ft->hop, ft->n_rows};
+    if (!feat::valid(p) || (p.n_rows && !filters)) return FLACGPU_ERR_INVALID_INPUT;
+    const uint32_t N = p.n_fft, B = feat::bins(p), R = feat::rows(p);
+    for (size_t i = 0; i < (size_t)p.n_rows * B; i++)
+        if (!std::isfinite(filters[i])) return FLACGPU_ERR_INVALID_INPUT;
+    if (frames && frames - 1u > (0x7FFFFFFFull - N) / p.hop) return FLACGPU_ERR_INVALID_INPUT;
+    *n = feat::delivered(p, total, start, frames);
+    if (frames == 0) return FLACGPU_OK;
+    if (!y) return FLACGPU_ERR_INVALID_INPUT;
+    std::vector<float> table, xf(N), P(B);
+    size_t tn = 0;
+    try {
+        table.resize((size_t)2u * B * N);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    const int rc = flacgpu_features_table(N, table.data(), table.size(), &tn);
+    if (rc) return rc;
+    for (uint64_t t = 0; t < frames; t++) {
+        // sample i of the frame is x[first + i]; a start past 2^41 >= 2 * total + span is wholly outside
+        const bool far = start > (1ull << 41);
+        const int64_t first = far ? 0 : (int64_t)(start + t * p.hop) - (int64_t)(N / 2u);
+        bool any = false;
+        for (uint32_t i = 0; i < N; i++) {
+            const int64_t at = first + (int64_t)i;
+            const bool in = !far && at >= 0 && (uint64_t)at < total;
+            xf[i] = in ? x[at] : 0.0f;
+            any = any || in;
+        }
+        for (uint32_t b = 0; b < B && any; b++) P[b] = feat::bin_power(table.data(), N, b, [&](uint32_t i) { return xf[i]; });
+        for (uint32_t r = 0; r < R; r++) {
+            float v = 0.0f;  // a frame wholly outside the stream: every chain stays at +0.0f
+            if (any) v = p.n_rows ? feat::filter_row_skip(filters + (size_t)r * B, P.data(), B) : P[r];
+            y[(size_t)r * frames + t] = v;
+        }
+    }
     return FLACGPU_OK;
 }
 

@@ -6,11 +6,14 @@
 // sample-window decode (fg_window.hpp, fg_window.hip): the positions of indexed streams, windows
 // over resident tables -- as PCM bytes or as tensor elements (fg_deliver.hpp) -- and the device
 // side of flacgpu_decode_files_windows; and the same windows stated and delivered at another
-// sample rate (fg_resample.hpp, fg_resample.hip).  The host-only side (metadata, the host index,
+// sample rate (fg_resample.hpp, fg_resample.hip), and as short-time power spectra and filter-bank
+// rows over that delivery (fg_features.hpp, fg_features.hip).  The host-only side (metadata, the host index,
 // flacgpu_decode_file / _files) is fg_dec_api.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstring>
 #include <new>
 #include <vector>
 
@@ -18,6 +21,7 @@
 #include "fg_ctx.hpp"
 #include "fg_dec.hpp"
 #include "fg_deliver.hpp"
+#include "fg_features.hpp"
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
 #include "fg_resample.hpp"
@@ -814,6 +818,213 @@ int flacgpu_decode_windows_device_resample(flacgpu_ctx *c, const uint8_t *d_data
                           d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
                           sample_format, flags, out_channels, channel_masks, d_out, out_offsets, out_caps, d_results, hip_stream,
                           src_rate, dst_rate);
+}
+
+}  // extern "C"
+
+namespace {
+
+// An operand table of k_features: `cols` columns of `depth` entries as blocks of 64 lanes x 4 floats,
+// block (column tile ct, k block kb, plane p of `planes`) at ((ct * nkb + kb) * planes + p) * 256,
+// lane l's float s the entry of column ct * 16 + (l & 15) at k = kb * 16 + 4 s + (l >> 4); zero
+// where the column or k is past the table's.  at(p, col, k): the entry.
+template <class At>
+int feat_blocks(uint32_t planes, uint32_t cols, uint32_t depth, At at, std::vector<float> &blk) {
+    const uint32_t nct = (cols + 15u) / 16u, nkb = (depth + 15u) / 16u;
+    try {
+        blk.assign((size_t)nct * nkb * planes * 256u, 0.0f);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    size_t o = 0;
+    for (uint32_t ct = 0; ct < nct; ct++)
+        for (uint32_t kb = 0; kb < nkb; kb++)
+            for (uint32_t p = 0; p < planes; p++)
+                for (uint32_t l = 0; l < 64u; l++)
+                    for (uint32_t s = 0; s < 4u; s++, o++) {
+                        const uint32_t col = ct * 16u + (l & 15u), k = kb * 16u + 4u * s + (l >> 4);
+                        if (col < cols && k < depth) blk[o] = at(p, col, k);
+                    }
+    return FLACGPU_OK;
+}
+
+int feat_upload(const std::vector<float> &blk, DevBuf<float> &d, hipStream_t st) {
+    HIPCHK(d.grow(blk.size()));
+    HIPCHK(hipMemcpyAsync(d.get(), blk.data(), blk.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));  // blk goes out of scope
+    return FLACGPU_OK;
+}
+
+// The device STFT table of n_fft: flacgpu_features_table's, in operand blocks (the cos and the sin
+// plane of a block side by side), uploaded by the first call of the context that needs it, which
+// waits for st once more than the others; kept for the context's life.
+int feat_table(flacgpu_ctx *c, uint32_t N, const float **d_table, hipStream_t st) {
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
+    for (const FeatTable &t : x->feat_tables)
+        if (t.n_fft == N) {
+            *d_table = t.blocks.get();
+            return FLACGPU_OK;
+        }
+    const uint32_t B = N / 2u + 1u;
+    std::vector<float> h, blk;
+    size_t n = 0;
+    try {
+        h.resize((size_t)2u * B * N);
+        x->feat_tables.reserve(x->feat_tables.size() + 1u);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    int rc = flacgpu_features_table(N, h.data(), h.size(), &n);
+    if (rc) return rc;
+    rc = feat_blocks(2u, B, N, [&](uint32_t p, uint32_t b, uint32_t k) { return h[((size_t)p * B + b) * N + k]; }, blk);
+    if (rc) return rc;
+    DevBuf<float> d;
+    rc = feat_upload(blk, d, st);
+    if (rc) return rc;
+    *d_table = d.get();
+    x->feat_tables.push_back({N, std::move(d)});
+    return FLACGPU_OK;
+}
+
+// The device copy of a filter bank F[R][B], found again by its content; a new one is uploaded as
+// the table is.  The context keeps the last kMaxFeatFilters banks: before the oldest is dropped st
+// is waited for, since work queued on it may still read that bank.
+int feat_filter(flacgpu_ctx *c, uint32_t R, uint32_t B, const float *F, const float **d_filters, hipStream_t st) {
+    IdxScratch *x = idx_scratch(c);
+    if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
+    const size_t n = (size_t)R * B;
+    for (const FeatFilter &f : x->feat_filters)
+        if (f.rows == R && f.bins == B && std::memcmp(f.host.data(), F, n * sizeof(float)) == 0) {
+            *d_filters = f.blocks.get();
+            return FLACGPU_OK;
+        }
+    FeatFilter f;
+    std::vector<float> blk;
+    try {
+        f.host.assign(F, F + n);
+        x->feat_filters.reserve(x->feat_filters.size() + 1u);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    f.rows = R;
+    f.bins = B;
+    int rc = feat_blocks(1u, R, B, [&](uint32_t, uint32_t r, uint32_t b) { return F[(size_t)r * B + b]; }, blk);
+    if (rc) return rc;
+    rc = feat_upload(blk, f.blocks, st);
+    if (rc) return rc;
+    if (x->feat_filters.size() >= kMaxFeatFilters) {
+        HIPCHK(hipStreamSynchronize(st));
+        x->feat_filters.erase(x->feat_filters.begin());
+    }
+    *d_filters = f.blocks.get();
+    x->feat_filters.push_back(std::move(f));
+    return FLACGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Two stages.  Stage 1 is windows_device itself: every window's extended span [start - N / 2,
+// + (frames - 1) * H + N), clipped at the stream's start on the host (`clip` samples that
+// k_features reads as zeros), goes as planar padded F32 into the context's scratch.  Stage 2,
+// k_features, reads those planes and stage 1's results and writes the elements and the results.
+int flacgpu_decode_windows_device_features(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams,
+                                           const uint64_t *table_first, const uint64_t *d_frame_offsets,
+                                           const uint32_t *d_frame_bytes, const flacgpu_index_result *d_index_results,
+                                           const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
+                                           uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
+                                           const uint64_t *window_frames, uint32_t sample_format, uint32_t out_channels,
+                                           const uint8_t *channel_masks, uint32_t src_rate, uint32_t dst_rate,
+                                           const flacgpu_features *ft, const float *filters, void *d_out,
+                                           const uint64_t *out_offsets, const uint64_t *out_caps,
+                                           flacgpu_window_result *d_results, void *hip_stream) {
+    if (!c || !ft || !d_data || !table_first || !d_frame_offsets || !d_frame_bytes || !d_index_results ||
+        !d_frame_first_sample || !d_stream_samples || n_windows > 65535u)
+        return FLACGPU_ERR_INVALID_INPUT;
+    const feat::Params p{ft->n_fft, ft->hop, ft->n_rows};
+    if (!feat::valid(p) || (p.n_rows && !filters)) return FLACGPU_ERR_INVALID_INPUT;
+    if (sample_format != deliver::SAMPLE_F32 && sample_format != deliver::SAMPLE_F16 && sample_format != deliver::SAMPLE_BF16)
+        return FLACGPU_ERR_INVALID_INPUT;
+    if ((uintptr_t)d_out & (deliver::elem_size(sample_format) - 1u)) return FLACGPU_ERR_INVALID_INPUT;
+    if (n_windows && (!window_stream || !window_start || !window_frames || !d_out || !out_offsets || !out_caps || !d_results))
+        return FLACGPU_ERR_INVALID_INPUT;
+    if (channel_masks && !deliver::mix_valid(c->fmt.channels, out_channels, channel_masks, sample_format))
+        return FLACGPU_ERR_INVALID_INPUT;
+    resample::Ratio rt{0, 0, 0, 0};
+    if ((src_rate || dst_rate) && !resample::valid_ratio(src_rate, dst_rate, &rt)) return FLACGPU_ERR_INVALID_INPUT;
+    const uint32_t B = feat::bins(p), n_rows = feat::rows(p), K = channel_masks ? out_channels : c->fmt.channels;
+    for (size_t i = 0; i < (size_t)p.n_rows * B; i++)
+        if (!std::isfinite(filters[i])) return FLACGPU_ERR_INVALID_INPUT;
+    for (uint32_t w = 0; w < n_windows; w++) {
+        if (window_stream[w] >= n_streams || out_offsets[w] + out_caps[w] < out_offsets[w]) return FLACGPU_ERR_INVALID_INPUT;
+        if (window_frames[w] && window_frames[w] - 1u > (0x7FFFFFFFull - p.n_fft) / p.hop) return FLACGPU_ERR_INVALID_INPUT;
+    }
+    if (n_windows == 0) return FLACGPU_OK;
+    const FeatGeometry g = feat_geometry(p.n_fft, p.hop, p.n_rows);
+    std::vector<FeatWindow> fw;
+    std::vector<uint64_t> s_start, s_count, s_off, s_cap;
+    try {
+        fw.resize(n_windows);
+        s_start.resize(n_windows);
+        s_count.resize(n_windows);
+        s_off.resize(n_windows);
+        s_cap.resize(n_windows);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    uint64_t x_total = 0, max_items = 0;
+    const uint32_t half = p.n_fft / 2u;
+    for (uint32_t w = 0; w < n_windows; w++) {
+        const uint64_t frames = window_frames[w], start = window_start[w];  // frames < 2^31: no product below passes 2^45
+        FeatWindow &f = fw[w];
+        f.too_small = (uint64_t)K * n_rows * frames > out_caps[w] ? 1u : 0u;
+        f.clip = start < half ? (uint32_t)(half - start) : 0u;
+        f.frames = (uint32_t)frames;
+        f.stream = window_stream[w];
+        f.start = start;
+        f.out_off = out_offsets[w];
+        f.x_off = x_total;
+        f.count = f.too_small ? 0u : feat::span(p, frames) - (frames ? f.clip : 0u);  // a TOO_SMALL window is dropped from stage 1
+        s_start[w] = f.count ? start + f.clip - half : 0u;
+        s_count[w] = f.count;
+        s_off[w] = f.x_off;
+        s_cap[w] = (uint64_t)K * f.count;
+        x_total += (s_cap[w] + 3u) & ~(uint64_t)3u;
+        if (f.count) max_items = std::max(max_items, (uint64_t)K * ((frames + g.frames - 1u) / g.frames));
+    }
+    if (x_total > (1ull << 45)) return FLACGPU_ERR_OUT_OF_MEMORY;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = dec_scratch(c);
+    if (rc) return rc;
+    DecScratch *d = c->dec.get();
+    hipStream_t st = pick_stream(c, hip_stream);
+    const float *d_table = nullptr, *d_filters = nullptr;
+    rc = feat_table(c, p.n_fft, &d_table, st);
+    if (rc) return rc;
+    if (p.n_rows) {
+        rc = feat_filter(c, p.n_rows, B, filters, &d_filters, st);
+        if (rc) return rc;
+    }
+    HIPCHK(d->feat_x.grow(x_total + 4u, &st));  // an earlier call on this stream may still read the old one
+    FeatWindow *d_fw = nullptr;
+    window::WindowResult *d_s1 = nullptr;
+    auto carve = [&](uint8_t *base) {
+        Carve v{base};
+        v.take(n_windows, d_fw);
+        return v.take(n_windows, d_s1);
+    };
+    HIPCHK(fit(d->feat_win, carve, &st));
+    HIPCHK(hipMemcpyAsync(d_fw, fw.data(), (uint64_t)n_windows * sizeof(FeatWindow), hipMemcpyHostToDevice, st));
+    rc = windows_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                        d_stream_samples, n_windows, window_stream, s_start.data(), s_count.data(), deliver::SAMPLE_F32,
+                        deliver::DELIVER_PLANAR | deliver::DELIVER_PAD, out_channels, channel_masks, d->feat_x.get(), s_off.data(),
+                        s_cap.data(), (flacgpu_window_result *)d_s1, hip_stream, src_rate, dst_rate);
+    if (rc) return rc;
+    HIPCHK(launch_features(d_fw, d_s1, d_stream_samples, rt, d->feat_x.get(), d_table, d_filters, (uint8_t *)d_out,
+                           (window::WindowResult *)d_results, p, K, sample_format, n_windows, max_items, st));
+    return FLACGPU_OK;
 }
 
 // every chunk's frames and frame table are uploaded, its results land at results + f0

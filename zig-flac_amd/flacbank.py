@@ -63,12 +63,15 @@ def _out_samples(samples: int, src: int, rate: int) -> int:
 
 
 def _crops(who, device, n_files, K, groups, where, check, file, start, length, dtype, planar, pad, out, strict,
-           rate=None, rate_of=None):
+           rate=None, rate_of=None, feat=None):
     """The one body of FlacBank.crops and FlacMixBank.crops: crops of K channels from `groups` =
     [(FlacBank, its channel masks or None)], file f being file where(f)[1] of group where(f)[0];
     check(fmt): the caller's own refusals of a format, raised between the dtype's and the crops'.
     rate: start and length are in samples at that rate, rate_of(f) being file f's own: the crops of
-    files at another rate are resampled, one call per group and source rate."""
+    files at another rate are resampled, one call per group and source rate.
+    feat: the body of the two `features` as well -- (n_fft, hop, filters or None, rows) after
+    flacgpu.features_params: `length` is then the frame count, a crop is [K, rows, length] and its
+    calls are flacgpu_decode_windows_device_features, routed as the crops' are."""
     import torch
 
     dtype = torch.float32 if dtype is None else dtype
@@ -84,6 +87,8 @@ def _crops(who, device, n_files, K, groups, where, check, file, start, length, d
     if length < 0 or any(not 0 <= int(f) < n_files for f in file) or any(int(s) < 0 for s in start):
         raise ValueError(f"{who}: a file index, a start or the length is out of range")
     shape = (W, K, length) if planar else (W, length, K)
+    if feat is not None:
+        shape = (W, K, feat[3], length)
     routed = [[] for _ in groups]  # group -> its crops, in the caller's order
     for w in range(W):
         routed[where(int(file[w]))[0]].append(w)
@@ -113,7 +118,7 @@ def _crops(who, device, n_files, K, groups, where, check, file, start, length, d
         flags = (flacgpu.DELIVER_PLANAR if planar else 0) | (flacgpu.DELIVER_PAD if pad else 0)
         st = torch.cuda.current_stream(device).cuda_stream
         d_res = torch.empty(32 * max(W, 1), dtype=torch.uint8, device=device)
-        per_crop, row = K * length, 0
+        per_crop, row = K * length * (feat[3] if feat is not None else 1), 0
         for bank, masks, src, ws in calls:
             for w0 in range(0, len(ws), MAX_WINDOWS):
                 part = ws[w0:w0 + MAX_WINDOWS]
@@ -121,7 +126,10 @@ def _crops(who, device, n_files, K, groups, where, check, file, start, length, d
                 tables = (bank._data.data_ptr(), bank._first, bank._off.data_ptr(), bank._fbytes.data_ptr(),
                           bank._ires.data_ptr(), bank._pos.data_ptr(), bank._totals.data_ptr(), windows, fmt, flags)
                 to = (x.data_ptr(), [w * per_crop for w in part], [per_crop] * len(part), d_res.data_ptr() + 32 * row)
-                if src is not None:
+                if feat is not None:
+                    bank._dec.decode_windows_device_features(*tables[:-1], masks, src or 0, rate if src else 0, *feat[:3], *to,
+                                                             stream=st)
+                elif src is not None:
                     bank._dec.decode_windows_device_resample(*tables, masks, src, rate, *to, stream=st)
                 elif masks is None:
                     bank._dec.decode_windows_device_as(*tables, *to, stream=st)
@@ -138,10 +146,94 @@ def _crops(who, device, n_files, K, groups, where, check, file, start, length, d
         for w, s in enumerate(statuses):
             if s != flacgpu.WINDOW_OK:
                 bad = f", frame {res[w].first_bad_frame}" if s == flacgpu.WINDOW_BAD_FRAME else ""
-                raise flacgpu.FlacGpuError(-2, f"{who}.crops: crop {w} (file {int(file[w])}, start {int(start[w])}) is "
+                raise flacgpu.FlacGpuError(-2, f"{who}.{'features' if feat is not None else 'crops'}: crop {w} (file {int(file[w])}, start {int(start[w])}) is "
                                                f"{WINDOW_STATUS.get(s, s)}{bad}")
         return x, n
     return x, n, statuses
+
+
+def _features(who, device, n_files, K, groups, where, file, start, frames, n_fft, hop, filters, log, floor, dtype, out, strict,
+              rate, rate_of):
+    """FlacBank.features and FlacMixBank.features over _crops: the checks, and the logarithm, which
+    is torch's over the kernel's float32 (it is not part of the library's rule)."""
+    import torch
+
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise ValueError(f"{who}.features: dtype {dtype} is none of float32, float16, bfloat16")
+    if log not in (None, "ln", "log10"):
+        raise ValueError(f"{who}.features: log is None, 'ln' or 'log10', not {log!r}")
+    ft, f, rows = flacgpu.features_params(n_fft, hop, filters)
+    frames = int(frames)
+    if frames and (frames - 1) * ft.hop + ft.n_fft >= flacgpu.FEATURES_MAX_SPAN:
+        raise ValueError(f"{who}.features: {frames} frames span 2^31 samples or more")
+    feat = (ft.n_fft, ft.hop, f, rows)
+    if log is None:
+        return _crops(who, device, n_files, K, groups, where, lambda fmt: None, file, start, frames, dtype, True, False, out,
+                      strict, rate=rate, rate_of=rate_of, feat=feat)
+    shape = (len(file), K, rows, max(frames, 0))
+    if out is not None and (tuple(out.shape) != shape or out.dtype != dtype or out.device != device or not out.is_contiguous()):
+        raise ValueError(f"{who}: out must be a contiguous {dtype} tensor of shape {shape} on {device}")
+    res = _crops(who, device, n_files, K, groups, where, lambda fmt: None, file, start, frames, torch.float32, True, False,
+                 out if dtype == torch.float32 else None, strict, rate=rate, rate_of=rate_of, feat=feat)
+    x = res[0].clamp_min_(float(floor))
+    x = torch.log_(x) if log == "ln" else torch.log10_(x)
+    if out is not None and out is not x:
+        out.copy_(x)
+        x = out
+    elif dtype != torch.float32:
+        x = x.to(dtype)
+    return (x,) + tuple(res[1:])
+
+
+def _hz_to_mel(f, scale: str):
+    import numpy as np
+
+    f = np.asarray(f, dtype=np.float64)
+    if scale == "htk":
+        return 2595.0 * np.log10(1.0 + f / 700.0)
+    lin = f / (200.0 / 3.0)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1000.0) / 1000.0) / (np.log(6.4) / 27.0), lin)
+
+
+def _mel_to_hz(m, scale: str):
+    import numpy as np
+
+    m = np.asarray(m, dtype=np.float64)
+    if scale == "htk":
+        return 700.0 * (10.0 ** (m / 2595.0) - 1.0)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), (200.0 / 3.0) * m)
+
+
+def mel_filters(sample_rate: int, n_fft: int, n_mels: int, fmin: float = 0.0, fmax: Optional[float] = None,
+                scale: str = "slaney", norm: Optional[str] = "slaney"):
+    """A mel filter bank for `features`: float32 numpy [n_mels, n_fft // 2 + 1], computed in float64.
+
+    The mel scale: scale="htk": mel(f) = 2595 * log10(1 + f / 700).  scale="slaney": mel(f) =
+    3 f / 200 below 1000 Hz, and 15 + 27 * ln(f / 1000) / ln(6.4) from 1000 Hz on (linear, then
+    logarithmic with 27 steps to the factor 6.4).  With m_0 < m_1 < ... < m_{n_mels + 1} equally
+    spaced from mel(fmin) to mel(fmax) (fmax None: sample_rate / 2) and f_i = hz(m_i), bin b sits at
+    g_b = b * sample_rate / n_fft and row r is the triangle
+        F[r][b] = max(0, min((g_b - f_r) / (f_{r+1} - f_r), (f_{r+2} - g_b) / (f_{r+2} - f_{r+1}))),
+    which peaks at the centre f_{r+1}.  norm="slaney" multiplies row r by 2 / (f_{r+2} - f_r), so that
+    every triangle has area 1 over frequency in Hz; norm=None leaves the peaks at 1."""
+    import numpy as np
+
+    sample_rate, n_fft, n_mels = int(sample_rate), int(n_fft), int(n_mels)
+    fmax = sample_rate / 2.0 if fmax is None else float(fmax)
+    if scale not in ("slaney", "htk") or norm not in ("slaney", None):
+        raise ValueError("mel_filters: scale is 'slaney' or 'htk', norm 'slaney' or None")
+    if sample_rate <= 0 or not (16 <= n_fft <= 2048 and n_fft % 2 == 0) or not 1 <= n_mels <= 256:
+        raise ValueError("mel_filters: sample_rate > 0, n_fft even in 16..2048, n_mels in 1..256")
+    if not 0.0 <= float(fmin) < fmax <= sample_rate / 2.0:
+        raise ValueError("mel_filters: 0 <= fmin < fmax <= sample_rate / 2")
+    edges = _mel_to_hz(np.linspace(_hz_to_mel(float(fmin), scale), _hz_to_mel(fmax, scale), n_mels + 2), scale)
+    g = np.arange(n_fft // 2 + 1, dtype=np.float64) * (sample_rate / n_fft)
+    lo, mid, hi = edges[:-2, None], edges[1:-1, None], edges[2:, None]
+    F = np.maximum(0.0, np.minimum((g[None, :] - lo) / (mid - lo), (hi - g[None, :]) / (hi - mid)))
+    if norm == "slaney":
+        F *= 2.0 / (hi - lo)
+    return np.ascontiguousarray(F, dtype=np.float32)
 
 
 class FlacBank:
@@ -267,6 +359,25 @@ class FlacBank:
         return _crops("FlacBank", self.device, len(self), self.channels, [(self, None)], lambda f: (0, f), lambda fmt: None,
                       file, start, length, dtype, planar, pad, out, strict,
                       rate=None if rate is None else int(rate), rate_of=self.sample_rates.__getitem__)
+
+    def features(self, file: Sequence[int], start: Sequence[int], frames: int, n_fft: int, hop: int, filters=None,
+                 log: Optional[str] = None, floor: float = 1e-10, dtype=None, out=None, strict: bool = True,
+                 rate: Optional[int] = None):
+        """`frames` short-time power frames of file[w] for every w, frame t centred at sample
+        start[w] + t * hop -> (x, n), or (x, n, statuses) with strict=False: x of shape
+        [W, channels, rows, frames]; n[w] the frames whose centre lies inside the file.  Frames are
+        computed from the stream's own samples around the crop (zeros only past the file's ends), by
+        the rule of flacgpu_decode_windows_device_features: a periodic Hann window of n_fft, the
+        power of the n_fft // 2 + 1 bins, and with `filters` (float32 [rows, bins], mel_filters for
+        one) their sums over the bins.  log: None (linear power), "ln" or "log10": the kernel then
+        delivers float32 and x is torch.log / torch.log10 of clamp_min(floor), cast to dtype.
+        dtype: torch.float32 (default), float16 (linear power above 65504 becomes inf), bfloat16.
+        rate, out, strict and the stream semantics are those of crops."""
+        if self._dec is None:
+            raise ValueError("FlacBank: closed")
+        return _features("FlacBank", self.device, len(self), self.channels, [(self, None)], lambda f: (0, f), file, start, frames,
+                         n_fft, hop, filters, log, floor, dtype, out, strict, None if rate is None else int(rate),
+                         self.sample_rates.__getitem__)
 
 
 MIX_MAX_CHANNELS = 8
@@ -421,3 +532,15 @@ class FlacMixBank:
 
         return _crops(who, self.device, len(self), self.channels, self._groups, self._where.__getitem__, check, file, start,
                       length, dtype, planar, pad, out, strict, rate=self.sample_rate, rate_of=self.sample_rates.__getitem__)
+
+    def features(self, file: Sequence[int], start: Sequence[int], frames: int, n_fft: int, hop: int, filters=None,
+                 log: Optional[str] = None, floor: float = 1e-10, dtype=None, out=None, strict: bool = True):
+        """FlacBank.features over the mixed bank -> (x, n), or (x, n, statuses) with strict=False: x of
+        shape [W, channels, rows, frames], every crop mixed to the bank's channels by its file's masks
+        before it is framed; in a bank with a sample_rate, start and hop are in samples at that rate
+        and files at another go through the resampler first.  Routed and queued as crops are."""
+        if not self._groups:
+            raise ValueError("FlacMixBank: closed")
+        return _features("FlacMixBank", self.device, len(self), self.channels, self._groups, self._where.__getitem__, file, start,
+                         frames, n_fft, hop, filters, log, floor, dtype, out, strict, self.sample_rate,
+                         self.sample_rates.__getitem__)

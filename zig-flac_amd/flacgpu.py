@@ -370,6 +370,10 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_resample_f32_host": (I32, [P, U64, U32, U32, U64, U64, P, ctypes.POINTER(U64)]),
         "flacgpu_decode_windows_device_resample": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, U32, U32, P, U32, U32,
                                                          P, P, P, P, P]),
+        "flacgpu_features_table": (I32, [U32, P, SZ, ctypes.POINTER(SZ)]),
+        "flacgpu_features_f32_host": (I32, [P, U64, P, P, U64, U64, P, ctypes.POINTER(U64)]),
+        "flacgpu_decode_windows_device_features": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, U32, P, U32, U32,
+                                                         P, P, P, P, P, P, P]),
     }
     # an older build named by FLACGPU_LIB (same-box A/B runs, tools/ab.sh) may predate later entry
     # points: those stay unbound there; the in-tree library must export every one
@@ -409,6 +413,7 @@ def exported_symbols() -> list:
         "flacgpu_flac_positions_streams_device", "flacgpu_decode_windows_device", "flacgpu_decode_files_windows",
         "flacgpu_decode_windows_device_as", "flacgpu_open_decoder", "flacgpu_decode_windows_device_mix",
         "flacgpu_resample_filter", "flacgpu_resample_f32_host", "flacgpu_decode_windows_device_resample",
+        "flacgpu_features_table", "flacgpu_features_f32_host", "flacgpu_decode_windows_device_features",
     ]
 
 
@@ -603,6 +608,67 @@ def resample_f32_host(x, src_rate: int, dst_rate: int, start: int = 0, count: Op
     return y[: got.value]
 
 
+class Features(ctypes.Structure):
+    """flacgpu_features: n_fft (even, 16..2048), hop (1..n_fft), n_rows (0: the bins, else the rows of
+    a filter bank, at most 256)."""
+    _fields_ = [("n_fft", ctypes.c_uint32), ("hop", ctypes.c_uint32), ("n_rows", ctypes.c_uint32)]
+
+
+FEATURES_MAX_SPAN = 1 << 31  # (frames - 1) * hop + n_fft stays below it
+
+
+def features_params(n_fft: int, hop: int, filters=None):
+    """(Features, filters as a contiguous float32 [rows, bins] numpy array or None, rows) after the
+    host checks of the feature calls; ValueError names what is wrong."""
+    import numpy as np
+
+    n_fft, hop = int(n_fft), int(hop)
+    if not (16 <= n_fft <= 2048 and n_fft % 2 == 0):
+        raise ValueError(f"features: n_fft {n_fft} is not an even number in 16..2048")
+    if not 1 <= hop <= n_fft:
+        raise ValueError(f"features: hop {hop} is not in 1..n_fft")
+    bins = n_fft // 2 + 1
+    if filters is None:
+        return Features(n_fft, hop, 0), None, bins
+    f = np.ascontiguousarray(filters, dtype=np.float32)
+    if f.ndim != 2 or f.shape[1] != bins or not 1 <= f.shape[0] <= 256:
+        raise ValueError(f"features: filters is not [1..256 rows, {bins} bins]")
+    if not np.isfinite(f).all():
+        raise ValueError("features: filters has an entry that is not finite")
+    return Features(n_fft, hop, f.shape[0]), f, f.shape[0]
+
+
+def features_table(n_fft: int):
+    """flacgpu_features_table (host only): the STFT table of n_fft, float32 [2, bins, n_fft]: the
+    windowed cosines, then the negated windowed sines."""
+    import numpy as np
+
+    ft, _, bins = features_params(n_fft, 1)
+    table, n = np.zeros(2 * bins * ft.n_fft, dtype=np.float32), ctypes.c_size_t(0)
+    _check(load_library().flacgpu_features_table(ft.n_fft, table.ctypes.data, table.size, ctypes.byref(n)), "features_table")
+    return table.reshape(2, bins, ft.n_fft)
+
+
+def features_f32_host(x, n_fft: int, hop: int, start: int, frames: int, filters=None):
+    """flacgpu_features_f32_host (host only): (y, n) -- y the float32 [rows, frames] power rows of
+    `frames` frames from sample `start` of the float32 samples x of one channel, n the frames whose
+    centre lies inside x.  The statement of the rule the device follows bit for bit: not a decode path."""
+    import numpy as np
+
+    ft, f, rows = features_params(n_fft, hop, filters)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 1:
+        raise ValueError("features_f32_host: x is one channel of samples")
+    if start < 0 or frames < 0 or (frames and (frames - 1) * ft.hop + ft.n_fft >= FEATURES_MAX_SPAN):
+        raise ValueError("features_f32_host: start or frames is negative, or the span reaches 2^31")
+    y, got = np.zeros((rows, max(frames, 1)), dtype=np.float32)[:, :frames].copy(), ctypes.c_uint64(0)
+    _check(load_library().flacgpu_features_f32_host(x.ctypes.data if len(x) else None, len(x), ctypes.byref(ft),
+                                                    f.ctypes.data if f is not None else None, start, frames,
+                                                    y.ctypes.data if frames else None, ctypes.byref(got)),
+           "features_f32_host")
+    return y, got.value
+
+
 class _DecodeOps:
     """The decode / verify entry points of a context (Encoder and Decoder share them)."""
 
@@ -728,6 +794,37 @@ class _DecodeOps:
             sample_format, flags, len(masks) if masks is not None else 0,
             (ctypes.c_uint8 * max(len(masks), 1))(*masks) if masks is not None else None, int(src_rate), int(dst_rate), d_out,
             _u64s(out_offsets), _u64s(out_caps), d_results, _stream(stream)), "decode_windows_device_resample")
+
+    def decode_windows_device_features(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int,
+                                       d_frame_bytes: int, d_index_results: int, d_frame_first_sample: int,
+                                       d_stream_samples: int, windows: Sequence, sample_format: int,
+                                       channel_masks: Optional[Sequence[int]], src_rate: int, dst_rate: int, n_fft: int,
+                                       hop: int, filters, d_out: int, out_offsets: Sequence[int], out_caps: Sequence[int],
+                                       d_results: int, stream: Optional[int] = None) -> None:
+        """flacgpu_decode_windows_device_features: windows = [(stream, start, frames)], start in samples
+        at the delivered rate; row r, frame t of channel k of window w at element
+        out_offsets[w] + (k * rows + r) * frames + t of d_out.  filters: None (the n_fft / 2 + 1 bins) or
+        float32 [rows, bins]; src_rate = dst_rate = 0: no rate change; channel_masks None: the
+        context's channels as they are.  What the host can check raises ValueError before the call."""
+        ft, f, _ = features_params(n_fft, hop, filters)
+        masks = None if channel_masks is None else [int(m) for m in channel_masks]
+        if masks is not None and (not 1 <= len(masks) <= 8 or any(not 0 <= m <= 255 for m in masks)):
+            raise ValueError("decode_windows_device_features: 1 to 8 channel masks, each in 0..255")
+        if sample_format not in (SAMPLE_F32, SAMPLE_F16, SAMPLE_BF16):
+            raise ValueError("decode_windows_device_features: the format is SAMPLE_F32, SAMPLE_F16 or SAMPLE_BF16")
+        if (src_rate or dst_rate) and resample_ratio(src_rate, dst_rate) is None:
+            raise ValueError(f"decode_windows_device_features: {src_rate} -> {dst_rate} is not a ratio the filter serves")
+        for _, start, frames in windows:
+            if start < 0 or frames < 0 or (frames and (frames - 1) * ft.hop + ft.n_fft >= FEATURES_MAX_SPAN):
+                raise ValueError("decode_windows_device_features: a window's start or frames is negative, or its span "
+                                 "reaches 2^31")
+        _check(self.lib.flacgpu_decode_windows_device_features(
+            *self._window_args(d_data, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                               d_stream_samples, windows),
+            sample_format, len(masks) if masks is not None else 0,
+            (ctypes.c_uint8 * max(len(masks), 1))(*masks) if masks is not None else None, int(src_rate), int(dst_rate),
+            ctypes.byref(ft), f.ctypes.data if f is not None else None, d_out, _u64s(out_offsets), _u64s(out_caps), d_results,
+            _stream(stream)), "decode_windows_device_features")
 
     def decode_files_windows(self, flacs: Sequence[bytes], windows: Sequence, guard: int = 0,
                              pcm_caps: Optional[Sequence[int]] = None):
