@@ -811,6 +811,47 @@ int flacgpu_decode_files_windows(flacgpu_ctx *ctx, uint32_t n_files, const void 
                                  const uint64_t *window_count, uint8_t *const *pcm_out, const size_t *pcm_cap,
                                  uint64_t *n_samples, int *status);
 
+/* ---- Elements to PCM: the inverse of the delivery --------------------------- */
+/* The rule.  An element of one of the four FLACGPU_SAMPLE_* formats becomes a sample of `bits` bits
+ * (8, 16, 24, 32).  A float format: the element widened to f32 (exact), v = x * 2^(bits-1) (a power
+ * of two: exact, or an overflow to +-inf), r = v rounded to an integer to nearest-even, clamped to
+ * [-2^(bits-1), 2^(bits-1) - 1]; NaN gives 0 and -0.0 gives 0.  The clamp compares r with +-2^(bits-1)
+ * as floats before the integer conversion (the upper limit is no f32 at 32 bits), so no conversion
+ * sees a value out of range.  FLACGPU_SAMPLE_I32: the value, clamped to the same range.  An element
+ * the clamp changed, or a NaN, is CLIPPED: 1.0 is, since a delivery only produces [-1, 1).  It is the
+ * inverse of flacgpu_decode_windows_device_as wherever that conversion is exact: a sample delivered
+ * as F32 (8, 16, 24 bits), as F16 or BF16 (8 bits) or as I32 (every depth) comes back as itself.
+ * There is no dither and no noise shaping.
+ * The PCM of a stream of T samples of C channels is T * C interleaved samples of bits / 8 bytes,
+ * signed little-endian (8-bit included), at a 4-byte-aligned byte offset: what flacgpu_plan_create
+ * takes.  The stream's last 32-bit word is written whole, its pad bytes zero; nothing past the
+ * stream's length rounded up to 4 is touched.
+ * flacgpu_pcm_from_elements_device: n_streams (at most 65535) streams in one launch, asynchronous on
+ * hip_stream, on an encode context (flacgpu_open), whose channels and depth they have.  d_src is a
+ * HOST array of device addresses, stream s's elements at any element alignment: channel c's sample
+ * t at element c * plane_stride[s] + t with FLACGPU_DELIVER_PLANAR (plane_stride[s] >= samples[s];
+ * plane_stride NULL: samples[s]), else at t * C + c.  Its PCM goes to d_pcm + pcm_offsets[s], the
+ * offsets ascending, and d_clipped[s] (device, u64) is set to its count of clipped elements.
+ * FLACGPU_ERR_INVALID_INPUT before any device work: a NULL pointer (ctx, an entry of d_src), a
+ * decode-only context, an offset that is no multiple of 4, a stream that passes pcm_cap or runs into
+ * the next one's offset, a format outside the four, a flag other than FLACGPU_DELIVER_PLANAR, a
+ * plane stride below samples[s], more than 65535 streams.  The stream table lives in device memory
+ * the context owns; the call waits for hip_stream only where that table has to grow.  Not timed. */
+int flacgpu_pcm_from_elements_device(flacgpu_ctx *ctx, uint32_t n_streams, const void *const *d_src,
+                                     const uint64_t *samples, const uint64_t *plane_stride,
+                                     uint32_t sample_format, uint32_t flags, uint8_t *d_pcm,
+                                     const uint64_t *pcm_offsets, uint64_t pcm_cap, uint64_t *d_clipped,
+                                     void *hip_stream);
+/* The same rule and the same PCM writer on the host, for one stream of `samples` samples of
+ * `channels` channels in host memory, into pcm_out (4-byte aligned, capacity cap bytes: the PCM
+ * length rounded up to 4, else FLACGPU_ERR_OUTPUT_TOO_SMALL); *clipped its count.  Needs no GPU.
+ * FLACGPU_ERR_INVALID_INPUT: a NULL or unaligned pointer, channels outside 1..8, bits not 8, 16, 24
+ * or 32, a bad format or flag, a plane stride below `samples`.  It is a statement of the rule for
+ * callers and tests, bit for bit what the device writes; it is NOT a conversion path. */
+int flacgpu_pcm_from_elements_host(const void *src, uint64_t samples, uint64_t plane_stride, uint32_t channels,
+                                   uint32_t bits, uint32_t sample_format, uint32_t flags, uint8_t *pcm_out,
+                                   size_t cap, uint64_t *clipped);
+
 /* ---- Instrumentation ---------------------------------------------------- */
 /* Kernel ids for flacgpu_kernel_time: frame analysis (4096-sample frames /
  * short frames), frame-size scan, frame packing (all frames), stream MD5. */

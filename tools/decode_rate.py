@@ -78,6 +78,15 @@ ratio is claimed in advance.  The first frames of the first and last window are 
 flacgpu.features_f32_host bit for bit, and the interior frames of the two paths with each other.
 
     python tools/decode_rate.py --legs features --features-out profiles/decode_features_rate.json
+
+The write leg (--write-out; opt-in, not part of `all`) takes the resample leg's PCM as 64 float32
+[channel, time] tensors on the device and builds a bank of them at 16 bits two ways, alternated in one
+process: FlacBank.from_tensors, and the route a caller had before it -- the tensors scaled, rounded
+and cast by torch ops and moved to the host, Encoder.encode_files, FlacBank(files).  Wall clock with
+the device synchronised at both ends, one warm call each, the medians of --repeats.  The first and
+the last file of the two routes are compared byte for byte, and a crop of each with the tensor.
+
+    python tools/decode_rate.py --legs write --write-out profiles/bank_write_rate.json
 """
 import argparse
 import contextlib
@@ -877,6 +886,70 @@ def features_rate(n_files: int, frames_each: int, window: int, warmup: int, repe
     return res
 
 
+def write_rate(n_files: int, frames_each: int, repeats: int) -> dict:
+    import numpy as np
+    import torch
+
+    import flacbank
+    import flacgpu
+    import synth
+
+    ch, bits, rate, _ = PRESETS["c2"]
+    dev = torch.device("cuda", 0)
+    unit = synth.synth_pcm(64 * 4096, ch, bits, rate)
+    n_each = frames_each * 4096
+    pcm = (unit * ((frames_each + 63) // 64))[: n_each * ch * (bits // 8)]
+    ints = np.frombuffer(pcm, dtype=np.int16).reshape(n_each, ch)
+    x = torch.from_numpy(np.ascontiguousarray(ints.T).astype(np.float32) * np.float32(2.0 ** -(bits - 1))).to(dev)
+    tensors = [x.clone() for _ in range(n_files)]  # [C, T] float32 on the device: what a data set of tensors is
+    torch.cuda.synchronize(dev)
+
+    def from_tensors():
+        t = time.perf_counter()
+        b = flacbank.FlacBank.from_tensors(tensors, rate, bits=bits)
+        torch.cuda.synchronize(dev)
+        return time.perf_counter() - t, b
+
+    def host_detour():
+        """The route without from_tensors: scale, round and cast in torch, to the host, encode_files, FlacBank(files)."""
+        t = time.perf_counter()
+        top = float(1 << (bits - 1))
+        pcms = [(v * top).round().clamp(-top, top - 1).to(torch.int16).t().contiguous().cpu().numpy().tobytes() for v in tensors]
+        with flacgpu.Encoder(ch, bits, rate, device=0, max_frames=n_files * frames_each) as enc:
+            files = enc.encode_files(pcms)
+        b = flacbank.FlacBank(files)
+        torch.cuda.synchronize(dev)
+        return time.perf_counter() - t, b, files
+
+    _, a = from_tensors()  # one warm call each: the allocations, the library's first use
+    _, b, files = host_detour()
+    assert a.clipped == [0] * n_files and a.samples == b.samples == [n_each] * n_files
+    assert a.file_bytes(0) == files[0] and a.file_bytes(n_files - 1) == files[-1], "the two routes write different files"
+    (xa, _), (xb, _) = a.crops([0, n_files - 1], [1234, 99], 65536), b.crops([0, n_files - 1], [1234, 99], 65536)
+    assert torch.equal(xa, xb) and torch.equal(xa[0], x[:, 1234:1234 + 65536]), "a crop differs from the tensor it was built from"
+    flac_bytes = a.compressed_bytes
+    a.close()
+    b.close()
+    s_new, s_old = [], []
+    for _ in range(repeats):  # alternated
+        dt, a = from_tensors()
+        a.close()
+        s_new.append(dt)
+        dt, b, _ = host_detour()
+        b.close()
+        s_old.append(dt)
+    total = n_files * n_each
+    res = {"files": n_files, "frames_per_file": frames_each, "channels": ch, "bits": bits, "dtype": "float32",
+           "tensor_bytes": n_files * x.numel() * 4, "pcm_bytes": n_files * len(pcm), "flac_bytes": flac_bytes, "repeats": repeats,
+           "clock": "wall, the device synchronised at both ends; one warm call of each route before the timed ones",
+           "from_tensors": {"seconds_median": statistics.median(s_new), "seconds": s_new,
+                            "msamples_per_s": total / statistics.median(s_new) / 1e6},
+           "host_detour": {"seconds_median": statistics.median(s_old), "seconds": s_old,
+                           "msamples_per_s": total / statistics.median(s_old) / 1e6}}
+    res["from_tensors"]["x_host_detour"] = res["host_detour"]["seconds_median"] / res["from_tensors"]["seconds_median"]
+    return res
+
+
 def bigblock_rate(blocks, n_streams: int, warmup: int, repeats: int) -> dict:
     import numpy as np
     import torch
@@ -950,8 +1023,9 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix", "resample", "features"),
+    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix", "resample", "features", "write"),
                     default="all")
+    ap.add_argument("--write-out", default=os.path.join(ROOT, "profiles", "bank_write_rate.json"))
     ap.add_argument("--resample-out", default=os.path.join(ROOT, "profiles", "decode_resample_rate.json"))
     ap.add_argument("--features-out", default=os.path.join(ROOT, "profiles", "decode_features_rate.json"))
     ap.add_argument("--mix-out", default=os.path.join(ROOT, "profiles", "decode_mix_rate.json"))
@@ -970,6 +1044,13 @@ def main():
         print(json.dumps({"bigblock": br}), flush=True)
         with open(a.bigblock_out, "w") as f:
             json.dump(br, f, indent=1)
+            f.write("\n")
+        return
+    if a.legs == "write":  # opt-in: `all` leaves it out
+        wr = {"c2": write_rate(a.files, a.frames // a.files, a.repeats)}
+        print(json.dumps({"write": wr}), flush=True)
+        with open(a.write_out, "w") as f:
+            json.dump(wr, f, indent=1)
             f.write("\n")
         return
     if a.legs == "mix":  # opt-in: `all` leaves it out

@@ -23,6 +23,7 @@
 #include "fg_internal.hpp"
 #include "fg_layout.hpp"
 #include "fg_md5_host.hpp"
+#include "fg_quantize.hpp"
 
 namespace fg {
 hipError_t launch_stage(int stage, const EncodeArgs &a, bool full, uint32_t threads, uint32_t lds, hipStream_t st);
@@ -1348,6 +1349,77 @@ int flacgpu_streaminfo_replay_device(flacgpu_ctx *c, const uint32_t *d_frame_byt
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = pick_stream(c, hip_stream);
     HIPCHK(launch_streaminfo_replay(d_frame_bytes, n_frames, d_minmax, st));
+    return FLACGPU_OK;
+}
+
+// ---- tensor elements to the encoder's PCM (fg_quantize.hpp) -------------------
+namespace {
+
+// a stream's PCM bytes rounded up to whole words, or false where T * C * B passes 2^62
+bool quant_span(uint64_t samples, uint32_t C, uint32_t B, uint64_t &span) {
+    if (samples > (1ull << 62) / ((uint64_t)C * B)) return false;
+    span = quantize::pcm_words(samples * C, B) * 4u;
+    return true;
+}
+
+}  // namespace
+
+int flacgpu_pcm_from_elements_device(flacgpu_ctx *c, uint32_t n_streams, const void *const *d_src, const uint64_t *samples,
+                                     const uint64_t *plane_stride, uint32_t sample_format, uint32_t flags, uint8_t *d_pcm,
+                                     const uint64_t *pcm_offsets, uint64_t pcm_cap, uint64_t *d_clipped, void *hip_stream) {
+    if (!c || !c->enc) return FLACGPU_ERR_INVALID_INPUT;  // a decode-only context has no PCM to encode
+    if (n_streams > quantize::kMaxStreams || sample_format >= quantize::SAMPLE_FORMATS || (flags & ~(uint32_t)FLACGPU_DELIVER_PLANAR))
+        return FLACGPU_ERR_INVALID_INPUT;
+    if (!n_streams) return FLACGPU_OK;
+    if (!d_src || !samples || !d_pcm || !pcm_offsets || !d_clipped) return FLACGPU_ERR_INVALID_INPUT;
+    EncState &e = *c->enc;
+    const uint32_t C = e.g.C, B = e.g.B;
+    const bool planar = (flags & FLACGPU_DELIVER_PLANAR) != 0;
+    std::vector<quantize::Stream> tab;
+    try {
+        tab.resize(n_streams);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    uint64_t max_units = 0;
+    for (uint32_t s = 0; s < n_streams; s++) {
+        uint64_t span;
+        const uint64_t stride = plane_stride ? plane_stride[s] : samples[s];
+        if (!d_src[s] || (pcm_offsets[s] & 3u) || !quant_span(samples[s], C, B, span)) return FLACGPU_ERR_INVALID_INPUT;
+        if (planar && stride < samples[s]) return FLACGPU_ERR_INVALID_INPUT;
+        if (pcm_offsets[s] > pcm_cap || span > pcm_cap - pcm_offsets[s]) return FLACGPU_ERR_INVALID_INPUT;
+        if (s + 1u < n_streams && (pcm_offsets[s + 1u] < pcm_offsets[s] || span > pcm_offsets[s + 1u] - pcm_offsets[s]))
+            return FLACGPU_ERR_INVALID_INPUT;  // a stream runs into the next one
+        tab[s] = {d_src[s], samples[s], stride, pcm_offsets[s]};
+        max_units = std::max(max_units, quantize::units(samples[s] * C));
+    }
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = pick_stream(c, hip_stream);
+    const uint64_t bytes = (uint64_t)n_streams * sizeof(quantize::Stream);
+    HIPCHK(e.d_quant.grow(bytes, &st));  // an earlier call on this stream may still read the old table
+    HIPCHK(hipMemcpyAsync(e.d_quant.get(), tab.data(), bytes, hipMemcpyHostToDevice, st));
+    HIPCHK(launch_elements_pcm((const quantize::Stream *)e.d_quant.get(), n_streams, max_units, d_pcm, d_clipped, C, B,
+                               sample_format, planar, st));
+    return FLACGPU_OK;
+}
+
+int flacgpu_pcm_from_elements_host(const void *src, uint64_t samples, uint64_t plane_stride, uint32_t channels, uint32_t bits,
+                                   uint32_t sample_format, uint32_t flags, uint8_t *pcm_out, size_t cap, uint64_t *clipped) {
+    if (!src || !pcm_out || !clipped || ((uintptr_t)pcm_out & 3u)) return FLACGPU_ERR_INVALID_INPUT;
+    if (channels < 1u || channels > 8u || (bits != 8u && bits != 16u && bits != 24u && bits != 32u)) return FLACGPU_ERR_INVALID_INPUT;
+    if (sample_format >= quantize::SAMPLE_FORMATS || (flags & ~(uint32_t)FLACGPU_DELIVER_PLANAR)) return FLACGPU_ERR_INVALID_INPUT;
+    const bool planar = (flags & FLACGPU_DELIVER_PLANAR) != 0;
+    const uint32_t B = bits / 8u;
+    uint64_t span;
+    if ((planar && plane_stride < samples) || !quant_span(samples, channels, B, span)) return FLACGPU_ERR_INVALID_INPUT;
+    *clipped = 0;
+    if (span > cap) return FLACGPU_ERR_OUTPUT_TOO_SMALL;
+    const quantize::Stream st{src, samples, plane_stride, 0};
+    const uint64_t n = samples * channels, nu = quantize::units(n);
+    uint64_t count = 0;
+    for (uint64_t u = 0; u < nu; u++)
+        count += quantize::convert_unit<uint64_t>(st, (uint32_t *)pcm_out, u, n, channels, B, sample_format, planar);
+    *clipped = count;
     return FLACGPU_OK;
 }
 

@@ -86,6 +86,9 @@ struct FG_LOCAL EncState {
     uint8_t md5_buf[64] = {};
     uint32_t md5_fill = 0;
     uint64_t md5_len = 0;
+
+    // ---- elements to PCM (flacgpu_pcm_from_elements_device): the stream table of a call, grow-only ----
+    DevBuf<uint8_t> d_quant;
 };
 
 // Decode scratch of a context (allocated by its first decode call, max_frames frames), one
@@ -218,6 +221,9 @@ struct Ratio;
 namespace feat {
 struct Params;
 }
+namespace quantize {
+struct Stream;
+}
 struct FeatWindow;
 
 // fg_api.cpp: an event of the context's pool, or a new one (empty: none could be created)
@@ -278,6 +284,9 @@ hipError_t launch_features(const FeatWindow *wins, const window::WindowResult *s
                            const resample::Ratio &rt, const float *x, const float *table, const float *filters, uint8_t *out,
                            window::WindowResult *results, const feat::Params &ft, uint32_t K, uint32_t format, uint32_t n,
                            uint64_t max_items, hipStream_t st);
+// fg_quantize.hip: k_elements_pcm<B> over a device table of n_streams quantize::Stream rows
+hipError_t launch_elements_pcm(const quantize::Stream *d_tab, uint32_t n_streams, uint64_t max_units, uint8_t *d_pcm,
+                               uint64_t *d_clipped, uint32_t C, uint32_t B, uint32_t format, bool planar, hipStream_t st);
 // fg_misc.hip
 hipError_t launch_md5_streams(const uint8_t *base, const uint64_t *offs, const uint64_t *lens, const uint8_t *fin,
                               uint32_t n, Md5State *states, uint8_t *digests, hipStream_t st, int kernel, int prio);

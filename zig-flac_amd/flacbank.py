@@ -7,13 +7,16 @@ scanned once (flacgpu_flac_index_streams_device, flacgpu_flac_positions_streams_
 (flacgpu_decode_windows_device_as), on the caller's current torch stream.  Plumbing over the C ABI:
 there is no CPU path.  A bank takes no locks: one bank per thread, like a context.  With a `rate`
 the crops are stated and delivered at that sample rate: those of files at another rate go through
-flacgpu_decode_windows_device_resample, one call per source rate.
+flacgpu_decode_windows_device_resample, one call per source rate.  FlacBank.from_tensors builds the
+same bank from tensors on the device (flacgpu_pcm_from_elements_device, flacgpu_encode_plan_device);
+file_bytes writes a bank's file back out as a .flac.
 
 FlacBank holds files of one channel count and depth.  FlacMixBank holds any, as one FlacBank per
 (channels, bits), and delivers every crop with the bank's one channel count through
 flacgpu_decode_windows_device_mix."""
 from __future__ import annotations
 
+import ctypes
 from typing import Optional, Sequence
 
 import flacgpu
@@ -254,10 +257,6 @@ class FlacBank:
             infos.append(si)
             bare.append(frames)
         self._dec = None
-        self.channels, self.bits = int(infos[0].channels), int(infos[0].bit_depth)
-        self.sample_rates = [int(si.sample_rate) for si in infos]
-        self.compressed_bytes = sum(len(b) for b in bare)
-        stated = [int(si.interchannel_samples) for si in infos]
         # the context decodes the largest block any file states
         for i, si in enumerate(infos):
             _check_blocks(who, names[i], si)
@@ -266,31 +265,50 @@ class FlacBank:
         import numpy as np
         import torch
 
-        self.device = torch.device("cuda", device)
-        block = max([int(si.max_block_size) for si in infos] + [16])
-        self._dec = flacgpu.Decoder(self.channels, self.bits, self.sample_rates[0], device=device, max_frames=max_frames,
-                                    block_size=block)
-        n = len(files)
         offs, at = [], 0
         for b in bare:  # stream offsets need no alignment
             offs.append(at)
             at += len(b)
         blob = np.frombuffer(b"".join(bare) + bytes(16), dtype=np.uint8)
-        self._caps = [len(b) // 8 + 1 for b in bare]  # a frame is at least 9 bytes
+        self.clipped = None  # elements clipped per file: of a bank built from tensors only
+        self._heads = [bytes(f[:len(f) - len(b)]) for f, b in zip(files, bare)]  # the metadata, as given
+        self._index(who, names, torch.from_numpy(blob.copy()), offs, [len(b) for b in bare], infos, device, max_frames)
+
+    def _index(self, who, names, data, offs, lens, infos, device, max_frames) -> None:
+        """What a bank is once its frames are in HBM, however they got there: data, a uint8 tensor
+        that holds stream i's bare frames at [offs[i], offs[i] + lens[i]) and 16 zero bytes after the
+        last -- on the device, or on the host and uploaded here once the context is open; infos, their
+        STREAMINFOs.  Opens the decode context, indexes the streams on the device (every frame's CRCs
+        are checked there), scans their sample positions and checks the totals against what the
+        STREAMINFOs state."""
+        import torch
+
+        self._dec = None
+        self.channels, self.bits = int(infos[0].channels), int(infos[0].bit_depth)
+        self.sample_rates = [int(si.sample_rate) for si in infos]
+        self.compressed_bytes = sum(lens)
+        stated = [int(si.interchannel_samples) for si in infos]
+        self._infos, self._offs, self._lens = list(infos), list(offs), list(lens)
+        self.device = torch.device("cuda", device)
+        block = max([int(si.max_block_size) for si in infos] + [16])
+        self._dec = flacgpu.Decoder(self.channels, self.bits, self.sample_rates[0], device=device, max_frames=max_frames,
+                                    block_size=block)
+        n = len(infos)
+        self._caps = [b // 8 + 1 for b in lens]  # a frame is at least 9 bytes
         self._first, entries = [], 0
         for c in self._caps:
             self._first.append(entries)
             entries += c
         with torch.cuda.device(self.device):
             st = torch.cuda.current_stream(self.device).cuda_stream
-            self._data = torch.from_numpy(blob.copy()).to(self.device)
+            self._data = data.to(self.device)
             self._off = torch.zeros(entries, dtype=torch.int64, device=self.device)
             self._fbytes = torch.zeros(entries, dtype=torch.int32, device=self.device)
             self._ires = torch.zeros(16 * n, dtype=torch.uint8, device=self.device)
             self._pos = torch.zeros(entries, dtype=torch.int64, device=self.device)
             self._totals = torch.zeros(n, dtype=torch.int64, device=self.device)
             bits = [self.bits] * n
-            self._dec.flac_index_streams_device(self._data.data_ptr(), offs, [len(b) for b in bare], self._first, self._caps,
+            self._dec.flac_index_streams_device(self._data.data_ptr(), offs, lens, self._first, self._caps,
                                                 self._off.data_ptr(), self._fbytes.data_ptr(), self._ires.data_ptr(),
                                                 stream_bits=bits, stream_rates=self.sample_rates, stream=st)
             self._dec.flac_positions_streams_device(self._data.data_ptr(), self._first, self._caps, self._off.data_ptr(),
@@ -307,6 +325,168 @@ class FlacBank:
             if stated[i] and self.samples[i] != stated[i]:
                 self.close()
                 raise ValueError(f"{who}: file {names[i]} holds {self.samples[i]} samples, its STREAMINFO states {stated[i]}")
+
+    @classmethod
+    def from_tensors(cls, tensors, sample_rate, bits: int = 16, device: int = 0, block_size: int = 4096,
+                     prediction: int = 0, planar: bool = True, max_frames: int = 4096, scratch_bytes: int = 1 << 30):
+        """A bank of the audio in `tensors`, compressed on the device: a sequence of [C, T_i] tensors
+        ([T_i, C] with planar=False) or one [N, C, T] ([N, T, C]) tensor, of one channel count (1..8)
+        and one dtype out of float32, float16, bfloat16 (a sample is the element times 2^(bits-1),
+        rounded to nearest-even and clamped: the inverse of `crops`) and int32 (the sample itself,
+        clamped); tensors on the CPU are moved to the device.  sample_rate: an int, or one per tensor.
+        bits (8, 16, 24, 32), block_size (16..4096) and prediction (0: fixed predictors, 1..12: LPC up
+        to that order) are the encoder's.  The tensors are taken in groups whose PCM and frame bound
+        fit scratch_bytes (a larger tensor is a group alone): each group is quantised
+        (flacgpu_pcm_from_elements_device) and encoded with its MD5 (flacgpu_encode_plan_device) on
+        torch.cuda.current_stream(device), the call waits once per group, and only the group's frames
+        are kept.  The result is an ordinary FlacBank, indexed on the device as one built from files
+        is; `clipped` holds the elements per tensor that the clamp changed or that were NaN.  What
+        is wrong with the arguments raises ValueError before any device use."""
+        import torch
+
+        who = "FlacBank.from_tensors"
+        if isinstance(tensors, torch.Tensor):
+            if tensors.dim() != 3:
+                raise ValueError(f"{who}: one tensor holds [N, C, T] (or [N, T, C]), not {tensors.dim()} dimensions")
+            tensors = tensors.unbind(0)
+        tensors = list(tensors)
+        n = len(tensors)
+        if n == 0:
+            raise ValueError(f"{who}: no tensors")
+        if n > 65535:
+            raise ValueError(f"{who}: more than 65535 tensors")
+        bits, block_size, prediction, scratch_bytes = int(bits), int(block_size), int(prediction), int(scratch_bytes)
+        if bits not in (8, 16, 24, 32):
+            raise ValueError(f"{who}: bits is {bits}, not 8, 16, 24 or 32")
+        if not 16 <= block_size <= 4096:
+            raise ValueError(f"{who}: block_size is {block_size}, not in 16..4096")
+        if not 0 <= prediction <= 12:
+            raise ValueError(f"{who}: prediction is {prediction}, not in 0..12")
+        rates = [int(r) for r in sample_rate] if isinstance(sample_rate, (list, tuple)) else [int(sample_rate)] * n
+        if len(rates) != n or any(not 0 < r < (1 << 20) for r in rates):
+            raise ValueError(f"{who}: sample_rate is one rate in 1..2^20-1, or one for each of the {n} tensors")
+        fmt, C, Ts = None, None, []
+        for i, x in enumerate(tensors):
+            if not isinstance(x, torch.Tensor) or x.dim() != 2:
+                raise ValueError(f"{who}: tensor {i} is not a tensor of two dimensions")
+            c, t = (x.shape[0], x.shape[1]) if planar else (x.shape[1], x.shape[0])
+            f = _formats().get(x.dtype)
+            if f is None:
+                raise ValueError(f"{who}: tensor {i} has dtype {x.dtype}, none of float32, float16, bfloat16, int32")
+            if i == 0:
+                fmt, C = f, int(c)
+                if not 1 <= C <= 8:
+                    raise ValueError(f"{who}: tensor 0 has {C} channels, not 1 to 8")
+            elif int(c) != C or f != fmt:
+                raise ValueError(f"{who}: tensor {i} has {int(c)} channels of {x.dtype}, tensor 0 has {C} of "
+                                 f"{tensors[0].dtype}: one bank holds one channel count and one dtype")
+            if int(t) == 0:
+                raise ValueError(f"{who}: tensor {i} holds no samples")
+            Ts.append(int(t))
+        B = bits // 8
+        # the bytes a tensor needs in a group: its PCM and its frames' share of the plan's output bound
+        cfg = flacgpu.Config(rates[0], block_size, C, bits, 1, 8, 30, prediction)
+        image = (flacgpu.load_library().flacgpu_frame_bound_bytes(ctypes.byref(cfg)) + 16 + 15) // 16 * 16
+        pcm_len = [(T * C * B + 3) // 4 * 4 for T in Ts]
+        need = [p + (T + block_size - 1) // block_size * image for p, T in zip(pcm_len, Ts)]
+        groups, used = [[]], 0
+        for i in range(n):
+            if groups[-1] and used + need[i] > scratch_bytes:
+                groups.append([])
+                used = 0
+            groups[-1].append(i)
+            used += need[i]
+
+        # ---- everything below needs the device
+        dev = torch.device("cuda", device)
+        encoders: dict = {}  # rate -> Encoder: the rate is in every frame header
+        kept, offs, lens, infos, clipped = [], [0] * n, [0] * n, [None] * n, [0] * n
+        at = 0
+        try:
+            for rate in dict.fromkeys(rates):
+                encoders[rate] = flacgpu.Encoder(C, bits, rate, device=device, max_frames=max_frames, block_size=block_size,
+                                                 lpc_order=prediction)
+            with torch.cuda.device(dev):
+                st = torch.cuda.current_stream(dev).cuda_stream
+                for group in groups:
+                    by_rate: dict = {}
+                    for i in group:
+                        by_rate.setdefault(rates[i], []).append(i)
+                    for rate, idx in by_rate.items():  # one quantise and one encode per rate of the group
+                        enc = encoders[rate]
+                        src = []
+                        for i in idx:
+                            x = tensors[i].to(dev)
+                            ok = x.is_contiguous() or (planar and x.stride(1) == 1 and (C == 1 or x.stride(0) >= Ts[i]))
+                            src.append(x if ok else x.contiguous())
+                        strides = [x.stride(0) if planar and C > 1 else Ts[i] for x, i in zip(src, idx)]
+                        p_off, total_pcm = [], 0
+                        for i in idx:
+                            p_off.append(total_pcm)
+                            total_pcm += pcm_len[i]
+                        d_pcm = torch.empty(total_pcm, dtype=torch.uint8, device=dev)
+                        d_clip = torch.empty(len(idx), dtype=torch.int64, device=dev)
+                        enc.pcm_from_elements_device([x.data_ptr() for x in src], [Ts[i] for i in idx], strides, fmt,
+                                                     flacgpu.DELIVER_PLANAR if planar else 0, d_pcm.data_ptr(), p_off,
+                                                     total_pcm, d_clip.data_ptr(), stream=st)
+                        plan = enc.plan(p_off, [Ts[i] for i in idx])
+                        try:
+                            nf, bound = int(plan.n_frames), int(plan.out_bound)
+                            d_out = torch.empty(bound, dtype=torch.uint8, device=dev)
+                            d_fb = torch.empty(nf, dtype=torch.int32, device=dev)
+                            d_fo = torch.empty(nf + 1, dtype=torch.int64, device=dev)  # the last entry: the total
+                            d_md5 = torch.empty(16 * len(idx), dtype=torch.uint8, device=dev)
+                            enc.encode_plan_device(plan, d_pcm.data_ptr(), d_out.data_ptr(), bound, d_fb.data_ptr(),
+                                                   d_fo.data_ptr(), d_fo.data_ptr() + 8 * nf, d_md5=d_md5.data_ptr(), stream=st)
+                            firsts = [int(f) for f in plan.first_frame] + [nf]
+                            d_cut = d_fo[torch.tensor(firsts, dtype=torch.int64).to(dev, non_blocking=True)]
+                            enc.sync_check(st)  # the one wait of the group (one per rate in it)
+                            cut = [int(v) for v in d_cut.cpu().tolist()]  # where every stream's bytes begin, and the total
+                        finally:
+                            plan.close()
+                        md5 = d_md5.cpu().numpy().tobytes()
+                        clip = d_clip.cpu().tolist()
+                        kept.append(d_out[:cut[-1]].clone())  # the compact frames: the bound's slack goes with d_out
+                        for j, i in enumerate(idx):
+                            offs[i], lens[i], clipped[i] = at + cut[j], cut[j + 1] - cut[j], int(clip[j])
+                            si = flacgpu.StreamInfo.new(rate, C, bits, Ts[i], block_size)
+                            ctypes.memmove(si.md5, md5[16 * j:16 * j + 16], 16)
+                            infos[i] = si
+                        at += cut[-1]
+                        del d_pcm, d_out, d_fb, d_fo, d_md5, d_clip, src
+                data = torch.cat(kept + [torch.zeros(16, dtype=torch.uint8, device=dev)])
+        finally:
+            for enc in encoders.values():
+                enc.close()
+        del kept
+        bank = cls.__new__(cls)
+        bank.clipped, bank._heads = clipped, None
+        bank._index("FlacBank.from_tensors", range(n), data, offs, lens, infos, device, max_frames)
+        return bank
+
+    def file_bytes(self, i: int) -> bytes:
+        """File i as a valid .flac: of a bank built from files the metadata it was given, up to the
+        first frame, then the frames as the bank holds them; of one built from tensors the 73-byte
+        header flacgpu_encode_file writes (STREAMINFO with the block size, the samples, the MD5 of
+        the PCM and the frame sizes replayed through flacgpu_streaminfo_update_frame_size; the vendor
+        comment), then the frames.  Copies the file's frames to the host: not a hot path."""
+        if self._dec is None:
+            raise ValueError("FlacBank: closed")
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise ValueError(f"FlacBank.file_bytes: file {i} is not in 0..{len(self) - 1}")
+        frames = self._data[self._offs[i]:self._offs[i] + self._lens[i]].cpu().numpy().tobytes()
+        if self._heads is not None:
+            return self._heads[i] + frames
+        src = self._infos[i]
+        si = flacgpu.StreamInfo.new(int(src.sample_rate), self.channels, self.bits, int(src.interchannel_samples),
+                                    int(src.max_block_size))
+        ctypes.memmove(si.md5, src.md5, 16)
+        first = self._first[i]
+        n_frames = flacgpu.IndexResult.from_buffer_copy(self._ires[16 * i:16 * i + 16].cpu().numpy().tobytes()).n_frames
+        for size in self._fbytes[first:first + n_frames].cpu().tolist():
+            si.update_frame_size(int(size))
+        return flacgpu.header_bytes(si, False) + flacgpu.vorbis_comment_bytes(True) + frames
 
     def close(self) -> None:
         if getattr(self, "_dec", None) is not None:

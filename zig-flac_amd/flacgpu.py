@@ -374,6 +374,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_features_f32_host": (I32, [P, U64, P, P, U64, U64, P, ctypes.POINTER(U64)]),
         "flacgpu_decode_windows_device_features": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, U32, P, U32, U32,
                                                          P, P, P, P, P, P, P]),
+        "flacgpu_pcm_from_elements_device": (I32, [P, U32, P, P, P, U32, U32, P, P, U64, P, P]),
+        "flacgpu_pcm_from_elements_host": (I32, [P, U64, U64, U32, U32, U32, U32, P, SZ, ctypes.POINTER(U64)]),
     }
     # an older build named by FLACGPU_LIB (same-box A/B runs, tools/ab.sh) may predate later entry
     # points: those stay unbound there; the in-tree library must export every one
@@ -414,6 +416,7 @@ def exported_symbols() -> list:
         "flacgpu_decode_windows_device_as", "flacgpu_open_decoder", "flacgpu_decode_windows_device_mix",
         "flacgpu_resample_filter", "flacgpu_resample_f32_host", "flacgpu_decode_windows_device_resample",
         "flacgpu_features_table", "flacgpu_features_f32_host", "flacgpu_decode_windows_device_features",
+        "flacgpu_pcm_from_elements_device", "flacgpu_pcm_from_elements_host",
     ]
 
 
@@ -667,6 +670,35 @@ def features_f32_host(x, n_fft: int, hop: int, start: int, frames: int, filters=
                                                     y.ctypes.data if frames else None, ctypes.byref(got)),
            "features_f32_host")
     return y, got.value
+
+
+def pcm_from_elements_host(x, bits: int, sample_format: int, planar: bool = True, samples: Optional[int] = None,
+                           plane_stride: Optional[int] = None):
+    """flacgpu_pcm_from_elements_host (host only): (PCM bytes rounded up to 4 with zero pads, clipped)
+    of one stream whose elements are the numpy array x: [C, T] with planar (plane_stride elements
+    between planes: default the row stride of x), else [T, C]; float16 and bfloat16 as uint16 bit
+    patterns, float32 as float32 or uint32, int32 as int32.  The statement of the rule the device
+    follows bit for bit: not a conversion path."""
+    import numpy as np
+
+    x = np.asarray(x)
+    if x.ndim != 2 or x.dtype.itemsize != ELEMENT_BYTES.get(sample_format, 0):
+        raise ValueError("pcm_from_elements_host: x is [C, T] or [T, C] elements of the format's size")
+    C, T = (x.shape[0], x.shape[1]) if planar else (x.shape[1], x.shape[0])
+    if samples is not None:
+        T = samples
+    if planar and plane_stride is None:
+        x = np.ascontiguousarray(x)
+        plane_stride = x.shape[1]
+    elif not planar:
+        x = np.ascontiguousarray(x)
+    cap = (T * C * (bits // 8) + 3) // 4 * 4
+    out = np.zeros(max(cap, 4) // 4, dtype=np.uint32)
+    clipped = ctypes.c_uint64(0)
+    _check(load_library().flacgpu_pcm_from_elements_host(x.ctypes.data, T, plane_stride or 0, C, bits, sample_format,
+                                                         DELIVER_PLANAR if planar else 0, out.ctypes.data, cap,
+                                                         ctypes.byref(clipped)), "pcm_from_elements_host")
+    return out.tobytes()[:cap], clipped.value
 
 
 class _DecodeOps:
@@ -1059,6 +1091,18 @@ class Encoder(_DecodeOps):
         _check(self.lib.flacgpu_encode_plan_device_ex(
             self.ctx, plan.handle, d_pcm, d_out, out_cap, d_frame_bytes, d_frame_offsets, d_total,
             d_md5_state or None, d_md5 or None, _stream(stream), _stream(md5_stream)), "encode_plan_device_ex")
+
+    def pcm_from_elements_device(self, d_src: Sequence[int], samples: Sequence[int], plane_stride: Optional[Sequence[int]],
+                                 sample_format: int, flags: int, d_pcm: int, pcm_offsets: Sequence[int], pcm_cap: int,
+                                 d_clipped: int, stream: Optional[int] = None) -> None:
+        """flacgpu_pcm_from_elements_device: len(d_src) streams of elements (device addresses) to the
+        interleaved PCM of this encoder's channels and depth at d_pcm + pcm_offsets[s]; d_clipped: a
+        uint64 per stream in device memory.  Nothing synchronised."""
+        n = len(d_src)
+        _check(self.lib.flacgpu_pcm_from_elements_device(
+            self.ctx, n, (ctypes.c_void_p * max(n, 1))(*d_src), _u64s(samples),
+            _u64s(plane_stride) if plane_stride is not None else None, sample_format, flags, d_pcm, _u64s(pcm_offsets),
+            pcm_cap, d_clipped, _stream(stream)), "pcm_from_elements_device")
 
     def sync_check(self, stream: Optional[int] = None) -> None:
         """Synchronise `stream` and raise if a kernel flagged a device-side error."""
