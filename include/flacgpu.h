@@ -797,6 +797,65 @@ int flacgpu_decode_windows_device_features(flacgpu_ctx *ctx, const uint8_t *d_da
                                            const flacgpu_features *ft, const float *filters,
                                            void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
                                            flacgpu_window_result *d_results, void *hip_stream);
+/* The channel mix by a weight matrix.  A source sample has the context's C channels; x_c is the
+ * FLACGPU_SAMPLE_F32 element of channel c exactly as flacgpu_decode_windows_device_as delivers it.  W
+ * is a row-major K x C float matrix (HOST memory).  Output channel k is y = +0.0f, then for
+ * c = 0 .. C - 1 in this order y = fmaf(W[k][c], x_c, y): one accumulator, one correctly rounded
+ * fused multiply-add a source channel, as in the resampler and the features.  FLACGPU_SAMPLE_F32 is
+ * y; F16 and BF16 are y rounded to nearest-even as every other element is (|y| can reach 2^35: F16
+ * is infinity from 65520 on, BF16 keeps the range); FLACGPU_SAMPLE_I32 is not offered.  A matrix is
+ * valid when C and K are 1 to 8, the format is F32, F16 or BF16 and every weight is 0 (of either
+ * sign) or has 2^-32 <= |w| <= 2^32 -- NaN, infinities and subnormals are refused.  The bounds are
+ * derived: |x_c| is 0 or lies in [2^-31, 1], so every product is 0 or a normal number, a multiple
+ * of 2^-86 and at most 2^32; no fused multiply-add underflows or overflows (|y| <= 2^35); an exact
+ * cancellation gives +0.0f, so no accumulator is ever -0.0f or subnormal; and passing over zero
+ * weights, and over channels whose x_c is 0, changes no bit (the library does not read a channel
+ * whose weight is 0).  A mean of three is {1/3, 1/3, 1/3}, mid/side {0.5, 0.5}, {0.5, -0.5}.
+ * flacgpu_mix_weights_valid (host only): 1 where `weights` (out_channels x channels) is valid for
+ * sample_format, else 0.  flacgpu_mix_weights_f32_host (host only): the rule over n samples of
+ * `channels` channels, samples[n][channels] sign-extended samples of `bits` (8, 16, 24, 32) bits,
+ * y[n][out_channels]; FLACGPU_ERR_INVALID_INPUT for an invalid matrix, depth or a sample outside the
+ * depth, n <= 2^40.  It is a statement of the rule for callers and tests, bit for bit what the
+ * device delivers; it is NOT a decode path. */
+int flacgpu_mix_weights_valid(uint32_t channels, uint32_t out_channels, const float *weights, uint32_t sample_format);
+int flacgpu_mix_weights_f32_host(const int32_t *samples, uint64_t n, uint32_t channels, uint32_t bits,
+                                 uint32_t out_channels, const float *weights, float *y);
+/* Every delivery above through one call that takes the delivery as a struct: the signature that
+ * further kinds of delivery extend by fields, not by arguments.  With channel_weights NULL the call
+ * IS the existing one the struct describes -- features != NULL: _features (window_count holds the
+ * frame counts, flags must be 0); else src_rate or dst_rate != 0: _resample; else channel_masks !=
+ * NULL: _mix; else _as -- with the same checks, bytes and results.  With channel_weights each of
+ * those four deliveries has K = out_channels channels made by the weighted rule above in place of
+ * the mask rule: the elements of _as / _mix; the planes x[i] the filter of _resample runs over;
+ * the channels the frames of _features are taken from (through the resampler first where the rates
+ * differ).  Layout, padding, capacity, statuses and results are those of the call it stands for
+ * with K channels.  FLACGPU_ERR_INVALID_INPUT before any device work: a NULL `how`, a size other
+ * than sizeof(flacgpu_window_delivery), both channel_masks and channel_weights, a matrix that
+ * flacgpu_mix_weights_valid refuses for the context's C (FLACGPU_SAMPLE_I32 with weights included),
+ * flags with features, and every argument error of the call it stands for.  The matrix lives in
+ * device memory the context owns, found again by its content (the context keeps the last 16),
+ * uploaded by the first call that needs it -- that call waits for hip_stream once more -- and freed
+ * by flacgpu_close. */
+typedef struct {
+    uint32_t size;                  /* sizeof(flacgpu_window_delivery) */
+    uint32_t sample_format, flags;  /* as flacgpu_decode_windows_device_as */
+    uint32_t out_channels;          /* K, with masks or weights */
+    const uint8_t *channel_masks;   /* host, K entries, or NULL */
+    const float *channel_weights;   /* host, K * C floats row-major, or NULL; not both */
+    uint32_t src_rate, dst_rate;    /* 0, 0: no rate change; else the rules of _resample */
+    const flacgpu_features *features; /* NULL: samples; else the rules of _features */
+    const float *filters;
+} flacgpu_window_delivery;
+int flacgpu_decode_windows_device_to(flacgpu_ctx *ctx, const uint8_t *d_data,
+                                     uint32_t n_streams, const uint64_t *table_first,
+                                     const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                     const flacgpu_index_result *d_index_results,
+                                     const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
+                                     uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
+                                     const uint64_t *window_count,
+                                     const flacgpu_window_delivery *how,
+                                     void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
+                                     flacgpu_window_result *d_results, void *hip_stream);
 /* Windows of whole files in host memory: window w is samples [window_start[w], + window_count[w])
  * of file window_file[w] (< n_files), delivered to pcm_out[w] (capacity pcm_cap[w]) with
  * n_samples[w].  Metadata is parsed on the host as in flacgpu_decode_files; the good files' frames

@@ -87,6 +87,17 @@ the device synchronised at both ends, one warm call each, the medians of --repea
 the last file of the two routes are compared byte for byte, and a crop of each with the tensor.
 
     python tools/decode_rate.py --legs write --write-out profiles/bank_write_rate.json
+
+The downmix leg (--downmix-out; opt-in, not part of `all`) takes 6-channel 16-bit files of the same
+sizes and windows and delivers them as stereo f32, planar and padded, two ways, alternated in one
+process: flacgpu_decode_windows_device_to with the ITU 6-to-2 weight matrix, and the route a caller
+had before it -- flacgpu_decode_windows_device_as of all six channels followed by torch.einsum with
+the same matrix.  Wall clock with the device synchronised at both ends, one warm call each, the
+medians of --repeats.  The first and the last window are compared with flacgpu.mix_weights_f32_host
+over the PCM bit for bit; the two tensors are compared with each other (they may differ in the last
+place: einsum need not be the one chain of fused multiply-adds).  No ratio is claimed in advance.
+
+    python tools/decode_rate.py --legs downmix --downmix-out profiles/decode_downmix_rate.json
 """
 import argparse
 import contextlib
@@ -419,8 +430,9 @@ def files_rate(n_files: int, frames_each: int, warmup: int, repeats: int) -> dic
 
 
 @contextlib.contextmanager
-def resident_windows(n_files: int, frames_each: int, window: int):
-    """The resident set of the windows, deliver and mix legs: n_files C2 files of frames_each frames
+def resident_windows(n_files: int, frames_each: int, window: int, channels: int = 0):
+    """The resident set of the windows, deliver and mix legs: n_files C2 files (`channels`: of that
+    many channels instead of two) of frames_each frames
     encoded on the GPU, their frames in one HBM buffer at 64-byte offsets and indexed once, and one
     window of `window` samples per file from a start that is no multiple of the block size.  The
     positions are the caller's to queue (r.positions()): the windows leg times them."""
@@ -433,6 +445,7 @@ def resident_windows(n_files: int, frames_each: int, window: int):
     import synth
 
     ch, bits, rate, _ = PRESETS["c2"]
+    ch = channels or ch
     per = ch * (bits // 8)
     dev = torch.device("cuda", 0)
     unit = synth.synth_pcm(64 * 4096, ch, bits, rate)
@@ -755,6 +768,68 @@ def mix_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: 
     return res
 
 
+def downmix_rate(n_files: int, frames_each: int, window: int, repeats: int) -> dict:
+    import numpy as np
+    import torch
+
+    import flacbank
+    import flacgpu
+
+    W = flacbank.downmix_matrix(6, 2, "itu")
+    with resident_windows(n_files, frames_each, window, channels=6) as r:
+        enc, ch, bits, per, dev, pcm, n_each, st, crops = r.enc, r.ch, r.bits, r.per, r.dev, r.pcm, r.n_each, r.st, r.crops
+        tables, d_wres, start = r.tables, r.d_wres, r.start
+        r.positions()
+        planar_pad = flacgpu.DELIVER_PLANAR | flacgpu.DELIVER_PAD
+        x_to = torch.zeros((n_files, 2, window), dtype=torch.float32, device=dev)
+        x_as = torch.zeros((n_files, ch, window), dtype=torch.float32, device=dev)
+        d_w = torch.from_numpy(W).to(dev)
+
+        def to():
+            enc.decode_windows_device_to(*tables, crops, flacgpu.SAMPLE_F32, planar_pad, x_to.data_ptr(),
+                                         [i * 2 * window for i in range(n_files)], [2 * window] * n_files, d_wres.data_ptr(),
+                                         channel_weights=W, stream=st)
+            return x_to
+
+        def as_then_einsum():
+            enc.decode_windows_device_as(*tables, crops, flacgpu.SAMPLE_F32, planar_pad, x_as.data_ptr(),
+                                         [i * ch * window for i in range(n_files)], [ch * window] * n_files, d_wres.data_ptr(),
+                                         stream=st)
+            return torch.einsum("kc,nct->nkt", d_w, x_as)
+
+        def wall_ms(fn):
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            return (time.perf_counter() - t0) * 1e3
+
+        legs = {"to_itu_f32": to, "as_f32_then_einsum": as_then_einsum}
+        for fn in legs.values():  # one warm call each
+            fn()
+            enc.sync_check(st)
+            assert r.results() == [(0, window)] * n_files
+        # the expectation from the PCM: the host statement of the rule
+        v = np.frombuffer(pcm, dtype=np.int16).reshape(n_each, ch)[start:start + window]
+        want = torch.from_numpy(np.ascontiguousarray(flacgpu.mix_weights_f32_host(v, bits, W).T))
+        got = to().cpu()
+        assert torch.equal(got[0], want) and torch.equal(got[-1], want), "the downmix differs from the host statement of the rule"
+        other = as_then_einsum().cpu()
+        ms = {k: [] for k in legs}
+        for _ in range(repeats):  # alternated
+            for k, fn in legs.items():
+                ms[k].append(wall_ms(fn))
+        res = {"files": n_files, "frames_per_file": frames_each, "channels": ch, "bits": bits, "out_channels": 2,
+               "weights": [[float(x) for x in row] for row in W], "window_samples": window, "window_start": start,
+               "window_bytes": n_files * window * per, "layout": "f32, planar, padded", "clock": "wall, device synchronised",
+               "warm_calls": 1, "repeats": repeats, "elements_that_differ_from_einsum": int((got != other).sum()),
+               "max_abs_difference_from_einsum": float((got - other).abs().max()), "elements": got.numel()}
+        for k in legs:
+            res[k] = summary(ms[k], keep=True)
+        res["to_itu_f32"]["x_as_then_einsum"] = res["as_f32_then_einsum"]["ms_median"] / res["to_itu_f32"]["ms_median"]
+    return res
+
+
 def resample_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: int, dst_rate: int = 48000) -> dict:
     import numpy as np
     import torch
@@ -1023,9 +1098,10 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix", "resample", "features", "write"),
+    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix", "resample", "features", "write", "downmix"),
                     default="all")
     ap.add_argument("--write-out", default=os.path.join(ROOT, "profiles", "bank_write_rate.json"))
+    ap.add_argument("--downmix-out", default=os.path.join(ROOT, "profiles", "decode_downmix_rate.json"))
     ap.add_argument("--resample-out", default=os.path.join(ROOT, "profiles", "decode_resample_rate.json"))
     ap.add_argument("--features-out", default=os.path.join(ROOT, "profiles", "decode_features_rate.json"))
     ap.add_argument("--mix-out", default=os.path.join(ROOT, "profiles", "decode_mix_rate.json"))
@@ -1051,6 +1127,13 @@ def main():
         print(json.dumps({"write": wr}), flush=True)
         with open(a.write_out, "w") as f:
             json.dump(wr, f, indent=1)
+            f.write("\n")
+        return
+    if a.legs == "downmix":  # opt-in: `all` leaves it out
+        dm = {"c6_16": downmix_rate(a.files, a.frames // a.files, a.window, a.repeats)}
+        print(json.dumps({"downmix": dm}), flush=True)
+        with open(a.downmix_out, "w") as f:
+            json.dump(dm, f, indent=1)
             f.write("\n")
         return
     if a.legs == "mix":  # opt-in: `all` leaves it out

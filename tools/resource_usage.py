@@ -22,4 +22,4 @@ for (k, v), dn in zip(rows.items(), names):
         continue
     print(f"{dn[:58]:58s} VGPR {v.get('VGPRs','?'):>3} spillV {v.get('VGPRs Spill','?'):>3} scratch "
           f"{v.get('ScratchSize [bytes/lane]','?'):>4} occ {v.get('Occupancy [waves/SIMD]','?')} "
-          f"spillS {v.get('SGPRs Spill','?')}")
+          f"spillS {v.get('SGPRs Spill','?')} SGPR {v.get('TotalSGPRs','?'):>3} LDS {v.get('LDS Size [bytes/block]','?')}")

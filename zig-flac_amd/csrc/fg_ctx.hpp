@@ -96,7 +96,15 @@ struct FG_LOCAL EncState {
 // and their scan, the expected frame table of a verify, and a chunk's frame table and results in
 // the host-buffer decodes (decode_chunk).  Those decodes' frames and PCM are grow-only.  The feature
 // delivery (fg_features.hpp) adds what its first stage leaves for k_features: the windows' extended
-// spans as planar F32 (feat_x) and their records and stage-1 results (feat_win), grow-only.
+// spans as planar F32 (feat_x) and their records and stage-1 results (feat_win), grow-only.  The
+// weighted channel mix (fg_deliver.hpp) adds the weight matrices of the window calls, found again by
+// their content (mix_weights: the last kMaxMixWeights of them).
+struct FG_LOCAL MixWeights {
+    uint32_t rows, cols;
+    std::vector<float> host;  // [rows][cols], what the caller passed
+    DevBuf<float> dev;        // the same floats
+};
+constexpr size_t kMaxMixWeights = 16;
 struct FG_LOCAL DecScratch {
     DevBuf<uint8_t> buf;
     uint64_t *samp_off, *total, *exp_off, *exp_number, *d_foff;
@@ -106,6 +114,7 @@ struct FG_LOCAL DecScratch {
     DevBuf<uint8_t> d_frames, d_pcm;
     DevBuf<float> feat_x;
     DevBuf<uint8_t> feat_win;
+    std::vector<MixWeights> mix_weights;
 };
 
 // Index scratch of a context, grow-only: the arrays of idx::IdxArgs, sized from the call's len and
@@ -264,7 +273,7 @@ hipError_t launch_window_init(const window::Cover *recs, streams::StreamResult *
 hipError_t launch_window_copy(const window::Cover *recs, const streams::StreamResult *res, const uint8_t *scratch,
                               const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off, uint32_t per, uint32_t n,
                               uint64_t max_bytes, hipStream_t st);
-// k_window_elements<dv.mix>: the delivery as tensor elements, with a channel mix or without
+// k_window_elements<dv.mix>: the delivery as tensor elements, without a channel mix, with masks or with weights
 hipError_t launch_window_elements(const window::Cover *recs, const streams::StreamResult *res, const window::WindowArg *args,
                                   const uint8_t *scratch, const uint64_t *src_base, uint8_t *out, const uint64_t *dst_off,
                                   const deliver::Delivery &dv, uint32_t n, uint64_t max_samples, hipStream_t st);

@@ -12,6 +12,7 @@
 
 #include "../../include/flacgpu.h"
 #include "fg_dec.hpp"
+#include "fg_deliver.hpp"
 #include "fg_features.hpp"
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
@@ -330,6 +331,30 @@ int flacgpu_resample_f32_host(const float *x, uint64_t total, uint32_t src_rate,
         });
     }
     *n = got;
+    return FLACGPU_OK;
+}
+
+int flacgpu_mix_weights_valid(uint32_t channels, uint32_t out_channels, const float *weights, uint32_t sample_format) {
+    return deliver::mixw_valid(channels, out_channels, weights, sample_format) ? 1 : 0;
+}
+
+int flacgpu_mix_weights_f32_host(const int32_t *samples, uint64_t n, uint32_t channels, uint32_t bits, uint32_t out_channels,
+                                 const float *weights, float *y) {
+    if ((bits != 8u && bits != 16u && bits != 24u && bits != 32u) || n > (1ull << 40) ||
+        !deliver::mixw_valid(channels, out_channels, weights, deliver::SAMPLE_F32))
+        return FLACGPU_ERR_INVALID_INPUT;
+    if (n == 0) return FLACGPU_OK;
+    if (!samples || !y) return FLACGPU_ERR_INVALID_INPUT;
+    const int64_t lo = -((int64_t)1 << (bits - 1u)), hi = ((int64_t)1 << (bits - 1u)) - 1;
+    for (uint64_t i = 0; i < n * channels; i++)
+        if (samples[i] < lo || samples[i] > hi) return FLACGPU_ERR_INVALID_INPUT;  // not a sample of `bits` bits
+    for (uint64_t t = 0; t < n; t++)
+        for (uint32_t k = 0; k < out_channels; k++) {
+            float acc = 0.0f;
+            for (uint32_t c = 0; c < channels; c++)
+                acc = deliver::mixw_step(acc, weights[(size_t)k * channels + c], samples[t * channels + c], bits);
+            y[t * out_channels + k] = acc;
+        }
     return FLACGPU_OK;
 }
 

@@ -426,6 +426,36 @@ int resample_table(flacgpu_ctx *c, const resample::Ratio &rt, uint32_t src_rate,
     return FLACGPU_OK;
 }
 
+// The device copy of a weight matrix W[K][C], found again by its content; a new one is uploaded by
+// the first call that needs it, which waits for st once more than the others.  The context keeps
+// the last kMaxMixWeights matrices: before the oldest is dropped st is waited for, since work queued
+// on it may still read that matrix.  dec_scratch(c) has run.
+int mix_weights(flacgpu_ctx *c, uint32_t K, uint32_t C, const float *W, const float **d_weights, hipStream_t st) {
+    DecScratch *d = c->dec.get();
+    const size_t n = (size_t)K * C;
+    for (const MixWeights &m : d->mix_weights)
+        if (m.rows == K && m.cols == C && std::memcmp(m.host.data(), W, n * sizeof(float)) == 0) {
+            *d_weights = m.dev.get();
+            return FLACGPU_OK;
+        }
+    MixWeights m;
+    try {
+        m.host.assign(W, W + n);
+        d->mix_weights.reserve(d->mix_weights.size() + 1u);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    m.rows = K;
+    m.cols = C;
+    HIPCHK(m.dev.grow(n));
+    HIPCHK(hipMemcpyAsync(m.dev.get(), m.host.data(), n * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (d->mix_weights.size() >= kMaxMixWeights) d->mix_weights.erase(d->mix_weights.begin());  // st has just been waited for
+    *d_weights = m.dev.get();
+    d->mix_weights.push_back(std::move(m));
+    return FLACGPU_OK;
+}
+
 // The windows of a call between its two halves: as uploaded, and their cover records on both sides.
 struct WindowsCall {
     uint32_t n = 0;
@@ -712,14 +742,15 @@ namespace {
 // flacgpu_decode_windows_device_as (offsets and caps in elements) and
 // flacgpu_decode_windows_device_mix (`masks`: its out_channels channel masks, else NULL) behind
 // their own checks; with src_rate != 0 flacgpu_decode_windows_device_resample: windows, offsets and
-// caps in output samples and elements at dst_rate
+// caps in output samples and elements at dst_rate.  `weights` (host, out_channels x C, never with
+// masks): the weighted mix of flacgpu_decode_windows_device_to in place of the masks.
 int windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
                    const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes, const flacgpu_index_result *d_index_results,
                    const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples, uint32_t n_windows,
                    const uint32_t *window_stream, const uint64_t *window_start, const uint64_t *window_count,
                    uint32_t sample_format, uint32_t flags, uint32_t out_channels, const uint8_t *masks, void *d_out,
                    const uint64_t *offsets, const uint64_t *caps, flacgpu_window_result *d_results, void *hip_stream,
-                   uint32_t src_rate = 0, uint32_t dst_rate = 0) {
+                   uint32_t src_rate = 0, uint32_t dst_rate = 0, const float *weights = nullptr) {
     if (!c || !d_data || !table_first || !d_frame_offsets || !d_frame_bytes || !d_index_results || !d_frame_first_sample ||
         !d_stream_samples || n_windows > 65535u)
         return FLACGPU_ERR_INVALID_INPUT;
@@ -730,9 +761,14 @@ int windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, co
     deliver::Delivery dv = deliver::identity_delivery(sample_format, flags, c->fmt.channels, c->fmt.bytes_per_sample);
     if (masks) {
         if (!deliver::mix_valid(c->fmt.channels, out_channels, masks, sample_format)) return FLACGPU_ERR_INVALID_INPUT;
-        dv.mix = 1u;
+        dv.mix = deliver::MIX_MASKS;
         dv.out_channels = out_channels;
         for (uint32_t k = 0; k < deliver::kMixMaxChannels; k++) dv.masks[k] = k < out_channels ? masks[k] : (uint8_t)0;
+    } else if (weights) {
+        if (!deliver::mixw_valid(c->fmt.channels, out_channels, weights, sample_format)) return FLACGPU_ERR_INVALID_INPUT;
+        dv.mix = deliver::MIX_WEIGHTS;
+        dv.out_channels = out_channels;
+        for (uint32_t k = 0; k < deliver::kMixMaxChannels; k++) dv.masks[k] = 0;
     }
     Resampling rs{{0, 0, 0, 0}, nullptr, d_stream_samples};
     if (src_rate && !resample::valid_ratio(src_rate, dst_rate, &rs.rt)) return FLACGPU_ERR_INVALID_INPUT;
@@ -743,6 +779,10 @@ int windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, co
     hipStream_t st = pick_stream(c, hip_stream);
     if (src_rate) {
         rc = resample_table(c, rs.rt, src_rate, dst_rate, &rs.d_coeffs, st);
+        if (rc) return rc;
+    }
+    if (weights) {
+        rc = mix_weights(c, out_channels, c->fmt.channels, weights, &dv.weights, st);
         if (rc) return rc;
     }
     WindowsCall wc;
@@ -922,24 +962,19 @@ int feat_filter(flacgpu_ctx *c, uint32_t R, uint32_t B, const float *F, const fl
     return FLACGPU_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-// Two stages.  Stage 1 is windows_device itself: every window's extended span [start - N / 2,
-// + (frames - 1) * H + N), clipped at the stream's start on the host (`clip` samples that
-// k_features reads as zeros), goes as planar padded F32 into the context's scratch.  Stage 2,
-// k_features, reads those planes and stage 1's results and writes the elements and the results.
-int flacgpu_decode_windows_device_features(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams,
-                                           const uint64_t *table_first, const uint64_t *d_frame_offsets,
-                                           const uint32_t *d_frame_bytes, const flacgpu_index_result *d_index_results,
-                                           const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
-                                           uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
-                                           const uint64_t *window_frames, uint32_t sample_format, uint32_t out_channels,
-                                           const uint8_t *channel_masks, uint32_t src_rate, uint32_t dst_rate,
-                                           const flacgpu_features *ft, const float *filters, void *d_out,
-                                           const uint64_t *out_offsets, const uint64_t *out_caps,
-                                           flacgpu_window_result *d_results, void *hip_stream) {
+// The one body of the feature delivery, in two stages.  Stage 1 is windows_device itself: every
+// window's extended span [start - N / 2, + (frames - 1) * H + N), clipped at the stream's start on
+// the host (`clip` samples that k_features reads as zeros), goes as planar padded F32 into the
+// context's scratch.  Stage 2, k_features, reads those planes and stage 1's results and writes the
+// elements and the results.  `weights` (host, out_channels x C, never with masks): stage 1 mixes by
+// the weighted rule, as flacgpu_decode_windows_device_to asks.
+int features_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
+                    const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes, const flacgpu_index_result *d_index_results,
+                    const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples, uint32_t n_windows,
+                    const uint32_t *window_stream, const uint64_t *window_start, const uint64_t *window_frames,
+                    uint32_t sample_format, uint32_t out_channels, const uint8_t *channel_masks, const float *weights,
+                    uint32_t src_rate, uint32_t dst_rate, const flacgpu_features *ft, const float *filters, void *d_out,
+                    const uint64_t *out_offsets, const uint64_t *out_caps, flacgpu_window_result *d_results, void *hip_stream) {
     if (!c || !ft || !d_data || !table_first || !d_frame_offsets || !d_frame_bytes || !d_index_results ||
         !d_frame_first_sample || !d_stream_samples || n_windows > 65535u)
         return FLACGPU_ERR_INVALID_INPUT;
@@ -952,9 +987,11 @@ int flacgpu_decode_windows_device_features(flacgpu_ctx *c, const uint8_t *d_data
         return FLACGPU_ERR_INVALID_INPUT;
     if (channel_masks && !deliver::mix_valid(c->fmt.channels, out_channels, channel_masks, sample_format))
         return FLACGPU_ERR_INVALID_INPUT;
+    if (weights && (channel_masks || !deliver::mixw_valid(c->fmt.channels, out_channels, weights, sample_format)))
+        return FLACGPU_ERR_INVALID_INPUT;
     resample::Ratio rt{0, 0, 0, 0};
     if ((src_rate || dst_rate) && !resample::valid_ratio(src_rate, dst_rate, &rt)) return FLACGPU_ERR_INVALID_INPUT;
-    const uint32_t B = feat::bins(p), n_rows = feat::rows(p), K = channel_masks ? out_channels : c->fmt.channels;
+    const uint32_t B = feat::bins(p), n_rows = feat::rows(p), K = channel_masks || weights ? out_channels : c->fmt.channels;
     for (size_t i = 0; i < (size_t)p.n_rows * B; i++)
         if (!std::isfinite(filters[i])) return FLACGPU_ERR_INVALID_INPUT;
     for (uint32_t w = 0; w < n_windows; w++) {
@@ -1020,11 +1057,81 @@ int flacgpu_decode_windows_device_features(flacgpu_ctx *c, const uint8_t *d_data
     rc = windows_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
                         d_stream_samples, n_windows, window_stream, s_start.data(), s_count.data(), deliver::SAMPLE_F32,
                         deliver::DELIVER_PLANAR | deliver::DELIVER_PAD, out_channels, channel_masks, d->feat_x.get(), s_off.data(),
-                        s_cap.data(), (flacgpu_window_result *)d_s1, hip_stream, src_rate, dst_rate);
+                        s_cap.data(), (flacgpu_window_result *)d_s1, hip_stream, src_rate, dst_rate, weights);
     if (rc) return rc;
     HIPCHK(launch_features(d_fw, d_s1, d_stream_samples, rt, d->feat_x.get(), d_table, d_filters, (uint8_t *)d_out,
                            (window::WindowResult *)d_results, p, K, sample_format, n_windows, max_items, st));
     return FLACGPU_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int flacgpu_decode_windows_device_features(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams,
+                                           const uint64_t *table_first, const uint64_t *d_frame_offsets,
+                                           const uint32_t *d_frame_bytes, const flacgpu_index_result *d_index_results,
+                                           const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
+                                           uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
+                                           const uint64_t *window_frames, uint32_t sample_format, uint32_t out_channels,
+                                           const uint8_t *channel_masks, uint32_t src_rate, uint32_t dst_rate,
+                                           const flacgpu_features *ft, const float *filters, void *d_out,
+                                           const uint64_t *out_offsets, const uint64_t *out_caps,
+                                           flacgpu_window_result *d_results, void *hip_stream) {
+    return features_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results,
+                           d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_frames,
+                           sample_format, out_channels, channel_masks, nullptr, src_rate, dst_rate, ft, filters, d_out, out_offsets,
+                           out_caps, d_results, hip_stream);
+}
+
+// The delivery as a struct.  Without weights it is the existing call the struct describes, behind
+// that call's own checks; with weights the same bodies (windows_device, features_device) run the
+// weighted mix in place of the masks.
+int flacgpu_decode_windows_device_to(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
+                                     const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                     const flacgpu_index_result *d_index_results, const uint64_t *d_frame_first_sample,
+                                     const uint64_t *d_stream_samples, uint32_t n_windows, const uint32_t *window_stream,
+                                     const uint64_t *window_start, const uint64_t *window_count,
+                                     const flacgpu_window_delivery *how, void *d_out, const uint64_t *out_offsets,
+                                     const uint64_t *out_caps, flacgpu_window_result *d_results, void *hip_stream) {
+    if (!c || !how || how->size != sizeof(flacgpu_window_delivery) || (how->channel_masks && how->channel_weights))
+        return FLACGPU_ERR_INVALID_INPUT;
+    if (how->features && how->flags) return FLACGPU_ERR_INVALID_INPUT;
+    const bool rates = how->src_rate || how->dst_rate;
+    const float *W = how->channel_weights;
+    if (how->features)
+        return features_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results,
+                               d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
+                               how->sample_format, how->out_channels, how->channel_masks, W, how->src_rate, how->dst_rate,
+                               how->features, how->filters, d_out, out_offsets, out_caps, d_results, hip_stream);
+    if (!W) {
+        if (rates)
+            return flacgpu_decode_windows_device_resample(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes,
+                                                          d_index_results, d_frame_first_sample, d_stream_samples, n_windows,
+                                                          window_stream, window_start, window_count, how->sample_format,
+                                                          how->flags, how->out_channels, how->channel_masks, how->src_rate,
+                                                          how->dst_rate, d_out, out_offsets, out_caps, d_results, hip_stream);
+        if (how->channel_masks)
+            return flacgpu_decode_windows_device_mix(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes,
+                                                     d_index_results, d_frame_first_sample, d_stream_samples, n_windows,
+                                                     window_stream, window_start, window_count, how->sample_format, how->flags,
+                                                     how->out_channels, how->channel_masks, d_out, out_offsets, out_caps,
+                                                     d_results, hip_stream);
+        return flacgpu_decode_windows_device_as(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results,
+                                                d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start,
+                                                window_count, how->sample_format, how->flags, d_out, out_offsets, out_caps,
+                                                d_results, hip_stream);
+    }
+    // weights: the checks of _as (or of _resample), then the matrix over the context's channels
+    if (how->sample_format >= deliver::SAMPLE_FORMATS || (how->flags & ~deliver::DELIVER_FLAGS) ||
+        ((uintptr_t)d_out & (deliver::elem_size(how->sample_format) - 1u)) ||
+        (rates && !resample::valid_ratio(how->src_rate, how->dst_rate, nullptr)) ||
+        !deliver::mixw_valid(c->fmt.channels, how->out_channels, W, how->sample_format))
+        return FLACGPU_ERR_INVALID_INPUT;
+    return windows_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results,
+                          d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
+                          how->sample_format, how->flags, how->out_channels, nullptr, d_out, out_offsets, out_caps, d_results,
+                          hip_stream, how->src_rate, how->dst_rate, W);
 }
 
 // every chunk's frames and frame table are uploaded, its results land at results + f0

@@ -1,8 +1,8 @@
 // fg_deliver.hpp -- the scalar rules of delivering decoded sample windows as tensor elements,
-// shared by the device kernel (k_window_elements in its two instantiations, fg_window.hip), the
+// shared by the device kernel (k_window_elements in its three instantiations, fg_window.hip), the
 // host layer (fg_dec_host.cpp) and the stand-alone host programs of the tests
-// (tests/cpp/deliver_host_main.cpp, tests/cpp/mix_host_main.cpp), which run the kernel's own row
-// code (fill_row_slot).  Compiles under hipcc and plain g++.
+// (tests/cpp/deliver_host_main.cpp, tests/cpp/mix_host_main.cpp, tests/cpp/mixw_host_main.cpp),
+// which run the kernel's own row code (fill_row_slot).  Compiles under hipcc and plain g++.
 //
 // A SOURCE SAMPLE is the B = bits / 8 bytes at a byte address of any alignment: signed two's
 // complement, little-endian, sign-extended to i32 -- what every decode call here writes to PCM,
@@ -13,7 +13,8 @@
 // consecutive destination elements (one plane, or the whole interleaved region); its ROW PLAN cuts
 // it into the elements before the first 16-byte boundary, whole 16-byte units and the elements
 // after them: the element-granular counterpart of window::copy_plan.  With a CHANNEL MIX the
-// region has K output channels in place of C, each made of a set of source channels (below).
+// region has K output channels in place of C, each made of a set of source channels or, with
+// WEIGHTS, of a weighted sum of all of them (below).
 #pragma once
 #include <stdint.h>
 
@@ -28,18 +29,25 @@ constexpr uint32_t SAMPLE_BYTES = 0xFFFFFFFFu;  // not an element format: the by
 
 constexpr uint32_t kMixMaxChannels = 8;  // output channels of a mix, and source channels of a mask
 
+// The three modes of a delivery's `mix`: the source channels as they are, output channels made of
+// channel masks, output channels made of a weight matrix.
+enum : uint32_t { MIX_NONE = 0, MIX_MASKS = 1, MIX_WEIGHTS = 2 };
+
 // How a window call delivers: `format` SAMPLE_BYTES copies the PCM bytes (k_window_copy, flags 0);
-// any other format converts (k_window_elements<false>) or, with `mix` set, converts and mixes
-// (k_window_elements<true>): out_channels output channels, output channel k made of the source
-// channels whose bits masks[k] has.  Without `mix` out_channels = channels and masks[k] = 1 << k.
+// any other format converts (k_window_elements<MIX_NONE>) or, with `mix` set, converts and mixes:
+// out_channels output channels, output channel k made of the source channels whose bits masks[k]
+// has (k_window_elements<MIX_MASKS>), or the weighted sum of all source channels by row k of
+// `weights`, out_channels x channels floats, row-major, in DEVICE memory
+// (k_window_elements<MIX_WEIGHTS>).  Without `mix` out_channels = channels and masks[k] = 1 << k.
 struct Delivery {
     uint32_t format, flags, channels, sample_bytes;
     uint32_t mix, out_channels;
     uint8_t masks[kMixMaxChannels];
+    const float *weights;
 };
 
 FG_HD Delivery identity_delivery(uint32_t format, uint32_t flags, uint32_t channels, uint32_t sample_bytes) {
-    Delivery dv = {format, flags, channels, sample_bytes, 0u, channels, {0, 0, 0, 0, 0, 0, 0, 0}};
+    Delivery dv = {format, flags, channels, sample_bytes, MIX_NONE, channels, {0, 0, 0, 0, 0, 0, 0, 0}, nullptr};
     for (uint32_t k = 0; k < channels && k < kMixMaxChannels; k++) dv.masks[k] = (uint8_t)(1u << k);
     return dv;
 }
@@ -160,6 +168,88 @@ FG_HD uint32_t mix_element(const uint32_t *words, uint32_t off, uint32_t B, uint
         }
     if (m == 1u) return element(one, 8u * B, format);
     return mean_element(s, 8u * B, m == 2u ? 1u : (m == 4u ? 2u : 3u), format);
+}
+
+// ---- the weighted channel mix --------------------------------------------------------------------
+// With weights, output channel k of a sample of C source channels is a chain over row k of a
+// row-major K x C float matrix W.  With x_c the F32 element of source channel c (f32_bits),
+//     y = +0.0f;  for c = 0 .. C-1 in this order:  y = fmaf(W[k][c], x_c, y)
+// one accumulator and one correctly rounded fused multiply-add a source channel: the construction
+// of resample::fir and of the feature chains.  SAMPLE_F32 is y, F16 and BF16 are y narrowed
+// (f16_bits_wide, bf16_bits); SAMPLE_I32 is not offered.
+//
+// A weight is 0 (either sign) or has 2^-32 <= |w| <= 2^32, and these bounds are derived: |x_c| is 0
+// or lies in [2^-31, 1] and is a multiple of 2^-31; a weight that is not 0 is a multiple of 2^-55
+// (24 significant bits from 2^-32 up).  Every product is therefore 0 or a normal number, a multiple
+// of 2^-86, of magnitude 2^-63 to 2^32; every partial sum is a multiple of 2^-86 of magnitude at
+// most 8 * 2^32 = 2^35.  So no fused multiply-add underflows or overflows, none of its results is
+// subnormal, and the only zero it gives is the exact cancellation, which to nearest-even is +0.0f:
+// the accumulator starts at +0.0f and is never -0.0f.  With y never -0.0f, fmaf(w, x, y) = y bit
+// for bit where w or x is zero (y + (+-0) = y), so passing over zero weights, and over channels
+// whose x_c is 0, changes no bit: mixw_step skips a zero weight, and such a channel is not read.
+FG_HD bool mixw_weight_valid(float w) {
+    union {
+        float f;
+        uint32_t u;
+    } v;
+    v.f = w;
+    const uint32_t a = v.u & 0x7FFFFFFFu;  // NaN and infinity lie above the upper bound, subnormals below the lower
+    return a == 0u || (a >= ((127u - 32u) << 23) && a <= ((127u + 32u) << 23));
+}
+
+// A weight matrix of K rows over a source of C channels: C and K are 1 to 8, the format is a float
+// one, every weight is valid.
+FG_HD bool mixw_valid(uint32_t C, uint32_t K, const float *W, uint32_t format) {
+    if (!W || C < 1u || C > kMixMaxChannels || K < 1u || K > kMixMaxChannels) return false;
+    if (format != SAMPLE_F32 && format != SAMPLE_F16 && format != SAMPLE_BF16) return false;
+    for (uint32_t i = 0; i < K * C; i++)
+        if (!mixw_weight_valid(W[i])) return false;
+    return true;
+}
+
+// One link of the chain: source sample s of `bits` bits under weight w onto the accumulator y.  The
+// multiply-add is the explicit builtin; nothing else here can be contracted (the scale of f32_bits
+// is an exact product and an operand of the multiplication, not of the sum).
+FG_HD float mixw_step(float y, float w, int32_t s, uint32_t bits) {
+    if (w == 0.0f) return y;
+    union {
+        float f;
+        uint32_t u;
+    } x;
+    x.u = f32_bits(s, bits);
+    return __builtin_fmaf(w, x.f, y);
+}
+
+// The chain over one row w[0 .. C) for the sample whose C source channels are the B-byte samples
+// from byte offset `off` of `words` on (sample_in_words); a channel under a zero weight is not read.
+FG_HD float mixw_value(const uint32_t *words, uint32_t off, uint32_t B, uint32_t C, const float *w) {
+    float y = 0.0f;
+    for (uint32_t c = 0; c < C; c++) {
+        const float wc = w[c];
+        if (wc != 0.0f) y = mixw_step(y, wc, sample_in_words(words, off + c * B, B), 8u * B);
+    }
+    return y;
+}
+
+// f16_bits for a value that can pass 65520 -- a weighted sample reaches 2^35, a resampled one four
+// times that --: from 65520 on, the tie between the largest f16 and 2^16, nearest-even is infinity.
+FG_HD uint16_t f16_bits_wide(uint32_t f) {
+    return (f & 0x7FFFFFFFu) >= 0x477FF000u ? (uint16_t)(((f >> 16) & 0x8000u) | 0x7C00u) : f16_bits(f);
+}
+
+// y in a float `format`: 32 bits, or 16 in the low half
+FG_HD uint32_t mixw_narrow(float y, uint32_t format) {
+    union {
+        float f;
+        uint32_t u;
+    } v;
+    v.f = y;
+    if (format == SAMPLE_F32) return v.u;
+    return format == SAMPLE_F16 ? f16_bits_wide(v.u) : bf16_bits(v.u);
+}
+
+FG_HD uint32_t mixw_element(const uint32_t *words, uint32_t off, uint32_t B, uint32_t C, const float *w, uint32_t format) {
+    return mixw_narrow(mixw_value(words, off, B, C, w), format);
 }
 
 // The capacity rule.  A window that delivers n of its `count` stated samples needs count * unit of

@@ -6,8 +6,8 @@
 //                      needs for them come from the stream's total, and the Cover record is the cover
 //                      of [lo, hi) with n_samples = n: the chunk loop, k_window_init and
 //                      k_window_results then run as for every other window call
-//   k_window_resample  in place of k_window_elements, one kernel in two instantiations (<true>: with
-//                      a channel mix).  A workgroup takes tiles of output samples: a tile's source
+//   k_window_resample  in place of k_window_elements, one kernel in three instantiations (the modes of
+//                      deliver::Delivery::mix: none, channel masks, a weight matrix).  A workgroup takes tiles of output samples: a tile's source
 //                      span, halo included, goes from the window's decoded covering frames to LDS as
 //                      F32 elements, one skewed plane an output channel (the mix applied once a
 //                      source sample, zeros where the span leaves the stream), then every row of the
@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(256) k_resample_cover(const WindowArg *args, c
 // padded as k_window_elements does.  src_base[w] + skip * per is source sample lo of the window's
 // source range [lo, hi) in the scratch.  tile, plane: resample::tile_plan's for (rt, K); the
 // dynamic LDS is K planes.  coeffs: the table of rt, L rows of T.
-template <bool Mix>
+template <uint32_t Mix>
 __global__ void __launch_bounds__(256) k_window_resample(const Cover *recs, const streams::StreamResult *res, const WindowArg *args,
                                                           const uint64_t *totals, const uint8_t *scratch, const uint64_t *src_base,
                                                           uint8_t *out, const uint64_t *dst_off, deliver::Delivery dv,
@@ -79,11 +79,11 @@ __global__ void __launch_bounds__(256) k_window_resample(const Cover *recs, cons
     const uint64_t count = a.count, n = c.n_samples;
     const uint64_t written = deliver::written_samples(n, count, dv.flags);
     if (written == 0) return;
-    const uint32_t C = dv.channels, K = Mix ? dv.out_channels : C, B = dv.sample_bytes, per = C * B;
+    const uint32_t C = dv.channels, K = Mix != deliver::MIX_NONE ? dv.out_channels : C, B = dv.sample_bytes, per = C * B;
     const uint32_t format = dv.format, esz = deliver::elem_size(format), per_unit = 16u / esz, T = rt.T;
     const bool planar = (dv.flags & deliver::DELIVER_PLANAR) != 0;
     uint64_t masks = 0;  // mask k in byte k: indexed by shifts, so that the argument is never addressed
-    if (Mix) {
+    if (Mix == deliver::MIX_MASKS) {
 #pragma unroll
         for (uint32_t k = 0; k < deliver::kMixMaxChannels; k++) masks |= (uint64_t)dv.masks[k] << (8u * k);
     }
@@ -102,18 +102,45 @@ __global__ void __launch_bounds__(256) k_window_resample(const Cover *recs, cons
             const uint64_t last = resample::source_index(rt, a.start + t0 + nfir - 1u, nullptr);
             const uint32_t len = (uint32_t)(last - first) + T;  // <= tile_span(rt, tile_n)
             const int64_t s0 = (int64_t)first - (int64_t)rt.Hw + 1;
-            for (uint32_t item = tid; item < len * K; item += 256u) {
-                const uint32_t ch = item / len, j = item - ch * len;
-                const int64_t i = s0 + (int64_t)j;
-                uint32_t v = 0u;  // +0.0f outside the stream
-                if (i >= (int64_t)lo && i < (int64_t)hi) {
-                    const uintptr_t at = (uintptr_t)(src + (uint64_t)(i - (int64_t)lo) * per), at0 = at & ~(uintptr_t)3;
-                    const uint32_t *words = (const uint32_t *)at0;
-                    const uint32_t off = (uint32_t)(at - at0);
-                    if (Mix) v = deliver::mix_element(words, off, B, (uint32_t)(masks >> (8u * ch)) & 0xFFu, deliver::SAMPLE_F32);
-                    else v = deliver::f32_bits(deliver::sample_in_words(words, off + ch * B, B), 8u * B);
+            if (Mix == deliver::MIX_WEIGHTS) {
+                // a plane at a time: row ch of the weights in registers (a uniform read of device memory
+                // under constant indices, no argument or array is addressed), then the chain of
+                // deliver::mixw_step once a source sample
+                for (uint32_t ch = 0; ch < K; ch++) {
+                    float wr[deliver::kMixMaxChannels];
+#pragma unroll
+                    for (uint32_t cc = 0; cc < deliver::kMixMaxChannels; cc++) wr[cc] = cc < C ? dv.weights[ch * C + cc] : 0.0f;
+                    for (uint32_t j = tid; j < len; j += 256u) {
+                        const int64_t i = s0 + (int64_t)j;
+                        float y = 0.0f;  // +0.0f outside the stream
+                        if (i >= (int64_t)lo && i < (int64_t)hi) {
+                            const uintptr_t at = (uintptr_t)(src + (uint64_t)(i - (int64_t)lo) * per), at0 = at & ~(uintptr_t)3;
+                            const uint32_t *words = (const uint32_t *)at0;
+                            const uint32_t off = (uint32_t)(at - at0);
+#pragma unroll
+                            for (uint32_t cc = 0; cc < deliver::kMixMaxChannels; cc++)
+                                if (cc < C && wr[cc] != 0.0f)
+                                    y = deliver::mixw_step(y, wr[cc], deliver::sample_in_words(words, off + cc * B, B), 8u * B);
+                        }
+                        s_x[ch * plane + resample::skew(j)] = y;
+                    }
                 }
-                s_x[ch * plane + resample::skew(j)] = __uint_as_float(v);
+            } else {
+                for (uint32_t item = tid; item < len * K; item += 256u) {
+                    const uint32_t ch = item / len, j = item - ch * len;
+                    const int64_t i = s0 + (int64_t)j;
+                    uint32_t v = 0u;  // +0.0f outside the stream
+                    if (i >= (int64_t)lo && i < (int64_t)hi) {
+                        const uintptr_t at = (uintptr_t)(src + (uint64_t)(i - (int64_t)lo) * per), at0 = at & ~(uintptr_t)3;
+                        const uint32_t *words = (const uint32_t *)at0;
+                        const uint32_t off = (uint32_t)(at - at0);
+                        if (Mix == deliver::MIX_MASKS)
+                            v = deliver::mix_element(words, off, B, (uint32_t)(masks >> (8u * ch)) & 0xFFu, deliver::SAMPLE_F32);
+                        else
+                            v =deliver::f32_bits(deliver::sample_in_words(words, off + ch * B, B), 8u * B);
+                    }
+                    s_x[ch * plane + resample::skew(j)] = __uint_as_float(v);
+                }
             }
         }
         __syncthreads();
@@ -131,6 +158,7 @@ __global__ void __launch_bounds__(256) k_window_resample(const Cover *recs, cons
                 const float *x = s_x + ch * plane;
                 const float y = resample::fir(coeffs + (uint64_t)p * T, T, [&](uint32_t tap) { return x[resample::skew(base + tap)]; });
                 const uint32_t f = __float_as_uint(y);
+                if (Mix == deliver::MIX_WEIGHTS) return deliver::mixw_narrow(y, format);  // |y| can pass the f16 range
                 if (format == deliver::SAMPLE_F32) return f;
                 return (uint32_t)(format == deliver::SAMPLE_F16 ? deliver::f16_bits(f) : deliver::bf16_bits(f));
             });
@@ -161,8 +189,11 @@ hipError_t launch_window_resample(const Cover *recs, const streams::StreamResult
     const resample::TilePlan tp = resample::tile_plan(rt, dv.out_channels);
     const uint64_t tiles = (max_samples + tp.tile - 1u) / tp.tile;
     const uint32_t gx = (uint32_t)(tiles > 1024u ? 1024u : tiles);
-    hipLaunchKernelGGL(dv.mix ? k_window_resample<true> : k_window_resample<false>, dim3(gx, n), dim3(256), tp.lds_bytes, st, recs,
-                       res, args, totals, scratch, src_base, out, dst_off, dv, rt, tp.tile, tp.plane, coeffs);
+    const auto kernel = dv.mix == deliver::MIX_WEIGHTS ? k_window_resample<deliver::MIX_WEIGHTS>
+                        : dv.mix                       ? k_window_resample<deliver::MIX_MASKS>
+                                                       : k_window_resample<deliver::MIX_NONE>;
+    hipLaunchKernelGGL(kernel, dim3(gx, n), dim3(256), tp.lds_bytes, st, recs, res, args, totals, scratch, src_base, out, dst_off,
+                       dv, rt, tp.tile, tp.plane, coeffs);
     return hipGetLastError();
 }
 

@@ -9,13 +9,16 @@
 //                     chunk loop in which a window is what a stream is in fg_dec_streams.hip
 //   k_window_copy     per window (blockIdx.y), after the last chunk: the delivered bytes from the
 //                     window's decoded covering frames to the caller's region
-//   k_window_elements in place of k_window_copy, one kernel in two instantiations.  <false>, for
+//   k_window_elements in place of k_window_copy, one kernel in three instantiations.  <MIX_NONE>, for
 //                     flacgpu_decode_windows_device_as: the delivered samples converted to tensor
 //                     elements (fg_deliver.hpp), interleaved or planar, the rest of a padded window
-//                     zeroed.  <true>, for flacgpu_decode_windows_device_mix: the same pass with a
+//                     zeroed.  <MIX_MASKS>, for flacgpu_decode_windows_device_mix: the same pass with a
 //                     channel count other than the source's, every output channel the exact mean
-//                     of a set of source channels, one of them, or silence.  Both write rows by
-//                     deliver::fill_row_slot, which the host programs of the tests run as well
+//                     of a set of source channels, one of them, or silence.  <MIX_WEIGHTS>, for
+//                     flacgpu_decode_windows_device_to with a weight matrix: every output channel
+//                     the fused multiply-add chain of deliver::mixw_value over all source channels.
+//                     All write rows by deliver::fill_row_slot, which the host programs of the tests
+//                     run as well
 //   k_window_results  per window: its flacgpu_window_result
 //
 // Every index is bounded by what the index left and the host sized: a frame i of stream s is
@@ -166,9 +169,20 @@ __device__ __forceinline__ uint32_t mix_tile_element(const uint32_t *words, uint
     return deliver::mix_element(words, lead + t * per, dv.sample_bytes, mask, dv.format);
 }
 
+// One element of a weighted tile: the chain of deliver::mixw_value over row w of the weights for the
+// tile's sample t, or zero past its `nsrc` decoded samples (the padding).
+__device__ __forceinline__ uint32_t mixw_tile_element(const uint32_t *words, uint32_t lead, uint32_t t, uint32_t nsrc, uint32_t per,
+                                                      const float *w, const deliver::Delivery &dv) {
+    if (t >= nsrc) return 0u;
+    return deliver::mixw_element(words, lead + t * per, dv.sample_bytes, dv.channels, w, dv.format);
+}
+
 // In place of k_window_copy: window w (blockIdx.y) as K channels of dv.format elements to out +
-// dst_off[w] elements; K = dv.channels, or with Mix dv.out_channels, output channel k of a sample
-// then made of the source channels in dv.masks[k] (deliver::mix_element).  A workgroup takes tiles
+// dst_off[w] elements; K = dv.channels, or with a Mix dv.out_channels, output channel k of a sample
+// then made of the source channels in dv.masks[k] (MIX_MASKS: deliver::mix_element) or of all of
+// them under row k of dv.weights (MIX_WEIGHTS: deliver::mixw_element; the K * C <= 64 weights go
+// from device memory to LDS once a workgroup, before the first tile, and are indexed there: a
+// by-value argument indexed dynamically would be forced into scratch).  A workgroup takes tiles
 // of tile_samples(per) consecutive source samples: the aligned 8-byte words of the scratch that
 // hold a tile's source bytes go to LDS (no word past the one that holds the window's last byte is
 // read; a tile of padding alone reads nothing), then every row of the tile -- a plane's part, or
@@ -176,7 +190,7 @@ __device__ __forceinline__ uint32_t mix_tile_element(const uint32_t *words, uint
 // (deliver::fill_row_slot): whole 16-byte units built from LDS, the head and the tail elements one
 // at a time.  A window that is not clean writes nothing; one with no samples still writes its
 // padding.
-template <bool Mix>
+template <uint32_t Mix>
 __global__ void __launch_bounds__(256) k_window_elements(const Cover *recs, const streams::StreamResult *res, const WindowArg *args,
                                                           const uint8_t *scratch, const uint64_t *src_base, uint8_t *out,
                                                           const uint64_t *dst_off, deliver::Delivery dv) {
@@ -187,13 +201,17 @@ __global__ void __launch_bounds__(256) k_window_elements(const Cover *recs, cons
     const uint64_t count = args[w].count, n = c.n_samples;
     const uint64_t total = deliver::written_samples(n, count, dv.flags);
     if (total == 0) return;
-    const uint32_t C = dv.channels, K = Mix ? dv.out_channels : C, per = C * dv.sample_bytes;
+    const uint32_t C = dv.channels, K = Mix != deliver::MIX_NONE ? dv.out_channels : C, per = C * dv.sample_bytes;
     const uint32_t esz = deliver::elem_size(dv.format), per_unit = 16u / esz, T = deliver::tile_samples(per);
     const bool planar = (dv.flags & deliver::DELIVER_PLANAR) != 0;
     uint64_t masks = 0;  // mask k in byte k: indexed by shifts, so that the argument is never addressed
-    if (Mix) {
+    if (Mix == deliver::MIX_MASKS) {
 #pragma unroll
         for (uint32_t k = 0; k < deliver::kMixMaxChannels; k++) masks |= (uint64_t)dv.masks[k] << (8u * k);
+    }
+    __shared__ float s_w[deliver::kMixMaxChannels * deliver::kMixMaxChannels];
+    if (Mix == deliver::MIX_WEIGHTS) {  // read after the first tile's barrier
+        if (tid < K * C) s_w[tid] = dv.weights[tid];
     }
     const uint8_t *src = scratch + src_base[w] + c.skip * per;
     uint8_t *dst = out + dst_off[w] * esz;
@@ -216,7 +234,12 @@ __global__ void __launch_bounds__(256) k_window_elements(const Cover *recs, cons
         for (uint32_t item = tid; item < rows * slots; item += 256u) {
             const uint32_t r = item / slots, k = item - r * slots;
             uint8_t *row = dst + (planar ? (uint64_t)r * count + t0 : t0 * K) * esz;
-            if (Mix) {
+            if (Mix == deliver::MIX_WEIGHTS) {
+                deliver::fill_row_slot(row, row_elems, esz, k, max_units, [&](uint32_t e) {
+                    const uint32_t t = planar ? e : e / K, ch = planar ? r : e - t * K;
+                    return mixw_tile_element(words, lead, t, nsrc, per, s_w + ch * C, dv);
+                });
+            } else if (Mix == deliver::MIX_MASKS) {
                 // row element e: sample e of plane r, or sample e / K, channel e % K of the interleaved row
                 deliver::fill_row_slot(row, row_elems, esz, k, max_units, [&](uint32_t e) {
                     const uint32_t t = planar ? e : e / K, ch = planar ? r : e - t * K;
@@ -306,8 +329,10 @@ hipError_t launch_window_elements(const Cover *recs, const streams::StreamResult
     const uint32_t T = deliver::tile_samples(dv.channels * dv.sample_bytes);
     const uint64_t tiles = (max_samples + T - 1u) / T;
     const uint32_t gx = (uint32_t)(tiles > 1024u ? 1024u : tiles);
-    hipLaunchKernelGGL(dv.mix ? k_window_elements<true> : k_window_elements<false>, dim3(gx, n), dim3(256), 0, st, recs, res, args,
-                       scratch, src_base, out, dst_off, dv);
+    const auto kernel = dv.mix == deliver::MIX_WEIGHTS ? k_window_elements<deliver::MIX_WEIGHTS>
+                        : dv.mix                       ? k_window_elements<deliver::MIX_MASKS>
+                                                       : k_window_elements<deliver::MIX_NONE>;
+    hipLaunchKernelGGL(kernel, dim3(gx, n), dim3(256), 0, st, recs, res, args, scratch, src_base, out, dst_off, dv);
     return hipGetLastError();
 }
 

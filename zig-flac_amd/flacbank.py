@@ -13,7 +13,8 @@ file_bytes writes a bank's file back out as a .flac.
 
 FlacBank holds files of one channel count and depth.  FlacMixBank holds any, as one FlacBank per
 (channels, bits), and delivers every crop with the bank's one channel count through
-flacgpu_decode_windows_device_mix."""
+flacgpu_decode_windows_device_mix (channel masks) or, where a group's mix is a weight matrix
+(a surround downmix, mid/side, a mean of three), flacgpu_decode_windows_device_to."""
 from __future__ import annotations
 
 import ctypes
@@ -68,7 +69,7 @@ def _out_samples(samples: int, src: int, rate: int) -> int:
 def _crops(who, device, n_files, K, groups, where, check, file, start, length, dtype, planar, pad, out, strict,
            rate=None, rate_of=None, feat=None):
     """The one body of FlacBank.crops and FlacMixBank.crops: crops of K channels from `groups` =
-    [(FlacBank, its channel masks or None)], file f being file where(f)[1] of group where(f)[0];
+    [(FlacBank, its channel masks, its [K, C] float32 weight matrix or None)], file f being file where(f)[1] of group where(f)[0];
     check(fmt): the caller's own refusals of a format, raised between the dtype's and the crops'.
     rate: start and length are in samples at that rate, rate_of(f) being file f's own: the crops of
     files at another rate are resampled, one call per group and source rate.
@@ -129,7 +130,13 @@ def _crops(who, device, n_files, K, groups, where, check, file, start, length, d
                 tables = (bank._data.data_ptr(), bank._first, bank._off.data_ptr(), bank._fbytes.data_ptr(),
                           bank._ires.data_ptr(), bank._pos.data_ptr(), bank._totals.data_ptr(), windows, fmt, flags)
                 to = (x.data_ptr(), [w * per_crop for w in part], [per_crop] * len(part), d_res.data_ptr() + 32 * row)
-                if feat is not None:
+                if _is_weights(masks):
+                    bank._dec.decode_windows_device_to(*tables[:8], fmt, 0 if feat is not None else flags, *to,
+                                                       channel_weights=masks, src_rate=src or 0, dst_rate=rate if src else 0,
+                                                       n_fft=feat[0] if feat is not None else None,
+                                                       hop=feat[1] if feat is not None else None,
+                                                       filters=feat[2] if feat is not None else None, stream=st)
+                elif feat is not None:
                     bank._dec.decode_windows_device_features(*tables[:-1], masks, src or 0, rate if src else 0, *feat[:3], *to,
                                                              stream=st)
                 elif src is not None:
@@ -563,6 +570,104 @@ class FlacBank:
 MIX_MAX_CHANNELS = 8
 
 
+def _is_weights(mix) -> bool:
+    """A group's mix is a list of channel masks, or a [K, C] float32 numpy array of weights."""
+    return mix is not None and not isinstance(mix, list)
+
+
+def _mix_entry(given):
+    """A channel_map entry as ("masks", [int]) or ("weights", float32 [K, C]); ValueError(why) for
+    an entry that is neither K integers nor K rows of numbers."""
+    import numpy as np
+
+    if hasattr(given, "detach") and hasattr(given, "numpy"):  # a torch tensor
+        if getattr(given, "is_cuda", False):
+            raise ValueError("it is a tensor on a device; weights are given on the CPU")
+        given = given.detach().numpy()
+    if isinstance(given, np.ndarray):
+        if given.ndim == 1:
+            return "masks", [int(m) for m in given]
+        if given.ndim != 2:
+            raise ValueError(f"it has {given.ndim} dimensions; masks have one, weights two")
+        rows = list(given)
+    else:
+        rows = list(given)
+        nested = [isinstance(r, (list, tuple, np.ndarray)) or (hasattr(r, "detach") and hasattr(r, "numpy")) for r in rows]
+        if not any(nested):
+            return "masks", [int(m) for m in rows]
+        if not all(nested):
+            raise ValueError("it mixes masks and rows of weights: give K integers, or K rows of numbers")
+    try:
+        w = np.ascontiguousarray(np.asarray([np.asarray(r, dtype=np.float64) for r in rows]), dtype=np.float32)
+    except (TypeError, ValueError):
+        raise ValueError("its rows are not numbers, or differ in length") from None
+    if w.ndim != 2:
+        raise ValueError("its rows are not rows of numbers of one length")
+    return "weights", w
+
+
+def _weights_error(C: int, K: int, w) -> Optional[str]:
+    """Why the float32 matrix w is no valid weighted mix of C channels to K (the library's
+    flacgpu_mix_weights_valid decides), or None."""
+    import numpy as np
+
+    if w.shape != (K, C):
+        return f"it has {w.shape[0]} rows of {w.shape[1]} weights, not {K} rows of {C}"
+    if flacgpu.mix_weights_valid(w):
+        return None
+    for k in range(K):
+        for c in range(C):
+            if not flacgpu.mix_weights_valid(w[k:k + 1, c:c + 1]):
+                return (f"weight [{k}][{c}] ({float(w[k, c])!r}) is neither 0 nor a finite number of magnitude "
+                        f"2^-32 to 2^32")
+    return "the library refuses it"
+
+
+_ITU = {  # RFC 9639's channel orders: l / r own front, c centre, f LFE, bl / br own-side back or side, bc back centre
+    3: ("l", "r", "c"), 4: ("l", "r", "bl", "br"), 5: ("l", "r", "c", "bl", "br"), 6: ("l", "r", "c", "f", "bl", "br"),
+    7: ("l", "r", "c", "f", "bc", "bl", "br"), 8: ("l", "r", "c", "f", "bl", "br", "bl", "br")}
+
+
+def _downmix(C: int, K: int, kind: str):
+    """The float32 [K, C] matrix of downmix `kind` for C channels to K, or None where it has none."""
+    import math
+
+    import numpy as np
+
+    if kind == "mean":
+        if K != 1 or not 1 <= C <= MIX_MAX_CHANNELS:
+            return None
+        return np.full((1, C), np.float32(1.0 / C), dtype=np.float32)
+    if kind != "itu" or K not in (1, 2) or C not in _ITU:
+        return None
+    a = math.sqrt(0.5)
+    left = {"l": 1.0, "r": 0.0, "c": a, "f": 0.0, "bl": a, "br": 0.0, "bc": 0.5}
+    right = {"l": 0.0, "r": 1.0, "c": a, "f": 0.0, "bl": 0.0, "br": a, "bc": 0.5}
+    rows = [[left[r] for r in _ITU[C]], [right[r] for r in _ITU[C]]]
+    if K == 1:
+        rows = [[x + y for x, y in zip(*rows)]]
+    return np.array([[v / math.fsum(row) for v in row] for row in rows], dtype=np.float64).astype(np.float32)
+
+
+def downmix_matrix(C: int, K: int, kind: str):
+    """The K rows of C float32 weights FlacMixBank(downmix=kind) uses for sources of C channels.
+
+    "mean": K = 1, any C in 1..8: every weight is (float)(1 / C).  "itu": K = 1 or 2, C = 3..8 in
+    RFC 9639's channel order (L R C; FL FR BL BR; FL FR FC BL BR; FL FR FC LFE BL BR; FL FR FC LFE
+    BC SL SR; FL FR FC LFE BL BR SL SR).  The left row, unnormalised, with a = sqrt(0.5): the own
+    front 1, FC a, LFE 0, every back or side channel of its own side a, BC 0.5, the other side 0;
+    the right row mirrors it; K = 1 is the sum of the two.  Every row is divided by its own sum in
+    double and rounded once to float32, so a full-scale input stays in [-1, 1] up to rounding.
+    ValueError for any other (C, K, kind)."""
+    C, K = int(C), int(K)
+    if kind not in ("mean", "itu"):
+        raise ValueError(f"downmix_matrix: kind is 'mean' or 'itu', not {kind!r}")
+    w = _downmix(C, K, kind)
+    if w is None:
+        raise ValueError(f"downmix_matrix: there is no {kind!r} mix of {C} channels to {K}")
+    return w
+
+
 def _mix_error(C: int, masks: Sequence[int], integers: bool = False) -> Optional[str]:
     """Why `masks` is no valid mix of a source of C channels (the rule of
     flacgpu_decode_windows_device_mix, checked here so that it is a ValueError before any call), or None."""
@@ -597,15 +702,23 @@ class FlacMixBank:
     flacgpu_decode_windows_device_mix with the group's channel masks: channel_map[C], a list of
     `channels` masks (bit c: source channel c; 0, 1, 2, 4 or 8 bits) for sources of C channels,
     or else the default: identity where C == channels, the one channel to every output where
-    C == 1, the mean of all where channels == 1 and C is 2, 4 or 8.  Without sample_rate, rates
+    C == 1, the mean of all where channels == 1 and C is 2, 4 or 8.  channel_map[C] may instead be
+    `channels` rows of C numbers (nested sequences, a [channels, C] numpy array or CPU tensor): a
+    weight matrix, converted to float32, every weight 0 or of magnitude 2^-32 to 2^32; output
+    channel k of such a group is the fused multiply-add chain of row k over the source channels
+    (flacgpu_decode_windows_device_to), e.g. {2: [[0.5, 0.5], [0.5, -0.5]]} for mid/side.  downmix
+    ("mean" or "itu", see downmix_matrix) gives such a matrix to the (C, channels) pairs for which
+    neither channel_map nor the default has a mix; without it they are refused.  Without sample_rate, rates
     are reported, never converted.  With it every crop is stated and delivered at that rate: files
     at another rate go through flacgpu_decode_windows_device_resample (float dtypes only); `samples`
     stays in source samples, `out_samples` counts them at sample_rate.  A bank takes no locks: one
     bank per thread."""
 
     def __init__(self, files: Sequence[bytes], channels: int, device: int = 0, max_frames: int = 4096,
-                 channel_map: Optional[dict] = None, sample_rate: Optional[int] = None):
+                 channel_map: Optional[dict] = None, sample_rate: Optional[int] = None, downmix: Optional[str] = None):
         who, K = "FlacMixBank", int(channels)
+        if downmix not in (None, "mean", "itu"):
+            raise ValueError(f"{who}: downmix is None, 'mean' or 'itu', not {downmix!r}")
         self._groups: list = []
         if len(files) == 0:
             raise ValueError(f"{who}: no files")
@@ -627,7 +740,22 @@ class FlacMixBank:
             if C in masks_of:
                 continue
             given = channel_map.get(C) if channel_map else None
-            masks = [int(m) for m in given] if given is not None else _default_masks(C, K)
+            if given is not None:
+                try:
+                    form, given = _mix_entry(given)
+                    why = _weights_error(C, K, given) if form == "weights" else None
+                except ValueError as e:
+                    form, why = "weights", str(e)
+                if form == "weights":
+                    if why:
+                        raise ValueError(f"{who}: channel_map[{C}], which file {idx[0]} needs, is not valid: {why}")
+                    masks_of[C] = given
+                    continue
+            masks = given if given is not None else _default_masks(C, K)
+            if masks is None and downmix is not None:
+                masks_of[C] = _downmix(C, K, downmix)
+                if masks_of[C] is not None:
+                    continue
             if masks is None:
                 raise ValueError(f"{who}: file {idx[0]} has {C} channels and there is no default mix of {C} channels "
                                  f"to {K}: give channel_map[{C}]")
@@ -702,6 +830,10 @@ class FlacMixBank:
         def check(fmt):
             if fmt != flacgpu.SAMPLE_I32:
                 return
+            for bank, masks in self._groups:
+                if _is_weights(masks):
+                    raise ValueError(f"{who}: int32 crops of {bank.channels}-channel files, which are mixed by weights: "
+                                     f"a weighted sample has no integer value to deliver")
             if len(self.bits) > 1:
                 raise ValueError(f"{who}: int32 crops of a bank that holds depths {self.bits}: the integers would have "
                                  f"different scales")

@@ -374,6 +374,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_features_f32_host": (I32, [P, U64, P, P, U64, U64, P, ctypes.POINTER(U64)]),
         "flacgpu_decode_windows_device_features": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, U32, P, U32, U32,
                                                          P, P, P, P, P, P, P]),
+        "flacgpu_mix_weights_valid": (I32, [U32, U32, P, U32]),
+        "flacgpu_mix_weights_f32_host": (I32, [P, U64, U32, U32, U32, P, P]),
+        "flacgpu_decode_windows_device_to": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, P, P, P, P, P, P]),
         "flacgpu_pcm_from_elements_device": (I32, [P, U32, P, P, P, U32, U32, P, P, U64, P, P]),
         "flacgpu_pcm_from_elements_host": (I32, [P, U64, U64, U32, U32, U32, U32, P, SZ, ctypes.POINTER(U64)]),
     }
@@ -417,6 +420,7 @@ def exported_symbols() -> list:
         "flacgpu_resample_filter", "flacgpu_resample_f32_host", "flacgpu_decode_windows_device_resample",
         "flacgpu_features_table", "flacgpu_features_f32_host", "flacgpu_decode_windows_device_features",
         "flacgpu_pcm_from_elements_device", "flacgpu_pcm_from_elements_host",
+        "flacgpu_mix_weights_valid", "flacgpu_mix_weights_f32_host", "flacgpu_decode_windows_device_to",
     ]
 
 
@@ -672,6 +676,52 @@ def features_f32_host(x, n_fft: int, hop: int, start: int, frames: int, filters=
     return y, got.value
 
 
+class WindowDelivery(ctypes.Structure):
+    """flacgpu_window_delivery: how flacgpu_decode_windows_device_to delivers."""
+    _fields_ = [("size", ctypes.c_uint32), ("sample_format", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("out_channels", ctypes.c_uint32), ("channel_masks", ctypes.c_void_p), ("channel_weights", ctypes.c_void_p),
+                ("src_rate", ctypes.c_uint32), ("dst_rate", ctypes.c_uint32), ("features", ctypes.c_void_p),
+                ("filters", ctypes.c_void_p)]
+
+
+def _weights(weights, who: str):
+    """A weight matrix as a contiguous float32 [K, C] numpy array."""
+    import numpy as np
+
+    w = np.ascontiguousarray(weights, dtype=np.float32)
+    if w.ndim != 2 or w.size == 0:
+        raise ValueError(f"{who}: the weights are K rows of C numbers")
+    return w
+
+
+def mix_weights_valid(weights, sample_format: int = SAMPLE_F32) -> bool:
+    """flacgpu_mix_weights_valid (host only): whether the [K, C] matrix is one the weighted channel
+    mix takes for sample_format: K and C in 1..8, a float format, every weight 0 or 2^-32 <= |w| <= 2^32."""
+    w = _weights(weights, "mix_weights_valid")
+    return bool(load_library().flacgpu_mix_weights_valid(w.shape[1], w.shape[0], w.ctypes.data, int(sample_format)))
+
+
+def mix_weights_f32_host(samples, bits: int, weights):
+    """flacgpu_mix_weights_f32_host (host only): the weighted mix of the integer samples [n, C] of
+    `bits` bits by the [K, C] matrix as a float32 numpy array [n, K].  The statement of the rule the
+    device follows bit for bit, for callers and tests: not a decode path."""
+    import numpy as np
+
+    w = _weights(weights, "mix_weights_f32_host")
+    x = np.asarray(samples)
+    if x.ndim != 2 or x.shape[1] != w.shape[1] or x.dtype.kind not in "iu":
+        raise ValueError("mix_weights_f32_host: samples is an integer array [n, C], C the columns of the weights")
+    lo, hi = -(1 << (int(bits) - 1)), (1 << (int(bits) - 1)) - 1
+    if x.size and (int(x.min()) < lo or int(x.max()) > hi):
+        raise ValueError(f"mix_weights_f32_host: a sample is outside {bits} bits")
+    x = np.ascontiguousarray(x, dtype=np.int32)
+    y = np.zeros((max(len(x), 1), w.shape[0]), dtype=np.float32)[:len(x)]
+    _check(load_library().flacgpu_mix_weights_f32_host(x.ctypes.data if len(x) else None, len(x), w.shape[1], int(bits),
+                                                       w.shape[0], w.ctypes.data, y.ctypes.data if len(x) else None),
+           "mix_weights_f32_host")
+    return y
+
+
 def pcm_from_elements_host(x, bits: int, sample_format: int, planar: bool = True, samples: Optional[int] = None,
                            plane_stride: Optional[int] = None):
     """flacgpu_pcm_from_elements_host (host only): (PCM bytes rounded up to 4 with zero pads, clipped)
@@ -857,6 +907,44 @@ class _DecodeOps:
             (ctypes.c_uint8 * max(len(masks), 1))(*masks) if masks is not None else None, int(src_rate), int(dst_rate),
             ctypes.byref(ft), f.ctypes.data if f is not None else None, d_out, _u64s(out_offsets), _u64s(out_caps), d_results,
             _stream(stream)), "decode_windows_device_features")
+
+    def decode_windows_device_to(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int, d_frame_bytes: int,
+                                 d_index_results: int, d_frame_first_sample: int, d_stream_samples: int,
+                                 windows: Sequence, sample_format: int, flags: int, d_out: int,
+                                 out_offsets: Sequence[int], out_caps: Sequence[int], d_results: int,
+                                 channel_masks: Optional[Sequence[int]] = None, channel_weights=None, src_rate: int = 0,
+                                 dst_rate: int = 0, n_fft: Optional[int] = None, hop: Optional[int] = None, filters=None,
+                                 stream: Optional[int] = None) -> None:
+        """flacgpu_decode_windows_device_to: every window delivery through one call.  channel_masks (K
+        masks) or channel_weights (K rows of C numbers: output channel k is the fused multiply-add
+        chain of row k over the source channels), not both, or neither for the context's channels;
+        src_rate and dst_rate as decode_windows_device_resample, 0 and 0 for no rate change; n_fft and
+        hop (and filters) as decode_windows_device_features, windows then being [(stream, start,
+        frames)] and flags 0.  Without channel_weights it is the existing call of those arguments."""
+        masks = None if channel_masks is None else [int(m) for m in channel_masks]
+        if masks is not None and (not 1 <= len(masks) <= 8 or any(not 0 <= m <= 255 for m in masks)):
+            raise FlacGpuError(-2, "decode_windows_device_to: 1 to 8 channel masks, each in 0..255")
+        w = None if channel_weights is None else _weights(channel_weights, "decode_windows_device_to")
+        if w is not None and w.shape[1] != self.channels:  # the library reads K * C floats: it cannot see the rows' length
+            raise FlacGpuError(-2, f"decode_windows_device_to: rows of {w.shape[1]} weights on a context of {self.channels} channels")
+        for name, r in (("src_rate", src_rate), ("dst_rate", dst_rate)):
+            if not 0 <= int(r) <= 0xFFFFFFFF:
+                raise FlacGpuError(-2, f"decode_windows_device_to: {name} is not in 0..2^32-1")
+        ft = f = None
+        if n_fft is not None:
+            ft, f, _ = features_params(n_fft, hop, filters)
+        c_masks = (ctypes.c_uint8 * len(masks))(*masks) if masks is not None else None
+        how = WindowDelivery(ctypes.sizeof(WindowDelivery), int(sample_format), int(flags),
+                             len(masks) if masks is not None else (w.shape[0] if w is not None else 0),
+                             ctypes.cast(c_masks, ctypes.c_void_p) if c_masks is not None else None,
+                             w.ctypes.data if w is not None else None, int(src_rate), int(dst_rate),
+                             ctypes.cast(ctypes.pointer(ft), ctypes.c_void_p) if ft is not None else None,
+                             f.ctypes.data if f is not None else None)
+        _check(self.lib.flacgpu_decode_windows_device_to(
+            *self._window_args(d_data, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                               d_stream_samples, windows),
+            ctypes.byref(how), d_out, _u64s(out_offsets), _u64s(out_caps), d_results, _stream(stream)),
+            "decode_windows_device_to")
 
     def decode_files_windows(self, flacs: Sequence[bytes], windows: Sequence, guard: int = 0,
                              pcm_caps: Optional[Sequence[int]] = None):
