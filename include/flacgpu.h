@@ -856,6 +856,46 @@ int flacgpu_decode_windows_device_to(flacgpu_ctx *ctx, const uint8_t *d_data,
                                      const flacgpu_window_delivery *how,
                                      void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
                                      flacgpu_window_result *d_results, void *hip_stream);
+/* The levels of sample windows: nothing is delivered but three numbers a block and channel.  A
+ * stream's samples are the sign-extended integers x[t][c] of its depth.  The window [start, start +
+ * count), clipped to n samples as in flacgpu_decode_windows_device, is cut by `hop` into ceil(n / hop)
+ * blocks: block j holds the window's samples [j * hop, min((j + 1) * hop, n)), positions relative to
+ * the window's start, the last block perhaps short.  Of every block and channel:
+ *   peak    max |x| as uint32 (at 32 bits |-2^31| = 2^31 fits);
+ *   sum     the sum of x as int64, exact (|sum| < 2^62 for hop < 2^31);
+ *   energy  the sum of x^2 as an exact unsigned 128-bit integer (below 2^93), delivered as the double
+ *           nearest to it, ties to even: the ONE rounding of the rule.  Below 2^64 it is the
+ *           conversion of the integer; above, the integer is shifted right by s = its bit length - 64
+ *           with every bit shifted out ORed into bit 0 (a sticky bit, 11 bits below the rounding
+ *           position), converted to double (round to nearest-even) and scaled by 2^s (exact).
+ *           Python's float(int) rounds the same way.
+ * Record out_offsets[w] + j * C + c of each of d_peak, d_sum and d_energy (device memory, aligned to
+ * their element) is block j, channel c of window w; out_offsets and out_caps count records.  Status
+ * FLACGPU_WINDOW_TOO_SMALL where C * ceil(n / hop) > out_caps[w], decided before anything is decoded,
+ * and nothing is written; a window with n = 0 is OK and writes nothing; n_samples of a result counts
+ * the samples measured.  Everything else -- the tables, BAD_INDEX and BAD_FRAME (which write
+ * nothing), windows that share streams and overlap, the one wait for hip_stream, the chunks of
+ * max_frames_per_call, what is timed -- is as in flacgpu_decode_windows_device.  The accumulators are
+ * integers and partial results combine exactly, so the bits do not depend on how the work is cut.
+ * FLACGPU_ERR_INVALID_INPUT before any device work: hop == 0 or hop >= 2^31, a NULL output array,
+ * one not aligned to its element size, out_offsets[w] + out_caps[w] passing 64 bits, and every
+ * argument error of flacgpu_decode_windows_device.
+ * flacgpu_levels_host (host only): the rule over n interleaved samples[n][channels] (any int32 is a
+ * sample), ceil(n / hop) * channels records to each array; FLACGPU_ERR_INVALID_INPUT for hop == 0 or
+ * >= 2^31, channels == 0, n > 2^40, or a NULL array with n > 0.  A statement of the rule for callers
+ * and tests, bit for bit what the device writes; it is NOT a decode path. */
+int flacgpu_levels_windows_device(flacgpu_ctx *ctx, const uint8_t *d_data,
+                                  uint32_t n_streams, const uint64_t *table_first,
+                                  const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                  const flacgpu_index_result *d_index_results,
+                                  const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
+                                  uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
+                                  const uint64_t *window_count,
+                                  uint32_t hop, uint32_t *d_peak, int64_t *d_sum, double *d_energy,
+                                  const uint64_t *out_offsets, const uint64_t *out_caps,
+                                  flacgpu_window_result *d_results, void *hip_stream);
+int flacgpu_levels_host(const int32_t *samples, uint64_t n, uint32_t channels, uint32_t hop, uint32_t *peak,
+                        int64_t *sum, double *energy);
 /* Windows of whole files in host memory: window w is samples [window_start[w], + window_count[w])
  * of file window_file[w] (< n_files), delivered to pcm_out[w] (capacity pcm_cap[w]) with
  * n_samples[w].  Metadata is parsed on the host as in flacgpu_decode_files; the good files' frames

@@ -79,6 +79,14 @@ flacgpu.features_f32_host bit for bit, and the interior frames of the two paths 
 
     python tools/decode_rate.py --legs features --features-out profiles/decode_features_rate.json
 
+The levels leg (--levels-out; opt-in, not part of `all`) takes the resample leg's files and windows and
+measures them without delivering them: flacgpu_levels_windows_device at hop 441 and at hop = the
+window, against flacgpu_decode_windows_device_as (I32, planar) followed by torch's abs().amax, sum
+and double().square().sum a block.  Medians of --repeats alternated runs, both sides, between events
+on the stream; the records of two windows are first compared with numpy over the PCM.
+
+    python tools/decode_rate.py --legs levels --levels-out profiles/decode_levels_rate.json
+
 The write leg (--write-out; opt-in, not part of `all`) takes the resample leg's PCM as 64 float32
 [channel, time] tensors on the device and builds a bank of them at 16 bits two ways, alternated in one
 process: FlacBank.from_tensors, and the route a caller had before it -- the tensors scaled, rounded
@@ -887,6 +895,74 @@ def resample_rate(n_files: int, frames_each: int, window: int, warmup: int, repe
     return res
 
 
+def levels_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: int) -> dict:
+    """The resample leg's files and windows measured, not delivered: flacgpu_levels_windows_device at
+    hop 441 and at hop = the window, against flacgpu_decode_windows_device_as (I32, planar) followed
+    by torch's abs().amax, sum and double().square().sum over the tensor reshaped to blocks (the short
+    last block of hop 441 by a second set of the three reductions over its slice).  Both are timed
+    between two events on the stream, alternated; the records of window 0 and of the last window
+    are compared with numpy over the PCM before anything is timed."""
+    import numpy as np
+    import torch
+
+    import flacgpu
+
+    with resident_windows(n_files, frames_each, window) as r:
+        enc, ch, bits, dev, pcm, n_each, st, crops = r.enc, r.ch, r.bits, r.dev, r.pcm, r.n_each, r.st, r.crops
+        tables, d_wres, start = r.tables, r.d_wres, r.start
+        r.positions()
+        x = torch.zeros((n_files, ch, window), dtype=torch.int32, device=dev)
+        res = {"files": n_files, "frames_per_file": frames_each, "channels": ch, "bits": bits, "window_samples": window,
+               "window_start": start, "warmup": warmup, "repeats": repeats,
+               "comparator": "decode_windows_device_as (I32, planar), then torch abs().amax, sum, double().square().sum a block"}
+        v = np.frombuffer(pcm, dtype=np.int16).reshape(n_each, ch)[start:start + window].astype(np.int64)
+        for hop in (441, window):
+            blocks = (window + hop - 1) // hop
+            whole = window // hop
+            peak = torch.zeros((n_files, blocks, ch), dtype=torch.int32, device=dev)
+            total = torch.zeros((n_files, blocks, ch), dtype=torch.int64, device=dev)
+            energy = torch.zeros((n_files, blocks, ch), dtype=torch.float64, device=dev)
+
+            def levels():
+                enc.levels_windows_device(*tables, crops, hop, peak.data_ptr(), total.data_ptr(), energy.data_ptr(),
+                                          [i * blocks * ch for i in range(n_files)], [blocks * ch] * n_files, d_wres.data_ptr(),
+                                          stream=st)
+
+            def as_then_torch():
+                enc.decode_windows_device_as(*tables, crops, flacgpu.SAMPLE_I32, flacgpu.DELIVER_PLANAR, x.data_ptr(),
+                                             [i * ch * window for i in range(n_files)], [ch * window] * n_files, d_wres.data_ptr(),
+                                             stream=st)
+                out = []
+                for part in ((x[:, :, :whole * hop].reshape(n_files, ch, whole, hop),) +
+                             ((x[:, :, whole * hop:].unsqueeze(2),) if blocks > whole else ())):
+                    out.append((part.abs().amax(dim=3), part.sum(dim=3), part.double().square().sum(dim=3)))
+                return out
+
+            legs = {"levels": levels, "as_i32_then_torch": as_then_torch}
+            for _ in range(warmup):
+                for fn in legs.values():
+                    fn()
+                    enc.sync_check(st)
+                    assert r.results() == [(0, window)] * n_files
+            levels()
+            enc.sync_check(st)
+            at = np.arange(0, window, hop)
+            want = (np.maximum.reduceat(np.abs(v), at, axis=0), np.add.reduceat(v, at, axis=0),
+                    np.add.reduceat(v * v, at, axis=0).astype(np.float64))  # 16 bits: the squares' sums are exact in int64
+            for i in (0, n_files - 1):
+                assert (peak[i].cpu().numpy() == want[0]).all() and (total[i].cpu().numpy() == want[1]).all()
+                assert (energy[i].cpu().numpy() == want[2]).all(), "the device differs from the rule"
+            ms = {k: [] for k in legs}
+            for _ in range(repeats):  # alternated
+                for k, fn in legs.items():
+                    ms[k].append(event_ms(fn))
+            leg = {k: summary(ms[k], keep=True) for k in legs}
+            leg["blocks_per_window"] = blocks
+            leg["levels"]["x_as_i32_then_torch"] = leg["as_i32_then_torch"]["ms_median"] / leg["levels"]["ms_median"]
+            res[f"hop_{hop}"] = leg
+    return res
+
+
 def features_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: int, dst_rate: int = 48000) -> dict:
     import numpy as np
     import torch
@@ -1098,10 +1174,11 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix", "resample", "features", "write", "downmix"),
+    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix", "resample", "features", "write", "downmix", "levels"),
                     default="all")
     ap.add_argument("--write-out", default=os.path.join(ROOT, "profiles", "bank_write_rate.json"))
     ap.add_argument("--downmix-out", default=os.path.join(ROOT, "profiles", "decode_downmix_rate.json"))
+    ap.add_argument("--levels-out", default=os.path.join(ROOT, "profiles", "decode_levels_rate.json"))
     ap.add_argument("--resample-out", default=os.path.join(ROOT, "profiles", "decode_resample_rate.json"))
     ap.add_argument("--features-out", default=os.path.join(ROOT, "profiles", "decode_features_rate.json"))
     ap.add_argument("--mix-out", default=os.path.join(ROOT, "profiles", "decode_mix_rate.json"))
@@ -1142,6 +1219,12 @@ def main():
         with open(a.mix_out, "w") as f:
             json.dump(mr, f, indent=1)
             f.write("\n")
+        return
+    if a.legs == "levels":  # opt-in: `all` leaves it out
+        lr = {"c2": levels_rate(a.files, a.frames // a.files, a.window, a.warmup, a.repeats)}
+        print(json.dumps({"levels": lr}), flush=True)
+        with open(a.levels_out, "w") as f:
+            json.dump(lr, f, indent=1)
         return
     if a.legs == "resample":  # opt-in: `all` leaves it out
         rr = {"c2": resample_rate(a.files, a.frames // a.files, a.window, a.warmup, a.repeats)}

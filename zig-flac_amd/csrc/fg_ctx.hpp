@@ -266,8 +266,8 @@ hipError_t launch_positions(const uint8_t *data, const window::PosStream *d_stre
                             const uint64_t *f_off, const uint32_t *f_bytes, const idx::IndexResult *ires, uint64_t *pos,
                             uint64_t *totals, hipStream_t st);
 hipError_t launch_window_cover(const window::WindowArg *args, const idx::IndexResult *ires, const uint64_t *pos,
-                               const uint64_t *totals, uint32_t unit, uint32_t flags, window::Cover *recs, uint32_t n,
-                               hipStream_t st);
+                               const uint64_t *totals, uint32_t unit, uint32_t flags, uint32_t hop, window::Cover *recs,
+                               uint32_t n, hipStream_t st);
 hipError_t launch_window_init(const window::Cover *recs, streams::StreamResult *res, uint64_t *carried, uint32_t n,
                               hipStream_t st);
 hipError_t launch_window_copy(const window::Cover *recs, const streams::StreamResult *res, const uint8_t *scratch,
@@ -279,6 +279,11 @@ hipError_t launch_window_elements(const window::Cover *recs, const streams::Stre
                                   const deliver::Delivery &dv, uint32_t n, uint64_t max_samples, hipStream_t st);
 hipError_t launch_window_results(const window::Cover *recs, const streams::StreamResult *res, window::WindowResult *out,
                                  uint32_t n, hipStream_t st);
+// fg_levels.hip: k_window_levels in place of k_window_copy, then k_levels_fold where blocks have several parts
+hipError_t launch_window_levels(const window::Cover *recs, const streams::StreamResult *res, const uint8_t *scratch,
+                                const uint64_t *src_base, const uint64_t *dst_off, const uint64_t *part_base, void *parts,
+                                uint32_t *peak, int64_t *sum, double *energy, uint32_t hop, uint32_t C, uint32_t B, uint32_t n,
+                                uint64_t max_samples, hipStream_t st);
 // fg_resample.hip: the cover and the delivery of windows stated at another sample rate
 hipError_t launch_resample_cover(const window::WindowArg *args, const idx::IndexResult *ires, const uint64_t *pos,
                                  const uint64_t *totals, const resample::Ratio &rt, uint32_t unit, uint32_t flags,

@@ -16,6 +16,7 @@
 #include "fg_features.hpp"
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
+#include "fg_levels.hpp"
 #include "fg_md5_host.hpp"
 #include "fg_resample.hpp"
 
@@ -355,6 +356,25 @@ int flacgpu_mix_weights_f32_host(const int32_t *samples, uint64_t n, uint32_t ch
                 acc = deliver::mixw_step(acc, weights[(size_t)k * channels + c], samples[t * channels + c], bits);
             y[t * out_channels + k] = acc;
         }
+    return FLACGPU_OK;
+}
+
+int flacgpu_levels_host(const int32_t *samples, uint64_t n, uint32_t channels, uint32_t hop, uint32_t *peak, int64_t *sum,
+                        double *energy) {
+    if (hop == 0u || hop > levels::kMaxHop || channels == 0u || n > (1ull << 40)) return FLACGPU_ERR_INVALID_INPUT;
+    if (n == 0) return FLACGPU_OK;
+    if (!samples || !peak || !sum || !energy) return FLACGPU_ERR_INVALID_INPUT;
+    const uint64_t nb = levels::n_blocks(n, hop);
+    for (uint64_t j = 0; j < nb; j++) {
+        const uint64_t t0 = j * hop, len = levels::block_len(n, hop, j);
+        for (uint32_t c = 0; c < channels; c++) {
+            levels::Acc a = levels::acc_zero();
+            for (uint64_t t = t0; t < t0 + len; t++) levels::acc_add(a, samples[t * channels + c]);
+            peak[j * channels + c] = a.peak;
+            sum[j * channels + c] = a.sum;
+            energy[j * channels + c] = levels::acc_energy(a);
+        }
+    }
     return FLACGPU_OK;
 }
 

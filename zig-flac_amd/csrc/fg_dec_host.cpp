@@ -7,7 +7,8 @@
 // over resident tables -- as PCM bytes or as tensor elements (fg_deliver.hpp) -- and the device
 // side of flacgpu_decode_files_windows; and the same windows stated and delivered at another
 // sample rate (fg_resample.hpp, fg_resample.hip), and as short-time power spectra and filter-bank
-// rows over that delivery (fg_features.hpp, fg_features.hip).  The host-only side (metadata, the host index,
+// rows over that delivery (fg_features.hpp, fg_features.hip); and the same windows measured, not
+// delivered: peak, sum and energy a block (fg_levels.hpp, fg_levels.hip).  The host-only side (metadata, the host index,
 // flacgpu_decode_file / _files) is fg_dec_api.cpp.
 #include <hip/hip_runtime.h>
 
@@ -24,6 +25,7 @@
 #include "fg_features.hpp"
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
+#include "fg_levels.hpp"
 #include "fg_resample.hpp"
 #include "fg_streams.hpp"
 #include "fg_window.hpp"
@@ -456,6 +458,15 @@ int mix_weights(flacgpu_ctx *c, uint32_t K, uint32_t C, const float *W, const fl
     return FLACGPU_OK;
 }
 
+// A window call that measures levels (fg_levels.hpp) in place of delivering: the hop and the three
+// arrays of records.
+struct Levels {
+    uint32_t hop;
+    uint32_t *d_peak;
+    int64_t *d_sum;
+    double *d_energy;
+};
+
 // The windows of a call between its two halves: as uploaded, and their cover records on both sides.
 struct WindowsCall {
     uint32_t n = 0;
@@ -468,11 +479,12 @@ struct WindowsCall {
 // covering frames, and the host waits for st ONCE to read the records.  caps[w]: the bytes of
 // window w's destination, or its elements where dv converts; TOO_SMALL is deliver::too_small's.
 // With `rs` the windows are stated in output samples of its ratio and k_resample_cover covers the
-// source samples their filter needs.
+// source samples their filter needs.  With `lv` caps[w] counts records of a block and channel and
+// TOO_SMALL is levels::too_small's.
 int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexResult *d_ires, const uint64_t *d_pos,
                   const uint64_t *d_totals, uint32_t n, const uint32_t *window_stream, const uint64_t *window_start,
                   const uint64_t *window_count, const uint64_t *caps, const deliver::Delivery &dv, WindowsCall &wc,
-                  hipStream_t st, const Resampling *rs = nullptr) {
+                  hipStream_t st, const Resampling *rs = nullptr, const Levels *lv = nullptr) {
     IdxScratch *x = idx_scratch(c);
     if (!x) return FLACGPU_ERR_OUT_OF_MEMORY;
     std::vector<window::WindowArg> args;
@@ -494,9 +506,9 @@ int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexR
     HIPCHK(hipMemcpyAsync(wc.d_args, args.data(), (uint64_t)n * sizeof(window::WindowArg), hipMemcpyHostToDevice, st));
     {
         Timed t(c, FLACGPU_K_SCAN, st);
-        const uint32_t unit = dv.format == deliver::SAMPLE_BYTES ? dv.channels * dv.sample_bytes : dv.out_channels;
+        const uint32_t unit = lv ? dv.channels : dv.format == deliver::SAMPLE_BYTES ? dv.channels * dv.sample_bytes : dv.out_channels;
         if (rs) HIPCHK(launch_resample_cover(wc.d_args, d_ires, d_pos, d_totals, rs->rt, unit, dv.flags, wc.d_recs, n, st));
-        else HIPCHK(launch_window_cover(wc.d_args, d_ires, d_pos, d_totals, unit, dv.flags, wc.d_recs, n, st));
+        else HIPCHK(launch_window_cover(wc.d_args, d_ires, d_pos, d_totals, unit, dv.flags, lv ? lv->hop : 0u, wc.d_recs, n, st));
     }
     HIPCHK(hipMemcpyAsync(wc.recs.data(), wc.d_recs, (uint64_t)n * sizeof(window::Cover), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
@@ -511,21 +523,27 @@ int windows_cover(flacgpu_ctx *c, const uint64_t *table_first, const idx::IndexR
 // instantiation where dv mixes: dv.out_channels channels a sample) writes its elements from element
 // out_offsets[w] of d_pcm_out on -- and k_window_results writes d_results.  With `rs` a record's
 // n_samples counts output samples, its cover is that of the filter's source range, and
-// k_window_resample stands in place of k_window_elements.
+// k_window_resample stands in place of k_window_elements.  With `lv` nothing is delivered:
+// k_window_levels stands in place of k_window_copy and writes the records of every clean window's
+// blocks from record out_offsets[w] of lv's arrays on; where a block is longer than a tile, window w
+// has levels::partial_records(n, ...) Acc of the chunk loop's scratch for its parts' exact partial
+// results, which k_levels_fold sums.
 int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_first, const uint64_t *d_foff,
                    const uint32_t *d_fbytes, const WindowsCall &wc, const uint32_t *window_stream,
                    const uint64_t *window_count, const deliver::Delivery &dv, uint8_t *d_pcm_out, const uint64_t *out_offsets,
-                   window::WindowResult *d_results, hipStream_t st, const Resampling *rs = nullptr) {
+                   window::WindowResult *d_results, hipStream_t st, const Resampling *rs = nullptr, const Levels *lv = nullptr) {
     IdxScratch *x = c->idx.get();
     const uint32_t n = wc.n;
     const uint64_t per = (uint64_t)c->fmt.channels * c->fmt.bytes_per_sample;
-    std::vector<uint64_t> frames, host;  // host: scratch base, scratch cap, table first, destination
+    std::vector<uint64_t> frames, host;  // host: scratch base, scratch cap, table first, destination(, lv: first partial)
     const bool convert = dv.format != deliver::SAMPLE_BYTES;
+    const levels::Plan pl = levels::plan(lv ? lv->hop : 1u, (uint32_t)per);
+    uint64_t n_parts = 0, max_measured = 0;  // lv: the partial records of all windows; the most samples a window measures
     uint64_t whole = 0, max_bytes = 0;  // whole: the end of the last region
     uint64_t max_written = 0;           // convert: the most samples a window writes, its padding included
     try {
         frames.assign(n, 0);
-        host.assign(4u * (uint64_t)n, 0);
+        host.assign((lv ? 5u : 4u) * (uint64_t)n, 0);
     } catch (...) {
         return FLACGPU_ERR_OUT_OF_MEMORY;
     }
@@ -544,17 +562,29 @@ int windows_decode(flacgpu_ctx *c, const uint8_t *d_data, const uint64_t *table_
         whole += (r.span * per + 15u) & ~(uint64_t)15u;
         if (whole > (1ull << 47)) return FLACGPU_ERR_OUT_OF_MEMORY;
         max_bytes = std::max(max_bytes, r.n_samples * per);
+        if (lv) {
+            host[4u * (uint64_t)n + w] = n_parts;
+            n_parts += levels::partial_records(r.n_samples, pl, c->fmt.channels);
+            max_measured = std::max(max_measured, r.n_samples);
+        }
     }
     HIPCHK(x->win_pcm.grow(whole + 16u, &st));
     ChunkRun run;
     streams::StreamResult *sres = nullptr;
-    int rc = run.prepare(c, frames, host, x->win, [&](Carve &v) { v.take(n, sres); }, st);
+    levels::Acc *d_parts = nullptr;
+    int rc = run.prepare(c, frames, host, x->win, [&](Carve &v) {
+        v.take(n, sres);
+        if (lv) v.take(n_parts, d_parts);
+    }, st);
     if (rc) return rc;
     HIPCHK(launch_window_init(wc.d_recs, sres, run.carried, n, st));
     rc = run.run(c, d_data, d_foff, d_fbytes, x->win_pcm.get(), whole, sres, st);
     if (rc) return rc;
     const uint64_t *d_base = run.row(0), *d_dst = run.row(3);
-    if (rs)
+    if (lv)
+        HIPCHK(launch_window_levels(wc.d_recs, sres, x->win_pcm.get(), d_base, d_dst, run.row(4), d_parts, lv->d_peak, lv->d_sum,
+                                    lv->d_energy, lv->hop, c->fmt.channels, c->fmt.bytes_per_sample, n, max_measured, st));
+    else if (rs)
         HIPCHK(launch_window_resample(wc.d_recs, sres, wc.d_args, rs->d_totals, x->win_pcm.get(), d_base, d_pcm_out, d_dst, dv, rs->rt,
                                       rs->d_coeffs, n, max_written, st));
     else if (convert)
@@ -750,11 +780,11 @@ int windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, co
                    const uint32_t *window_stream, const uint64_t *window_start, const uint64_t *window_count,
                    uint32_t sample_format, uint32_t flags, uint32_t out_channels, const uint8_t *masks, void *d_out,
                    const uint64_t *offsets, const uint64_t *caps, flacgpu_window_result *d_results, void *hip_stream,
-                   uint32_t src_rate = 0, uint32_t dst_rate = 0, const float *weights = nullptr) {
+                   uint32_t src_rate = 0, uint32_t dst_rate = 0, const float *weights = nullptr, const Levels *lv = nullptr) {
     if (!c || !d_data || !table_first || !d_frame_offsets || !d_frame_bytes || !d_index_results || !d_frame_first_sample ||
         !d_stream_samples || n_windows > 65535u)
         return FLACGPU_ERR_INVALID_INPUT;
-    if (n_windows && (!window_stream || !window_start || !window_count || !d_out || !offsets || !caps || !d_results))
+    if (n_windows && (!window_stream || !window_start || !window_count || (!d_out && !lv) || !offsets || !caps || !d_results))
         return FLACGPU_ERR_INVALID_INPUT;
     for (uint32_t w = 0; w < n_windows; w++)
         if (window_stream[w] >= n_streams || offsets[w] + caps[w] < offsets[w]) return FLACGPU_ERR_INVALID_INPUT;
@@ -787,13 +817,30 @@ int windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, co
     }
     WindowsCall wc;
     rc = windows_cover(c, table_first, (const idx::IndexResult *)d_index_results, d_frame_first_sample, d_stream_samples,
-                       n_windows, window_stream, window_start, window_count, caps, dv, wc, st, src_rate ? &rs : nullptr);
+                       n_windows, window_stream, window_start, window_count, caps, dv, wc, st, src_rate ? &rs : nullptr, lv);
     if (rc) return rc;
     return windows_decode(c, d_data, table_first, d_frame_offsets, d_frame_bytes, wc, window_stream, window_count, dv,
-                          (uint8_t *)d_out, offsets, (window::WindowResult *)d_results, st, src_rate ? &rs : nullptr);
+                          (uint8_t *)d_out, offsets, (window::WindowResult *)d_results, st, src_rate ? &rs : nullptr, lv);
 }
 
 }  // namespace
+
+int flacgpu_levels_windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
+                                  const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                  const flacgpu_index_result *d_index_results, const uint64_t *d_frame_first_sample,
+                                  const uint64_t *d_stream_samples, uint32_t n_windows, const uint32_t *window_stream,
+                                  const uint64_t *window_start, const uint64_t *window_count, uint32_t hop, uint32_t *d_peak,
+                                  int64_t *d_sum, double *d_energy, const uint64_t *out_offsets, const uint64_t *out_caps,
+                                  flacgpu_window_result *d_results, void *hip_stream) {
+    if (!c || hop == 0u || hop > levels::kMaxHop || !d_peak || !d_sum || !d_energy || ((uintptr_t)d_peak & 3u) ||
+        ((uintptr_t)d_sum & 7u) || ((uintptr_t)d_energy & 7u))
+        return FLACGPU_ERR_INVALID_INPUT;
+    const Levels lv{hop, d_peak, d_sum, d_energy};
+    return windows_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results,
+                          d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
+                          deliver::SAMPLE_BYTES, 0u, 0u, nullptr, nullptr, out_offsets, out_caps, d_results, hip_stream, 0u, 0u,
+                          nullptr, &lv);
+}
 
 int flacgpu_decode_windows_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
                                   const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,

@@ -28,6 +28,7 @@
 #include "fg_common.hpp"
 #include "fg_deliver.hpp"
 #include "fg_index.hpp"
+#include "fg_levels.hpp"
 #include "fg_streams.hpp"
 #include "fg_window.hpp"
 
@@ -87,8 +88,8 @@ __global__ void __launch_bounds__(256) k_pos_scan(const PosStream *streams, cons
 }
 
 __global__ void __launch_bounds__(256) k_window_cover(const WindowArg *args, const idx::IndexResult *ires, const uint64_t *pos,
-                                                       const uint64_t *totals, uint32_t unit, uint32_t flags, Cover *recs,
-                                                       uint32_t n) {
+                                                       const uint64_t *totals, uint32_t unit, uint32_t flags, uint32_t hop,
+                                                       Cover *recs, uint32_t n) {
     const uint32_t w = blockIdx.x * 256u + threadIdx.x;
     if (w >= n) return;
     const WindowArg a = args[w];
@@ -100,7 +101,9 @@ __global__ void __launch_bounds__(256) k_window_cover(const WindowArg *args, con
     } else {
         c = cover(pos + a.table_first, r.n_frames, totals[a.stream], a.start, a.count);
         // the byte copy: unit = per, no flags, so n_samples * per > cap with no product to overflow
-        if (deliver::too_small(c.n_samples, a.count, flags, a.cap, unit)) c.status = WIN_TOO_SMALL;
+        // the levels (hop != 0): unit = the channels, the capacity in records of a block and channel
+        if (hop ? levels::too_small(c.n_samples, hop, unit, a.cap) : deliver::too_small(c.n_samples, a.count, flags, a.cap, unit))
+            c.status = WIN_TOO_SMALL;
     }
     recs[w] = c;
 }
@@ -295,11 +298,13 @@ hipError_t launch_positions(const uint8_t *data, const PosStream *d_streams, uin
     return hipGetLastError();
 }
 
-// unit, flags: the capacity rule's (deliver::too_small); the byte copy passes per and 0
+// unit, flags: the capacity rule's (deliver::too_small); the byte copy passes per and 0.  hop != 0:
+// the capacity rule of the levels (levels::too_small) with unit = the channels
 hipError_t launch_window_cover(const WindowArg *args, const idx::IndexResult *ires, const uint64_t *pos, const uint64_t *totals,
-                               uint32_t unit, uint32_t flags, Cover *recs, uint32_t n, hipStream_t st) {
+                               uint32_t unit, uint32_t flags, uint32_t hop, Cover *recs, uint32_t n, hipStream_t st) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_window_cover, dim3((n + 255u) / 256u), dim3(256), 0, st, args, ires, pos, totals, unit, flags, recs, n);
+    hipLaunchKernelGGL(k_window_cover, dim3((n + 255u) / 256u), dim3(256), 0, st, args, ires, pos, totals, unit, flags, hop,
+                       recs, n);
     return hipGetLastError();
 }
 

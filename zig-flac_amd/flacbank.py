@@ -9,7 +9,8 @@ there is no CPU path.  A bank takes no locks: one bank per thread, like a contex
 the crops are stated and delivered at that sample rate: those of files at another rate go through
 flacgpu_decode_windows_device_resample, one call per source rate.  FlacBank.from_tensors builds the
 same bank from tensors on the device (flacgpu_pcm_from_elements_device, flacgpu_encode_plan_device);
-file_bytes writes a bank's file back out as a .flac.
+file_bytes writes a bank's file back out as a .flac.  FlacBank.levels and crop_levels measure instead
+of delivering: peak, sum and energy of every block of a hop (flacgpu_levels_windows_device).
 
 FlacBank holds files of one channel count and depth.  FlacMixBank holds any, as one FlacBank per
 (channels, bits), and delivers every crop with the bank's one channel count through
@@ -565,6 +566,154 @@ class FlacBank:
         return _features("FlacBank", self.device, len(self), self.channels, [(self, None)], lambda f: (0, f), file, start, frames,
                          n_fft, hop, filters, log, floor, dtype, out, strict, None if rate is None else int(rate),
                          self.sample_rates.__getitem__)
+
+    def _tables(self):
+        return (self._data.data_ptr(), self._first, self._off.data_ptr(), self._fbytes.data_ptr(), self._ires.data_ptr(),
+                self._pos.data_ptr(), self._totals.data_ptr())
+
+    def levels(self, hop: int, span: int = 1 << 20, scratch_bytes: int = 1 << 30) -> "BankLevels":
+        """The levels of the whole bank in one pass, nothing delivered: every file cut into blocks of
+        `hop` samples (the last perhaps short), and of every block and channel the peak max |x|, the
+        exact sum and the energy -- the exact sum of squares rounded once to float64 -- by the rule of
+        flacgpu_levels_windows_device -> BankLevels.  A file is measured in windows of the largest
+        multiple of hop that is not above max(span, hop) samples, so every block lies in one window;
+        the windows go in calls of at most 65535 whose covering frames fit scratch_bytes of decoded
+        PCM (a call holds one window at least), queued on torch.cuda.current_stream(device); the
+        method waits for them and raises FlacGpuError for a window that is not OK."""
+        import torch
+
+        if self._dec is None:
+            raise ValueError("FlacBank: closed")
+        hop, span, scratch_bytes = int(hop), int(span), int(scratch_bytes)
+        if not 1 <= hop <= flacgpu.LEVELS_MAX_HOP:
+            raise ValueError(f"FlacBank.levels: the hop is 1 to 2^31 - 1 samples, not {hop}")
+        if span < 1 or scratch_bytes < 1:
+            raise ValueError("FlacBank.levels: span and scratch_bytes are at least 1")
+        C, per = self.channels, self.channels * (self.bits // 8)
+        win = max(span, hop) // hop * hop
+        first, blocks, at = [], [], 0
+        for n in self.samples:
+            first.append(at)
+            blocks.append((n + hop - 1) // hop)
+            at += blocks[-1]
+        calls, cur, used = [], [], 0  # a call: [(file, start, count, first record, records)]
+        for i, n in enumerate(self.samples):
+            slack = 2 * int(self._infos[i].max_block_size)  # the covering frames reach a block past either end at most
+            for s in range(0, n, win):
+                count = min(win, n - s)
+                need = (count + slack) * per + 16
+                if cur and (len(cur) == MAX_WINDOWS or used + need > scratch_bytes):
+                    calls.append(cur)
+                    cur, used = [], 0
+                cur.append((i, s, count, (first[i] + s // hop) * C, (count + hop - 1) // hop * C))
+                used += need
+        if cur:
+            calls.append(cur)
+        W = sum(len(c) for c in calls)
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            peak = torch.zeros((at, C), dtype=torch.int32, device=self.device)  # the kernel's uint32
+            total = torch.zeros((at, C), dtype=torch.int64, device=self.device)
+            energy = torch.zeros((at, C), dtype=torch.float64, device=self.device)
+            d_res = torch.empty(32 * max(W, 1), dtype=torch.uint8, device=self.device)
+            row = 0
+            for c in calls:
+                self._dec.levels_windows_device(*self._tables(), [w[:3] for w in c], hop, peak.data_ptr(), total.data_ptr(),
+                                                energy.data_ptr(), [w[3] for w in c], [w[4] for w in c],
+                                                d_res.data_ptr() + 32 * row, stream=st)
+                row += len(c)
+            rows = (flacgpu.WindowResult * max(W, 1)).from_buffer_copy(d_res.cpu().numpy().tobytes())  # waits for st
+            row = 0
+            for c in calls:
+                for i, s, count, _, _ in c:
+                    r = rows[row]
+                    row += 1
+                    if r.status != flacgpu.WINDOW_OK or r.n_samples != count:
+                        raise flacgpu.FlacGpuError(-2, f"FlacBank.levels: file {i} from sample {s} is "
+                                                       f"{WINDOW_STATUS.get(int(r.status), int(r.status))} ({r.n_samples} of {count} samples)")
+            peak = peak.to(torch.int64) & 0xFFFFFFFF
+        return BankLevels(peak, total, energy, first, blocks, hop, list(self.samples), self.bits)
+
+    def crop_levels(self, file: Sequence[int], start: Sequence[int], length: int, strict: bool = True):
+        """The levels of samples [start[w], start[w] + length) of file[w], one block a crop ->
+        (peak, sum, energy, n): int64, int64 and float64 tensors [W, channels] by the rule of
+        flacgpu_levels_windows_device with hop = length, and n[w] the samples crop w really holds, as
+        in crops (a crop that holds none gives zeros).  strict and the stream semantics are those of
+        crops: strict=False returns (peak, sum, energy, n, statuses)."""
+        import torch
+
+        if self._dec is None:
+            raise ValueError("FlacBank: closed")
+        W, length = len(file), int(length)
+        if len(start) != W:
+            raise ValueError("FlacBank.crop_levels: file and start differ in length")
+        if (not 0 <= length <= flacgpu.LEVELS_MAX_HOP or any(not 0 <= int(f) < len(self) for f in file)
+                or any(int(s) < 0 for s in start)):
+            raise ValueError("FlacBank.crop_levels: a file index, a start or the length (at most 2^31 - 1) is out of range")
+        C = self.channels
+        with torch.cuda.device(self.device):
+            st = torch.cuda.current_stream(self.device).cuda_stream
+            peak = torch.zeros((W, C), dtype=torch.int32, device=self.device)  # the kernel's uint32
+            total = torch.zeros((W, C), dtype=torch.int64, device=self.device)
+            energy = torch.zeros((W, C), dtype=torch.float64, device=self.device)
+            d_res = torch.zeros(32 * max(W, 1), dtype=torch.uint8, device=self.device)  # length 0: OK, no samples
+            for w0 in range(0, W if length else 0, MAX_WINDOWS):
+                part = range(w0, min(w0 + MAX_WINDOWS, W))
+                self._dec.levels_windows_device(*self._tables(), [(int(file[w]), int(start[w]), length) for w in part], length,
+                                                peak.data_ptr(), total.data_ptr(), energy.data_ptr(), [w * C for w in part],
+                                                [C] * len(part), d_res.data_ptr() + 32 * w0, stream=st)
+            rows = (flacgpu.WindowResult * max(W, 1)).from_buffer_copy(d_res.cpu().numpy().tobytes())  # waits for st
+            peak = peak.to(torch.int64) & 0xFFFFFFFF
+        n = [int(rows[w].n_samples) for w in range(W)]
+        statuses = [int(rows[w].status) for w in range(W)]
+        if strict:
+            for w, s in enumerate(statuses):
+                if s != flacgpu.WINDOW_OK:
+                    bad = f", frame {rows[w].first_bad_frame}" if s == flacgpu.WINDOW_BAD_FRAME else ""
+                    raise flacgpu.FlacGpuError(-2, f"FlacBank.crop_levels: crop {w} (file {int(file[w])}, start {int(start[w])}) is "
+                                                   f"{WINDOW_STATUS.get(s, s)}{bad}")
+            return peak, total, energy, n
+        return peak, total, energy, n, statuses
+
+
+class BankLevels:
+    """What FlacBank.levels returns: device tensors peak (int64), sum (int64) and energy (float64) of
+    shape [blocks, channels] over all files' blocks, file i's being rows first[i] to first[i] +
+    blocks[i]; block j of a file holds its samples [j * hop, min((j + 1) * hop, samples))."""
+
+    def __init__(self, peak, total, energy, first, blocks, hop, samples, bits):
+        self.peak, self.sum, self.energy = peak, total, energy
+        self.first, self.blocks, self.hop, self.samples, self.bits = first, blocks, hop, samples, bits
+
+    def file(self, i: int):
+        """(peak, sum, energy) of file i: views [blocks[i], channels]."""
+        i = int(i)
+        if not 0 <= i < len(self.first):
+            raise ValueError(f"BankLevels: file {i} is not in 0..{len(self.first) - 1}")
+        a, b = self.first[i], self.first[i] + self.blocks[i]
+        return self.peak[a:b], self.sum[a:b], self.energy[a:b]
+
+    def block_samples(self, i: int):
+        """The samples every block of file i holds: hop, the last block's perhaps fewer (float64 [blocks[i]])."""
+        import torch
+
+        n = torch.full((self.blocks[int(i)],), float(self.hop), dtype=torch.float64, device=self.energy.device)
+        if self.blocks[int(i)]:
+            n[-1] = float(self.samples[int(i)] - (self.blocks[int(i)] - 1) * self.hop)
+        return n
+
+    def rms_dbfs(self, i: int):
+        """10 * log10(energy / samples in the block / 4^(bits - 1)) of file i, float64 [blocks[i], channels]:
+        0 dB is a full-scale square wave; -inf is digital silence.  Torch's arithmetic over the exact
+        energies: not part of the library's rule."""
+        import torch
+
+        e = self.file(i)[2]
+        return 10.0 * torch.log10(e / self.block_samples(i)[:, None] / float(4 ** (self.bits - 1)))
+
+    def active(self, i: int, threshold_db: float):
+        """The blocks of file i where any channel's RMS reaches threshold_db: bool [blocks[i]]."""
+        return (self.rms_dbfs(i) >= float(threshold_db)).any(dim=1)
 
 
 MIX_MAX_CHANNELS = 8

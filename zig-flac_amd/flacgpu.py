@@ -379,6 +379,8 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_decode_windows_device_to": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, P, P, P, P, P, P]),
         "flacgpu_pcm_from_elements_device": (I32, [P, U32, P, P, P, U32, U32, P, P, U64, P, P]),
         "flacgpu_pcm_from_elements_host": (I32, [P, U64, U64, U32, U32, U32, U32, P, SZ, ctypes.POINTER(U64)]),
+        "flacgpu_levels_windows_device": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, P, P, P, P, P, P, P]),
+        "flacgpu_levels_host": (I32, [P, U64, U32, U32, P, P, P]),
     }
     # an older build named by FLACGPU_LIB (same-box A/B runs, tools/ab.sh) may predate later entry
     # points: those stay unbound there; the in-tree library must export every one
@@ -421,6 +423,7 @@ def exported_symbols() -> list:
         "flacgpu_features_table", "flacgpu_features_f32_host", "flacgpu_decode_windows_device_features",
         "flacgpu_pcm_from_elements_device", "flacgpu_pcm_from_elements_host",
         "flacgpu_mix_weights_valid", "flacgpu_mix_weights_f32_host", "flacgpu_decode_windows_device_to",
+        "flacgpu_levels_windows_device", "flacgpu_levels_host",
     ]
 
 
@@ -722,6 +725,36 @@ def mix_weights_f32_host(samples, bits: int, weights):
     return y
 
 
+LEVELS_MAX_HOP = (1 << 31) - 1  # of flacgpu_levels_windows_device and flacgpu_levels_host
+
+
+def levels_host(x, hop: int):
+    """flacgpu_levels_host (host only): (peak, sum, energy) of the integer samples x [n, C] cut into
+    blocks of `hop` samples -- numpy arrays [ceil(n / hop), C] of uint32, int64 and float64: max |x|,
+    the exact sum, and the exact sum of squares rounded once to the nearest double.  The statement of
+    the rule the device follows bit for bit, for callers and tests: not a decode path."""
+    import numpy as np
+
+    x = np.asarray(x)
+    if x.ndim != 2 or x.shape[1] < 1 or x.dtype.kind not in "iu":
+        raise ValueError("levels_host: x is an integer array [n, C]")
+    hop = int(hop)
+    if not 1 <= hop <= LEVELS_MAX_HOP:
+        raise ValueError("levels_host: the hop is 1 to 2^31 - 1")
+    if x.size and (int(x.min()) < -(1 << 31) or int(x.max()) >= 1 << 31):
+        raise ValueError("levels_host: a sample is outside 32 bits")
+    x = np.ascontiguousarray(x, dtype=np.int32)
+    n, C = x.shape
+    blocks = (n + hop - 1) // hop
+    peak = np.zeros((max(blocks, 1), C), dtype=np.uint32)[:blocks]
+    total = np.zeros((max(blocks, 1), C), dtype=np.int64)[:blocks]
+    energy = np.zeros((max(blocks, 1), C), dtype=np.float64)[:blocks]
+    _check(load_library().flacgpu_levels_host(x.ctypes.data if n else None, n, C, hop, peak.ctypes.data if n else None,
+                                              total.ctypes.data if n else None, energy.ctypes.data if n else None),
+           "levels_host")
+    return peak, total, energy
+
+
 def pcm_from_elements_host(x, bits: int, sample_format: int, planar: bool = True, samples: Optional[int] = None,
                            plane_stride: Optional[int] = None):
     """flacgpu_pcm_from_elements_host (host only): (PCM bytes rounded up to 4 with zero pads, clipped)
@@ -837,6 +870,23 @@ class _DecodeOps:
                                d_stream_samples, windows),
             sample_format, flags, d_out, _u64s(out_offsets), _u64s(out_caps), d_results, _stream(stream)),
             "decode_windows_device_as")
+
+    def levels_windows_device(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int, d_frame_bytes: int,
+                              d_index_results: int, d_frame_first_sample: int, d_stream_samples: int,
+                              windows: Sequence, hop: int, d_peak: int, d_sum: int, d_energy: int,
+                              out_offsets: Sequence[int], out_caps: Sequence[int], d_results: int,
+                              stream: Optional[int] = None) -> None:
+        """flacgpu_levels_windows_device: the windows of decode_windows_device measured, not delivered:
+        every window cut into blocks of `hop` samples, and of block j, channel c the peak (uint32), the
+        sum (int64) and the energy (float64) at record out_offsets[w] + j * channels + c of d_peak,
+        d_sum and d_energy; out_caps in records too."""
+        if not 0 <= int(hop) < 1 << 32:
+            raise FlacGpuError(-2, "levels_windows_device: hop is not in 0..2^32-1")
+        _check(self.lib.flacgpu_levels_windows_device(
+            *self._window_args(d_data, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                               d_stream_samples, windows),
+            int(hop), d_peak, d_sum, d_energy, _u64s(out_offsets), _u64s(out_caps), d_results, _stream(stream)),
+            "levels_windows_device")
 
     def decode_windows_device_mix(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int, d_frame_bytes: int,
                                   d_index_results: int, d_frame_first_sample: int, d_stream_samples: int,
