@@ -856,6 +856,65 @@ int flacgpu_decode_windows_device_to(flacgpu_ctx *ctx, const uint8_t *d_data,
                                      const flacgpu_window_delivery *how,
                                      void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
                                      flacgpu_window_result *d_results, void *hip_stream);
+/* The same delivery convolved with a FIR filter of the window's choice: band-limiting, a microphone
+ * or device response, pre-emphasis, a tilt, a short room response.  The rule.  x is one output
+ * channel of the delivery as FLACGPU_SAMPLE_F32 elements at the delivered rate -- what _as, _mix or
+ * the weighted mix of _to delivers, or _resample where the rates differ -- `total` samples, +0.0f
+ * outside [0, total).  A filter has T taps h[0 .. T), 1 <= T <= 4096, all finite, and a delay d,
+ * 0 <= d < T.  Element t of a window that starts at sample `start` is y = +0.0f, then for
+ * k = 0 .. T - 1 in this order y = fmaf(h[k], x[start + t + d - k], y): one accumulator, one correctly
+ * rounded fused multiply-add a tap, subnormals kept; a y that is zero is delivered as +0.0f.  Nothing
+ * reassociates, splits, shortens or skips a step.  (The device adds steps of a zero tap times a
+ * finite sample before and after the T: they change no accumulator but -0.0f, which only the
+ * underflow of a negative product or sum to zero produces and the last clause removes on both
+ * sides.)  d re-centres a linear-phase filter (d = (T - 1) / 2) or a response's direct path, so
+ * that labels stay aligned; {1.0f} with d = 0 delivers the unfiltered crop bit for bit, which is how
+ * one call mixes filtered and unfiltered crops.  The count is clipped to the stream as in _as:
+ * n_samples is the part of [start, start + count) inside the stream at the delivered rate; elements
+ * t < n follow the rule and read the stream's own samples before and after the window, zeros only
+ * past the file's ends; with FLACGPU_DELIVER_PAD the rest of the window is +0.0f, without it the
+ * rest is not written.  FLACGPU_SAMPLE_F32 is y; F16 and BF16 are y rounded to nearest-even as the
+ * weighted mix's are (F16 is infinity from 65520 on); FLACGPU_SAMPLE_I32 is not offered.
+ * flacgpu_fir_f32_host (host only) is this rule over one channel x[0 .. total), total <= 2^40,
+ * count + n_taps - 1 < 2^31: y[t] for t < *n, +0.0f for the rest of the `count`.  It is a statement
+ * of the rule for callers and tests, bit for bit what the device delivers; it is NOT a decode path.
+ * The call.  `how` selects format, flags, masks or weights and rates exactly as
+ * flacgpu_decode_windows_device_to does (K output channels); how->features must be NULL.  d_taps is
+ * DEVICE memory the caller owns, taps_len floats, 4-byte aligned: a response bank is built once,
+ * and the library neither copies nor inspects it.  Its taps must be finite: with a tap that is not,
+ * the values are unspecified, but every write stays inside the window's elements.  filters[n_filters]
+ * and window_filter[n_windows] are HOST arrays: window w goes through filters[window_filter[w]],
+ * whose row r is the `taps` floats from d_taps + offset + r * taps; rows = 1: every output channel
+ * uses row 0; rows = K: channel k uses row k (binaural or array responses after a mono-to-K mix).
+ * FLACGPU_ERR_INVALID_INPUT before any device work: a NULL or misaligned d_taps or a NULL filters
+ * where n_filters > 0, taps outside 1 .. 4096, delay >= taps, rows neither 1 nor K, reserved != 0,
+ * offset + rows * taps > taps_len, window_filter[w] >= n_filters, count + taps - 1 >= 2^31,
+ * FLACGPU_SAMPLE_I32 or an unknown format, how->features != NULL, and every argument error of the
+ * call `how` describes.  Layout, TOO_SMALL (decided from n and the count as in _as, with K channels,
+ * but on the device, after the span has been decoded),
+ * BAD_INDEX and BAD_FRAME are as in _as; a window that is not OK writes nothing.  first_frame and
+ * n_frames of a result are those of the covering frames of the samples
+ * [start + d - (T - 1), start + count + d) inside the stream -- through the resampler's own reach
+ * where the rates differ -- and BAD_FRAME is over them.  The call runs in two stages as _features
+ * does: the window delivery itself leaves every window's span as F32 in scratch the context owns,
+ * then one kernel runs the chains on the f32-input matrix instructions, whose accumulation is the
+ * chain above bit for bit.  The one wait for the covers, the 65535-window limit, the chunks and the
+ * stream semantics are those of flacgpu_decode_windows_device; the filter kernel is not timed. */
+typedef struct { uint64_t offset; uint32_t taps, delay, rows, reserved; } flacgpu_fir;
+int flacgpu_fir_f32_host(const float *x, uint64_t total, const float *taps, uint32_t n_taps, uint32_t delay,
+                         uint64_t start, uint64_t count, float *y, uint64_t *n);
+int flacgpu_decode_windows_device_fir(flacgpu_ctx *ctx, const uint8_t *d_data,
+                                      uint32_t n_streams, const uint64_t *table_first,
+                                      const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                      const flacgpu_index_result *d_index_results,
+                                      const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples,
+                                      uint32_t n_windows, const uint32_t *window_stream, const uint64_t *window_start,
+                                      const uint64_t *window_count,
+                                      const flacgpu_window_delivery *how,
+                                      const float *d_taps, uint64_t taps_len, uint32_t n_filters, const flacgpu_fir *filters,
+                                      const uint32_t *window_filter,
+                                      void *d_out, const uint64_t *out_offsets, const uint64_t *out_caps,
+                                      flacgpu_window_result *d_results, void *hip_stream);
 /* The levels of sample windows: nothing is delivered but three numbers a block and channel.  A
  * stream's samples are the sign-extended integers x[t][c] of its depth.  The window [start, start +
  * count), clipped to n samples as in flacgpu_decode_windows_device, is cut by `hop` into ceil(n / hop)

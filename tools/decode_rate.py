@@ -106,6 +106,18 @@ over the PCM bit for bit; the two tensors are compared with each other (they may
 place: einsum need not be the one chain of fused multiply-adds).  No ratio is claimed in advance.
 
     python tools/decode_rate.py --legs downmix --downmix-out profiles/decode_downmix_rate.json
+
+The fir leg (--fir-out; opt-in, not part of `all`) takes the resample leg's files and windows, both
+channels, f32, planar and padded, through a causal filter of 64, 512 and 4096 taps:
+flacgpu_decode_windows_device_fir against flacgpu_decode_windows_device_as followed by torch, once
+as conv1d and once as an rfft / irfft product, alternated in one process (HIP events, three warm
+calls each, the medians of --repeats).  The first outputs of the first and the last window are
+compared with flacgpu.fir_f32_host over the PCM bit for bit; the torch routes, which read zeros
+before the crop where the call reads the file, are compared with the call on the interior samples,
+the largest difference relative to the largest value.  No ratio is claimed in advance, and the
+kernel's own time is not separated from the call's.
+
+    python tools/decode_rate.py --legs fir --fir-out profiles/decode_fir_rate.json
 """
 import argparse
 import contextlib
@@ -895,6 +907,89 @@ def resample_rate(n_files: int, frames_each: int, window: int, warmup: int, repe
     return res
 
 
+def fir_rate(n_files: int, frames_each: int, window: int, repeats: int, taps_list=(64, 512, 4096)) -> dict:
+    """The resample leg's files and windows delivered through a causal FIR filter (delay 0) of 64,
+    512 and 4096 taps, one call of flacgpu_decode_windows_device_fir, against what a user does today:
+    flacgpu_decode_windows_device_as (F32, planar) and then torch, once as conv1d over the crop
+    padded with zeros on the left and once as an rfft / irfft product.  Both torch routes read zeros
+    where the call reads the file's samples before the crop, so they are compared on the interior
+    samples t >= taps - 1 only.  HIP events around each route, three warm calls each, alternated."""
+    import numpy as np
+    import torch
+
+    import flacgpu
+
+    with resident_windows(n_files, frames_each, window) as r:
+        enc, ch, bits, dev, pcm, n_each, st, crops = r.enc, r.ch, r.bits, r.dev, r.pcm, r.n_each, r.st, r.crops
+        tables, d_wres, start = r.tables, r.d_wres, r.start
+        r.positions()
+        planar_pad = flacgpu.DELIVER_PLANAR | flacgpu.DELIVER_PAD
+        offs, caps = [i * ch * window for i in range(n_files)], [ch * window] * n_files
+        x_as = torch.zeros((n_files, ch, window), dtype=torch.float32, device=dev)
+        x_fir = torch.zeros((n_files, ch, window), dtype=torch.float32, device=dev)
+        res = {"files": n_files, "frames_per_file": frames_each, "channels": ch, "bits": bits, "window_samples": window,
+               "window_start": start, "layout": "f32, planar, padded", "delay": 0, "warm_calls": 3, "repeats": repeats,
+               "clock": "HIP events around each route on the current stream, the routes alternated",
+               "kernel_own_time": "not measured: the call is timed whole (stage 1 decodes taps - 1 samples more than _as)"}
+
+        def deliver():
+            enc.decode_windows_device_as(*tables, crops, flacgpu.SAMPLE_F32, planar_pad, x_as.data_ptr(), offs, caps,
+                                         d_wres.data_ptr(), stream=st)
+            return x_as
+
+        for T in taps_list:
+            rng = np.random.RandomState(T)
+            h = (rng.uniform(-1.0, 1.0, T) * np.exp(-np.arange(T) / (T / 3.0))).astype(np.float32)
+            d_h = torch.from_numpy(h).to(dev)
+            w_conv = d_h.flip(0).reshape(1, 1, T).contiguous()
+            n_fft = 1 << (window + T - 2).bit_length()
+            H = torch.fft.rfft(d_h, n_fft)
+
+            def fir():
+                enc.decode_windows_device_fir(*tables, crops, flacgpu.SAMPLE_F32, planar_pad, d_h.data_ptr(), T, [(0, T, 0, 1)],
+                                              [0] * n_files, x_fir.data_ptr(), offs, caps, d_wres.data_ptr(), stream=st)
+                return x_fir
+
+            def as_then_conv1d():
+                x = deliver().reshape(n_files * ch, 1, window)
+                return torch.nn.functional.conv1d(torch.nn.functional.pad(x, (T - 1, 0)), w_conv).reshape(n_files, ch, window)
+
+            def as_then_fft():
+                return torch.fft.irfft(torch.fft.rfft(deliver(), n_fft) * H, n_fft)[..., :window]
+
+            legs = {"fir_f32": fir, "as_f32_then_conv1d": as_then_conv1d, "as_f32_then_rfft_irfft": as_then_fft}
+            for _ in range(3):
+                for fn in legs.values():
+                    fn()
+                    enc.sync_check(st)
+                    assert r.results() == [(0, window)] * n_files
+            # the expectation from the PCM: the host statement of the rule over channel 0's elements
+            check = 2048
+            v = np.frombuffer(pcm, dtype=np.int16).reshape(n_each, ch)[:, 0].astype(np.float32) * np.float32(2.0 ** -(bits - 1))
+            want = torch.from_numpy(flacgpu.fir_f32_host(v, h, 0, start, check)[0])
+            got = fir().clone()
+            assert torch.equal(got[0, 0, :check].cpu(), want) and torch.equal(got[-1, 0, :check].cpu(), want), \
+                "the device differs from the host rule"
+            top = float(got.abs().max())
+            diff = {k: float((legs[k]()[..., T - 1:] - got[..., T - 1:]).abs().max()) / top for k in list(legs)[1:]}
+            ms = {k: [] for k in legs}
+            for _ in range(repeats):  # alternated
+                for k, fn in legs.items():
+                    ms[k].append(event_ms(fn))
+            leg = {k: summary(ms[k], keep=True) for k in legs}
+            for k, v_ in diff.items():
+                leg[k]["max_interior_difference_over_max_value"] = v_
+                leg[k]["x_fir"] = leg[k]["ms_median"] / leg["fir_f32"]["ms_median"]
+            leg["outputs_checked_against_the_host_rule"] = 2 * check
+            leg["rfft_size"] = n_fft
+            res[f"taps_{T}"] = leg
+        ms_as = []
+        for _ in range(repeats):
+            ms_as.append(event_ms(deliver))
+        res["as_f32"] = summary(ms_as, keep=True)
+    return res
+
+
 def levels_rate(n_files: int, frames_each: int, window: int, warmup: int, repeats: int) -> dict:
     """The resample leg's files and windows measured, not delivered: flacgpu_levels_windows_device at
     hop 441 and at hop = the window, against flacgpu_decode_windows_device_as (I32, planar) followed
@@ -1174,11 +1269,12 @@ def main():
     ap.add_argument("--cpu-frames", type=int, default=512)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=10)
-    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix", "resample", "features", "write", "downmix", "levels"),
+    ap.add_argument("--legs", choices=("all", "decode", "index", "files", "windows", "deliver", "bigblock", "mix", "resample", "features", "write", "downmix", "levels", "fir"),
                     default="all")
     ap.add_argument("--write-out", default=os.path.join(ROOT, "profiles", "bank_write_rate.json"))
     ap.add_argument("--downmix-out", default=os.path.join(ROOT, "profiles", "decode_downmix_rate.json"))
     ap.add_argument("--levels-out", default=os.path.join(ROOT, "profiles", "decode_levels_rate.json"))
+    ap.add_argument("--fir-out", default=os.path.join(ROOT, "profiles", "decode_fir_rate.json"))
     ap.add_argument("--resample-out", default=os.path.join(ROOT, "profiles", "decode_resample_rate.json"))
     ap.add_argument("--features-out", default=os.path.join(ROOT, "profiles", "decode_features_rate.json"))
     ap.add_argument("--mix-out", default=os.path.join(ROOT, "profiles", "decode_mix_rate.json"))
@@ -1225,6 +1321,13 @@ def main():
         print(json.dumps({"levels": lr}), flush=True)
         with open(a.levels_out, "w") as f:
             json.dump(lr, f, indent=1)
+        return
+    if a.legs == "fir":  # opt-in: `all` leaves it out
+        fr = {"c2": fir_rate(a.files, a.frames // a.files, a.window, a.repeats)}
+        print(json.dumps({"fir": fr}), flush=True)
+        with open(a.fir_out, "w") as f:
+            json.dump(fr, f, indent=1)
+            f.write("\n")
         return
     if a.legs == "resample":  # opt-in: `all` leaves it out
         rr = {"c2": resample_rate(a.files, a.frames // a.files, a.window, a.warmup, a.repeats)}

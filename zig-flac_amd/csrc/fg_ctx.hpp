@@ -96,7 +96,8 @@ struct FG_LOCAL EncState {
 // and their scan, the expected frame table of a verify, and a chunk's frame table and results in
 // the host-buffer decodes (decode_chunk).  Those decodes' frames and PCM are grow-only.  The feature
 // delivery (fg_features.hpp) adds what its first stage leaves for k_features: the windows' extended
-// spans as planar F32 (feat_x) and their records and stage-1 results (feat_win), grow-only.  The
+// spans as planar F32 (feat_x) and their records and stage-1 results (feat_win), grow-only; the
+// filtered delivery (fg_fir.hpp) leaves the same there for k_window_fir.  The
 // weighted channel mix (fg_deliver.hpp) adds the weight matrices of the window calls, found again by
 // their content (mix_weights: the last kMaxMixWeights of them).
 struct FG_LOCAL MixWeights {
@@ -234,6 +235,7 @@ namespace quantize {
 struct Stream;
 }
 struct FeatWindow;
+struct FirWindow;
 
 // fg_api.cpp: an event of the context's pool, or a new one (empty: none could be created)
 FG_LOCAL Event get_event(flacgpu_ctx *c);
@@ -298,6 +300,11 @@ hipError_t launch_features(const FeatWindow *wins, const window::WindowResult *s
                            const resample::Ratio &rt, const float *x, const float *table, const float *filters, uint8_t *out,
                            window::WindowResult *results, const feat::Params &ft, uint32_t K, uint32_t format, uint32_t n,
                            uint64_t max_items, hipStream_t st);
+// fg_fir.hip: stage 2 of the filtered delivery, over the planar F32 spans stage 1 left in x
+hipError_t launch_window_fir(const FirWindow *wins, const window::WindowResult *stage1, const uint64_t *totals,
+                             const resample::Ratio &rt, const float *x, const float *taps, uint8_t *out,
+                             window::WindowResult *results, uint32_t K, uint32_t format, uint32_t flags, uint32_t n,
+                             uint64_t max_items, hipStream_t st);
 // fg_quantize.hip: k_elements_pcm<B> over a device table of n_streams quantize::Stream rows
 hipError_t launch_elements_pcm(const quantize::Stream *d_tab, uint32_t n_streams, uint64_t max_units, uint8_t *d_pcm,
                                uint64_t *d_clipped, uint32_t C, uint32_t B, uint32_t format, bool planar, hipStream_t st);

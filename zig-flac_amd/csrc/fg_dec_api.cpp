@@ -5,7 +5,8 @@
 // same for many files through one batch (fg_dec_host.cpp decode_files_resident).  Plain C++ over
 // include/flacgpu.h and the shared decode core.  And the host statement of the resampling rule
 // (fg_resample.hpp): the coefficient table of a ratio and the sample rule over F32 elements; and of
-// the feature rule (fg_features.hpp): the STFT table and the rule over one channel of F32 elements.
+// the feature rule (fg_features.hpp): the STFT table and the rule over one channel of F32 elements;
+// and of the filter rule (fg_fir.hpp) over one channel of F32 elements.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -14,6 +15,7 @@
 #include "fg_dec.hpp"
 #include "fg_deliver.hpp"
 #include "fg_features.hpp"
+#include "fg_fir.hpp"
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
 #include "fg_levels.hpp"
@@ -375,6 +377,23 @@ int flacgpu_levels_host(const int32_t *samples, uint64_t n, uint32_t channels, u
             energy[j * channels + c] = levels::acc_energy(a);
         }
     }
+    return FLACGPU_OK;
+}
+
+int flacgpu_fir_f32_host(const float *x, uint64_t total, const float *taps, uint32_t n_taps, uint32_t delay, uint64_t start,
+                         uint64_t count, float *y, uint64_t *n) {
+    if (!n || (total && !x) || total > (1ull << 40) || !taps) return FLACGPU_ERR_INVALID_INPUT;
+    const fir::Filter f{0u, n_taps, delay, 1u, 0u};
+    if (!fir::filter_valid(f, 1u, n_taps) || !fir::span_valid(count, n_taps)) return FLACGPU_ERR_INVALID_INPUT;
+    for (uint32_t k = 0; k < n_taps; k++)
+        if (!std::isfinite(taps[k])) return FLACGPU_ERR_INVALID_INPUT;
+    *n = resample::delivered(total, start, count);
+    if (count == 0) return FLACGPU_OK;
+    if (!y) return FLACGPU_ERR_INVALID_INPUT;
+    // *n > 0 only where start < total <= 2^40: no index below passes 2^42
+    for (uint64_t t = 0; t < *n; t++)
+        y[t] = fir::element(taps, n_taps, delay, start, t, [&](int64_t i) { return i >= 0 && (uint64_t)i < total ? x[i] : 0.0f; });
+    for (uint64_t t = *n; t < count; t++) y[t] = 0.0f;
     return FLACGPU_OK;
 }
 

@@ -7,7 +7,8 @@
 // over resident tables -- as PCM bytes or as tensor elements (fg_deliver.hpp) -- and the device
 // side of flacgpu_decode_files_windows; and the same windows stated and delivered at another
 // sample rate (fg_resample.hpp, fg_resample.hip), and as short-time power spectra and filter-bank
-// rows over that delivery (fg_features.hpp, fg_features.hip); and the same windows measured, not
+// rows over that delivery (fg_features.hpp, fg_features.hip), and convolved with a per-window FIR
+// filter (fg_fir.hpp, fg_fir.hip); and the same windows measured, not
 // delivered: peak, sum and energy a block (fg_levels.hpp, fg_levels.hip).  The host-only side (metadata, the host index,
 // flacgpu_decode_file / _files) is fg_dec_api.cpp.
 #include <hip/hip_runtime.h>
@@ -23,6 +24,7 @@
 #include "fg_dec.hpp"
 #include "fg_deliver.hpp"
 #include "fg_features.hpp"
+#include "fg_fir.hpp"
 #include "fg_index.hpp"
 #include "fg_internal.hpp"
 #include "fg_levels.hpp"
@@ -45,6 +47,7 @@ static_assert(sizeof(idx::IndexResult) == sizeof(flacgpu_index_result), "index r
 static_assert(sizeof(streams::StreamResult) == sizeof(flacgpu_stream_result), "stream result layout");
 static_assert(FLACGPU_INDEX_INVALID == (int)idx::IDX_INVALID && FLACGPU_INDEX_TOO_SMALL == (int)idx::IDX_TOO_SMALL,
               "index status codes");
+static_assert(sizeof(fir::Filter) == sizeof(flacgpu_fir), "filter layout");
 
 namespace {
 
@@ -1111,6 +1114,112 @@ int features_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, c
     return FLACGPU_OK;
 }
 
+// The one body of the filtered delivery, in two stages shaped as features_device's.  Stage 1 is
+// windows_device itself: every window's span [start + d - (T - 1), start + count + d) of its filter,
+// clipped at the stream's start on the host (`clip` samples that k_window_fir reads as zeros), goes as
+// planar padded F32 into the context's scratch (feat_x and feat_win: a call is one delivery or the
+// other).  Stage 2, k_window_fir, reads those planes, stage 1's results and the caller's taps and
+// writes the elements and the results; the capacity rule is deliver::too_small's over the window's
+// own n, which only the device knows, so k_window_fir applies it.
+int fir_device(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
+               const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes, const flacgpu_index_result *d_index_results,
+               const uint64_t *d_frame_first_sample, const uint64_t *d_stream_samples, uint32_t n_windows,
+               const uint32_t *window_stream, const uint64_t *window_start, const uint64_t *window_count,
+               const flacgpu_window_delivery *how, const float *d_taps, uint64_t taps_len, uint32_t n_filters,
+               const flacgpu_fir *filters, const uint32_t *window_filter, void *d_out, const uint64_t *out_offsets,
+               const uint64_t *out_caps, flacgpu_window_result *d_results, void *hip_stream) {
+    if (!c || !how || how->size != sizeof(flacgpu_window_delivery) || how->features || (how->channel_masks && how->channel_weights))
+        return FLACGPU_ERR_INVALID_INPUT;
+    if (!d_data || !table_first || !d_frame_offsets || !d_frame_bytes || !d_index_results || !d_frame_first_sample ||
+        !d_stream_samples || n_windows > 65535u)
+        return FLACGPU_ERR_INVALID_INPUT;
+    const uint32_t format = how->sample_format, flags = how->flags;
+    if (format != deliver::SAMPLE_F32 && format != deliver::SAMPLE_F16 && format != deliver::SAMPLE_BF16)
+        return FLACGPU_ERR_INVALID_INPUT;
+    if ((flags & ~deliver::DELIVER_FLAGS) || ((uintptr_t)d_out & (deliver::elem_size(format) - 1u))) return FLACGPU_ERR_INVALID_INPUT;
+    const uint8_t *masks = how->channel_masks;
+    const float *weights = how->channel_weights;
+    if (masks && !deliver::mix_valid(c->fmt.channels, how->out_channels, masks, format)) return FLACGPU_ERR_INVALID_INPUT;
+    if (weights && !deliver::mixw_valid(c->fmt.channels, how->out_channels, weights, format)) return FLACGPU_ERR_INVALID_INPUT;
+    resample::Ratio rt{0, 0, 0, 0};
+    if ((how->src_rate || how->dst_rate) && !resample::valid_ratio(how->src_rate, how->dst_rate, &rt)) return FLACGPU_ERR_INVALID_INPUT;
+    const uint32_t K = masks || weights ? how->out_channels : c->fmt.channels;
+    if (n_filters && (!d_taps || ((uintptr_t)d_taps & 3u) || !filters)) return FLACGPU_ERR_INVALID_INPUT;
+    for (uint32_t f = 0; f < n_filters; f++) {
+        const fir::Filter ff{filters[f].offset, filters[f].taps, filters[f].delay, filters[f].rows, filters[f].reserved};
+        if (!fir::filter_valid(ff, K, taps_len)) return FLACGPU_ERR_INVALID_INPUT;
+    }
+    if (n_windows && (!window_stream || !window_start || !window_count || !window_filter || !d_out || !out_offsets || !out_caps ||
+                      !d_results))
+        return FLACGPU_ERR_INVALID_INPUT;
+    for (uint32_t w = 0; w < n_windows; w++) {
+        if (window_stream[w] >= n_streams || out_offsets[w] + out_caps[w] < out_offsets[w] || window_filter[w] >= n_filters)
+            return FLACGPU_ERR_INVALID_INPUT;
+        if (!fir::span_valid(window_count[w], filters[window_filter[w]].taps)) return FLACGPU_ERR_INVALID_INPUT;
+    }
+    if (n_windows == 0) return FLACGPU_OK;
+    std::vector<FirWindow> fw;
+    std::vector<uint64_t> s_start, s_count, s_off, s_cap;
+    try {
+        fw.resize(n_windows);
+        s_start.resize(n_windows);
+        s_count.resize(n_windows);
+        s_off.resize(n_windows);
+        s_cap.resize(n_windows);
+    } catch (...) {
+        return FLACGPU_ERR_OUT_OF_MEMORY;
+    }
+    uint64_t x_total = 0, max_items = 0;
+    const uint32_t tile = fir_geometry(1u).tile;  // the same for every T
+    for (uint32_t w = 0; w < n_windows; w++) {
+        const flacgpu_fir &f = filters[window_filter[w]];
+        const fir::Span sp = fir::span(window_start[w], window_count[w], f.taps, f.delay);
+        FirWindow &a = fw[w];
+        a.x_off = x_total;
+        a.s_count = sp.count;
+        a.start = window_start[w];
+        a.out_off = out_offsets[w];
+        a.cap = out_caps[w];
+        a.tap_off = f.offset;
+        a.count = (uint32_t)window_count[w];
+        a.clip = sp.clip;
+        a.stream = window_stream[w];
+        a.taps = f.taps;
+        a.rows = f.rows;
+        a.pad = 0u;
+        s_start[w] = sp.first;
+        s_count[w] = sp.count;
+        s_off[w] = a.x_off;
+        s_cap[w] = (uint64_t)K * sp.count;
+        x_total += (s_cap[w] + 3u) & ~(uint64_t)3u;
+        max_items = std::max(max_items, (uint64_t)K * ((window_count[w] + tile - 1u) / tile));
+    }
+    if (x_total > (1ull << 45)) return FLACGPU_ERR_OUT_OF_MEMORY;
+    HIPCHK(hipSetDevice(c->device));
+    int rc = dec_scratch(c);
+    if (rc) return rc;
+    DecScratch *d = c->dec.get();
+    hipStream_t st = pick_stream(c, hip_stream);
+    HIPCHK(d->feat_x.grow(x_total + 4u, &st));  // an earlier call on this stream may still read the old one
+    FirWindow *d_fw = nullptr;
+    window::WindowResult *d_s1 = nullptr;
+    auto carve = [&](uint8_t *base) {
+        Carve v{base};
+        v.take(n_windows, d_fw);
+        return v.take(n_windows, d_s1);
+    };
+    HIPCHK(fit(d->feat_win, carve, &st));
+    HIPCHK(hipMemcpyAsync(d_fw, fw.data(), (uint64_t)n_windows * sizeof(FirWindow), hipMemcpyHostToDevice, st));
+    rc = windows_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                        d_stream_samples, n_windows, window_stream, s_start.data(), s_count.data(), deliver::SAMPLE_F32,
+                        deliver::DELIVER_PLANAR | deliver::DELIVER_PAD, how->out_channels, masks, d->feat_x.get(), s_off.data(),
+                        s_cap.data(), (flacgpu_window_result *)d_s1, hip_stream, how->src_rate, how->dst_rate, weights);
+    if (rc) return rc;
+    HIPCHK(launch_window_fir(d_fw, d_s1, d_stream_samples, rt, d->feat_x.get(), d_taps, (uint8_t *)d_out,
+                             (window::WindowResult *)d_results, K, format, flags, n_windows, max_items, st));
+    return FLACGPU_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1179,6 +1288,20 @@ int flacgpu_decode_windows_device_to(flacgpu_ctx *c, const uint8_t *d_data, uint
                           d_frame_first_sample, d_stream_samples, n_windows, window_stream, window_start, window_count,
                           how->sample_format, how->flags, how->out_channels, nullptr, d_out, out_offsets, out_caps, d_results,
                           hip_stream, how->src_rate, how->dst_rate, W);
+}
+
+int flacgpu_decode_windows_device_fir(flacgpu_ctx *c, const uint8_t *d_data, uint32_t n_streams, const uint64_t *table_first,
+                                      const uint64_t *d_frame_offsets, const uint32_t *d_frame_bytes,
+                                      const flacgpu_index_result *d_index_results, const uint64_t *d_frame_first_sample,
+                                      const uint64_t *d_stream_samples, uint32_t n_windows, const uint32_t *window_stream,
+                                      const uint64_t *window_start, const uint64_t *window_count,
+                                      const flacgpu_window_delivery *how, const float *d_taps, uint64_t taps_len,
+                                      uint32_t n_filters, const flacgpu_fir *filters, const uint32_t *window_filter, void *d_out,
+                                      const uint64_t *out_offsets, const uint64_t *out_caps, flacgpu_window_result *d_results,
+                                      void *hip_stream) {
+    return fir_device(c, d_data, n_streams, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                      d_stream_samples, n_windows, window_stream, window_start, window_count, how, d_taps, taps_len, n_filters,
+                      filters, window_filter, d_out, out_offsets, out_caps, d_results, hip_stream);
 }
 
 // every chunk's frames and frame table are uploaded, its results land at results + f0

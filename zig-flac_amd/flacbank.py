@@ -15,7 +15,9 @@ of delivering: peak, sum and energy of every block of a hop (flacgpu_levels_wind
 FlacBank holds files of one channel count and depth.  FlacMixBank holds any, as one FlacBank per
 (channels, bits), and delivers every crop with the bank's one channel count through
 flacgpu_decode_windows_device_mix (channel masks) or, where a group's mix is a weight matrix
-(a surround downmix, mid/side, a mean of three), flacgpu_decode_windows_device_to."""
+(a surround downmix, mid/side, a mean of three), flacgpu_decode_windows_device_to.  With a FirBank
+(`crops(fir=, fir_index=)`) every crop is delivered convolved with the filter of its choice, over the
+file's own samples around it, through flacgpu_decode_windows_device_fir."""
 from __future__ import annotations
 
 import ctypes
@@ -68,7 +70,7 @@ def _out_samples(samples: int, src: int, rate: int) -> int:
 
 
 def _crops(who, device, n_files, K, groups, where, check, file, start, length, dtype, planar, pad, out, strict,
-           rate=None, rate_of=None, feat=None):
+           rate=None, rate_of=None, feat=None, fir=None, fir_index=None):
     """The one body of FlacBank.crops and FlacMixBank.crops: crops of K channels from `groups` =
     [(FlacBank, its channel masks, its [K, C] float32 weight matrix or None)], file f being file where(f)[1] of group where(f)[0];
     check(fmt): the caller's own refusals of a format, raised between the dtype's and the crops'.
@@ -76,7 +78,9 @@ def _crops(who, device, n_files, K, groups, where, check, file, start, length, d
     files at another rate are resampled, one call per group and source rate.
     feat: the body of the two `features` as well -- (n_fft, hop, filters or None, rows) after
     flacgpu.features_params: `length` is then the frame count, a crop is [K, rows, length] and its
-    calls are flacgpu_decode_windows_device_features, routed as the crops' are."""
+    calls are flacgpu_decode_windows_device_features, routed as the crops' are.
+    fir: a FirBank, fir_index[w] the filter crop w goes through: the calls are
+    flacgpu_decode_windows_device_fir, routed as the crops' are; without it nothing here changes."""
     import torch
 
     dtype = torch.float32 if dtype is None else dtype
@@ -91,6 +95,10 @@ def _crops(who, device, n_files, K, groups, where, check, file, start, length, d
         raise ValueError(f"{who}: file and start differ in length")
     if length < 0 or any(not 0 <= int(f) < n_files for f in file) or any(int(s) < 0 for s in start):
         raise ValueError(f"{who}: a file index, a start or the length is out of range")
+    if fir is not None:
+        fir._check_crops(who, device, K, fmt, W, fir_index, length)
+    elif fir_index is not None:
+        raise ValueError(f"{who}: fir_index without fir")
     shape = (W, K, length) if planar else (W, length, K)
     if feat is not None:
         shape = (W, K, feat[3], length)
@@ -131,7 +139,14 @@ def _crops(who, device, n_files, K, groups, where, check, file, start, length, d
                 tables = (bank._data.data_ptr(), bank._first, bank._off.data_ptr(), bank._fbytes.data_ptr(),
                           bank._ires.data_ptr(), bank._pos.data_ptr(), bank._totals.data_ptr(), windows, fmt, flags)
                 to = (x.data_ptr(), [w * per_crop for w in part], [per_crop] * len(part), d_res.data_ptr() + 32 * row)
-                if _is_weights(masks):
+                if fir is not None:
+                    weighted = _is_weights(masks)
+                    bank._dec.decode_windows_device_fir(*tables, fir.taps.data_ptr(), fir.taps.numel(), fir.table,
+                                                        [int(fir_index[w]) for w in part], *to,
+                                                        channel_masks=None if weighted else masks,
+                                                        channel_weights=masks if weighted else None, src_rate=src or 0,
+                                                        dst_rate=rate if src else 0, stream=st)
+                elif _is_weights(masks):
                     bank._dec.decode_windows_device_to(*tables[:8], fmt, 0 if feat is not None else flags, *to,
                                                        channel_weights=masks, src_rate=src or 0, dst_rate=rate if src else 0,
                                                        n_fft=feat[0] if feat is not None else None,
@@ -245,6 +260,96 @@ def mel_filters(sample_rate: int, n_fft: int, n_mels: int, fmin: float = 0.0, fm
     if norm == "slaney":
         F *= 2.0 / (hi - lo)
     return np.ascontiguousarray(F, dtype=np.float32)
+
+
+def fir_windowed_sinc(sample_rate: int, f_lo: float, f_hi: Optional[float], taps: int):
+    """(h, delay): a Kaiser-windowed (beta 9, as the resampler's) band-pass of `taps` taps that passes
+    f_lo .. f_hi Hz at sample_rate, as a float32 numpy array, and its delay (taps - 1) // 2, which
+    re-centres it.  f_lo = 0 gives a low-pass; f_hi = None a high-pass from f_lo (odd `taps` only: an
+    even-length symmetric filter has a zero at half the rate).  Computed in numpy float64 -- the ideal
+    response 2 f2 sinc(2 f2 m) - 2 f1 sinc(2 f1 m), m = n - (taps - 1) / 2, f in cycles a sample, times
+    np.kaiser(taps, 9) -- and rounded once."""
+    import numpy as np
+
+    sample_rate, taps = int(sample_rate), int(taps)
+    if sample_rate < 1 or not 1 <= taps <= flacgpu.FIR_MAX_TAPS:
+        raise ValueError(f"fir_windowed_sinc: a sample rate of at least 1 and 1 to {flacgpu.FIR_MAX_TAPS} taps")
+    nyq = sample_rate / 2.0
+    if f_hi is None and taps % 2 == 0:
+        raise ValueError("fir_windowed_sinc: a high-pass (f_hi=None) needs an odd number of taps")
+    hi = nyq if f_hi is None else float(f_hi)
+    lo = float(f_lo)
+    if not (0.0 <= lo < hi <= nyq) or (f_hi is None and lo == 0.0):
+        raise ValueError(f"fir_windowed_sinc: 0 <= f_lo < f_hi <= {nyq} Hz (f_hi=None: f_lo > 0)")
+    m = np.arange(taps, dtype=np.float64) - (taps - 1) / 2.0
+    f1, f2 = lo / sample_rate, hi / sample_rate
+    ideal = 2.0 * f2 * np.sinc(2.0 * f2 * m) - 2.0 * f1 * np.sinc(2.0 * f1 * m)
+    return (ideal * np.kaiser(taps, 9.0)).astype(np.float32), (taps - 1) // 2
+
+
+class FirBank:
+    """FIR filters for `crops(fir=, fir_index=)`, packed once into one float32 tensor on the device.
+
+    filters: a sequence of [T] or [K, T] arrays or tensors, 1 <= T <= 4096 finite taps at the
+    delivered rate: one row serves every output channel, K rows one each (K the channels of the
+    crops: binaural or array responses; a bank serves crops of K channels only where every filter has
+    1 or K rows).  delays: one per filter, 0 .. T - 1 (default 0): element t of
+    a crop is the sum over k of h[k] x[start + t + delay - k], so delay = (T - 1) // 2 re-centres a
+    linear-phase filter and a response's direct-path index keeps labels aligned.  `table` is the host
+    side of flacgpu_decode_windows_device_fir: [(offset, taps, delay, rows)]."""
+
+    def __init__(self, filters: Sequence, delays: Optional[Sequence[int]] = None, device=0):
+        import numpy as np
+        import torch
+
+        who = "FirBank"
+        if len(filters) == 0:
+            raise ValueError(f"{who}: no filters")
+        if delays is not None and len(delays) != len(filters):
+            raise ValueError(f"{who}: {len(delays)} delays for {len(filters)} filters")
+        rows_of, self.table, offset = [], [], 0
+        for i, f in enumerate(filters):
+            if isinstance(f, torch.Tensor):
+                f = f.detach().cpu().numpy()
+            h = np.ascontiguousarray(f, dtype=np.float32)
+            if h.ndim == 1:
+                h = h[None, :]
+            if h.ndim != 2 or not 1 <= h.shape[0] <= 8:
+                raise ValueError(f"{who}: filter {i} is not [T] or [K, T] with 1 to 8 rows")
+            T = h.shape[1]
+            if not 1 <= T <= flacgpu.FIR_MAX_TAPS:
+                raise ValueError(f"{who}: filter {i} has {T} taps, not 1 to {flacgpu.FIR_MAX_TAPS}")
+            if not np.isfinite(h).all():
+                raise ValueError(f"{who}: filter {i} has a tap that is not finite")
+            d = 0 if delays is None else int(delays[i])
+            if not 0 <= d < T:
+                raise ValueError(f"{who}: filter {i} has delay {d}, not 0 to {T - 1}")
+            rows_of.append(h)
+            self.table.append((offset, T, d, h.shape[0]))
+            offset += h.size
+        # ---- everything below needs the device
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        self.taps = torch.from_numpy(np.concatenate([h.reshape(-1) for h in rows_of])).to(self.device)
+
+    def __len__(self) -> int:
+        return len(self.table)
+
+    def _check_crops(self, who, device, K, fmt, W, fir_index, length) -> None:
+        if fmt == flacgpu.SAMPLE_I32:
+            raise ValueError(f"{who}: int32 crops through a filter: a filtered sample has no integer value to deliver")
+        if self.device != device:
+            raise ValueError(f"{who}: the FirBank is on {self.device}, the bank on {device}")
+        if fir_index is None or len(fir_index) != W:
+            raise ValueError(f"{who}: fir needs fir_index, one filter index a crop")
+        for i, (_, _, _, rows) in enumerate(self.table):  # the call refuses a table with such a filter, used or not
+            if rows not in (1, K):
+                raise ValueError(f"{who}: filter {i} has {rows} rows, the crops {K} channels")
+        for i in set(int(i) for i in fir_index):
+            if not 0 <= i < len(self.table):
+                raise ValueError(f"{who}: filter index {i} is not in 0..{len(self.table) - 1}")
+            T = self.table[i][1]
+            if length + T - 1 >= flacgpu.FIR_MAX_SPAN:
+                raise ValueError(f"{who}: {length} samples through {T} taps span 2^31 samples or more")
 
 
 class FlacBank:
@@ -528,7 +633,8 @@ class FlacBank:
         return [_out_samples(n, src, rate) for n, src in zip(self.samples, self.sample_rates)]
 
     def crops(self, file: Sequence[int], start: Sequence[int], length: int, dtype=None, planar: bool = True,
-              pad: bool = True, out=None, strict: bool = True, rate: Optional[int] = None):
+              pad: bool = True, out=None, strict: bool = True, rate: Optional[int] = None, fir: Optional["FirBank"] = None,
+              fir_index: Optional[Sequence[int]] = None):
         """Samples [start[w], start[w] + length) of file[w] for every w -> (x, n): x of shape
         [W, channels, length] (planar) or [W, length, channels] in dtype (torch.float32 -- the
         default --, float16, bfloat16: sample * 2^-(bits-1); int32: the sample), n[w] the samples
@@ -541,12 +647,17 @@ class FlacBank:
         at that rate: crops of files already at it are delivered as without it, bit for bit, the
         others through the polyphase filter of flacgpu_decode_windows_device_resample, one call per
         source rate (and per 65535 crops); float dtypes only; a file whose ratio to `rate` is not
-        served raises ValueError when a crop names it."""
+        served raises ValueError when a crop names it.
+        fir, fir_index: a FirBank and one filter index a crop: crop w is delivered convolved with that
+        filter (its taps at the delivered rate) by the rule of flacgpu_decode_windows_device_fir, over
+        the file's own samples before and after the crop, zeros only past the file's ends; float
+        dtypes only.  A filter of one tap 1.0 delivers the crop as without `fir`, bit for bit."""
         if self._dec is None:
             raise ValueError("FlacBank: closed")
         return _crops("FlacBank", self.device, len(self), self.channels, [(self, None)], lambda f: (0, f), lambda fmt: None,
                       file, start, length, dtype, planar, pad, out, strict,
-                      rate=None if rate is None else int(rate), rate_of=self.sample_rates.__getitem__)
+                      rate=None if rate is None else int(rate), rate_of=self.sample_rates.__getitem__, fir=fir,
+                      fir_index=fir_index)
 
     def features(self, file: Sequence[int], start: Sequence[int], frames: int, n_fft: int, hop: int, filters=None,
                  log: Optional[str] = None, floor: float = 1e-10, dtype=None, out=None, strict: bool = True,
@@ -961,7 +1072,8 @@ class FlacMixBank:
         return len(self.sample_rates)
 
     def crops(self, file: Sequence[int], start: Sequence[int], length: int, dtype=None, planar: bool = True,
-              pad: bool = True, out=None, strict: bool = True):
+              pad: bool = True, out=None, strict: bool = True, fir: Optional["FirBank"] = None,
+              fir_index: Optional[Sequence[int]] = None):
         """FlacBank.crops over the mixed bank -> (x, n), or (x, n, statuses) with strict=False: x of
         shape [W, channels, length] (planar) or [W, length, channels], every crop mixed to the bank's
         channels by its file's masks; n and the statuses in the caller's order.  float dtypes scale
@@ -971,7 +1083,8 @@ class FlacMixBank:
         torch.cuda.current_stream(device) into the one x, and the call waits once per such call of
         a group that has crops, then once for the results.  A damaged frame in one file harms no
         crop of another.  In a bank with a sample_rate, start and length are in samples at that rate
-        (out_samples per file), a group's crops go in one call per source rate, and int32 is refused."""
+        (out_samples per file), a group's crops go in one call per source rate, and int32 is refused.
+        fir, fir_index: as in FlacBank.crops, the filter over the mixed (and resampled) channels."""
         who = "FlacMixBank"
         if not self._groups:
             raise ValueError(f"{who}: closed")
@@ -992,7 +1105,8 @@ class FlacMixBank:
                     raise ValueError(f"{who}: int32 crops of {bank.channels}-channel files: {why}")
 
         return _crops(who, self.device, len(self), self.channels, self._groups, self._where.__getitem__, check, file, start,
-                      length, dtype, planar, pad, out, strict, rate=self.sample_rate, rate_of=self.sample_rates.__getitem__)
+                      length, dtype, planar, pad, out, strict, rate=self.sample_rate, rate_of=self.sample_rates.__getitem__,
+                      fir=fir, fir_index=fir_index)
 
     def features(self, file: Sequence[int], start: Sequence[int], frames: int, n_fft: int, hop: int, filters=None,
                  log: Optional[str] = None, floor: float = 1e-10, dtype=None, out=None, strict: bool = True):

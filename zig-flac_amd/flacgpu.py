@@ -381,6 +381,9 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         "flacgpu_pcm_from_elements_host": (I32, [P, U64, U64, U32, U32, U32, U32, P, SZ, ctypes.POINTER(U64)]),
         "flacgpu_levels_windows_device": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, U32, P, P, P, P, P, P, P]),
         "flacgpu_levels_host": (I32, [P, U64, U32, U32, P, P, P]),
+        "flacgpu_fir_f32_host": (I32, [P, U64, P, U32, U32, U64, U64, P, ctypes.POINTER(U64)]),
+        "flacgpu_decode_windows_device_fir": (I32, [P, P, U32, P, P, P, P, P, P, U32, P, P, P, P, P, U64, U32, P, P, P, P, P, P,
+                                                    P]),
     }
     # an older build named by FLACGPU_LIB (same-box A/B runs, tools/ab.sh) may predate later entry
     # points: those stay unbound there; the in-tree library must export every one
@@ -424,6 +427,7 @@ def exported_symbols() -> list:
         "flacgpu_pcm_from_elements_device", "flacgpu_pcm_from_elements_host",
         "flacgpu_mix_weights_valid", "flacgpu_mix_weights_f32_host", "flacgpu_decode_windows_device_to",
         "flacgpu_levels_windows_device", "flacgpu_levels_host",
+        "flacgpu_fir_f32_host", "flacgpu_decode_windows_device_fir",
     ]
 
 
@@ -725,6 +729,39 @@ def mix_weights_f32_host(samples, bits: int, weights):
     return y
 
 
+class Fir(ctypes.Structure):
+    """flacgpu_fir: one filter of flacgpu_decode_windows_device_fir (host memory, 24 bytes): row r is the
+    `taps` floats from float offset + r * taps of the call's device taps."""
+    _fields_ = [("offset", ctypes.c_uint64), ("taps", ctypes.c_uint32), ("delay", ctypes.c_uint32),
+                ("rows", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+FIR_MAX_TAPS = 4096  # of a filter of flacgpu_decode_windows_device_fir
+FIR_MAX_SPAN = 1 << 31  # count + taps - 1 stays below it
+
+
+def fir_f32_host(x, taps, delay: int, start: int, count: int):
+    """flacgpu_fir_f32_host (host only): (y, n) -- y the float32 [count] elements of the window
+    [start, start + count) of the float32 samples x of one channel through the filter `taps` (1 to
+    4096 finite numbers) with `delay` (0 .. len(taps) - 1), n the samples of the window inside x; y is
+    +0.0 from n on.  The statement of the rule the device follows bit for bit: not a decode path."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    h = np.ascontiguousarray(taps, dtype=np.float32)
+    if x.ndim != 1 or h.ndim != 1:
+        raise ValueError("fir_f32_host: x is one channel of samples, taps one row of numbers")
+    if not 1 <= len(h) <= FIR_MAX_TAPS or not np.isfinite(h).all() or not 0 <= int(delay) < len(h):
+        raise ValueError("fir_f32_host: 1 to 4096 finite taps and a delay below their count")
+    if start < 0 or count < 0 or count + len(h) - 1 >= FIR_MAX_SPAN:
+        raise ValueError("fir_f32_host: start or count is negative, or the span reaches 2^31")
+    y, got = np.zeros(max(count, 1), dtype=np.float32)[:count], ctypes.c_uint64(0)
+    _check(load_library().flacgpu_fir_f32_host(x.ctypes.data if len(x) else None, len(x), h.ctypes.data, len(h), int(delay),
+                                               start, count, y.ctypes.data if count else None, ctypes.byref(got)),
+           "fir_f32_host")
+    return y, got.value
+
+
 LEVELS_MAX_HOP = (1 << 31) - 1  # of flacgpu_levels_windows_device and flacgpu_levels_host
 
 
@@ -995,6 +1032,46 @@ class _DecodeOps:
                                d_stream_samples, windows),
             ctypes.byref(how), d_out, _u64s(out_offsets), _u64s(out_caps), d_results, _stream(stream)),
             "decode_windows_device_to")
+
+    def decode_windows_device_fir(self, d_data: int, table_first: Sequence[int], d_frame_offsets: int, d_frame_bytes: int,
+                                  d_index_results: int, d_frame_first_sample: int, d_stream_samples: int,
+                                  windows: Sequence, sample_format: int, flags: int, d_taps: int, taps_len: int,
+                                  filters: Sequence, window_filter: Sequence[int], d_out: int, out_offsets: Sequence[int],
+                                  out_caps: Sequence[int], d_results: int, channel_masks: Optional[Sequence[int]] = None,
+                                  channel_weights=None, src_rate: int = 0, dst_rate: int = 0,
+                                  stream: Optional[int] = None) -> None:
+        """flacgpu_decode_windows_device_fir: the windows of decode_windows_device_to (masks, weights
+        and rates as there) convolved with a FIR filter each.  d_taps: taps_len float32 in device
+        memory; filters = [(offset, taps, delay, rows)], rows 1 or the output channels, row r at float
+        offset + r * taps of d_taps; window w goes through filters[window_filter[w]]: element t is the
+        fused multiply-add chain over its taps k of x[start + t + delay - k]."""
+        masks = None if channel_masks is None else [int(m) for m in channel_masks]
+        if masks is not None and (not 1 <= len(masks) <= 8 or any(not 0 <= m <= 255 for m in masks)):
+            raise FlacGpuError(-2, "decode_windows_device_fir: 1 to 8 channel masks, each in 0..255")
+        w = None if channel_weights is None else _weights(channel_weights, "decode_windows_device_fir")
+        if w is not None and w.shape[1] != self.channels:  # the library reads K * C floats: it cannot see the rows' length
+            raise FlacGpuError(-2, f"decode_windows_device_fir: rows of {w.shape[1]} weights on a context of {self.channels} channels")
+        for name, r in (("src_rate", src_rate), ("dst_rate", dst_rate)):
+            if not 0 <= int(r) <= 0xFFFFFFFF:
+                raise FlacGpuError(-2, f"decode_windows_device_fir: {name} is not in 0..2^32-1")
+        if len(window_filter) != len(windows):
+            raise FlacGpuError(-2, "decode_windows_device_fir: one filter index a window")
+        for f in filters:
+            if len(f) != 4 or any(not 0 <= int(v) <= 0xFFFFFFFF for v in f[1:]) or not 0 <= int(f[0]) < 1 << 64:
+                raise FlacGpuError(-2, "decode_windows_device_fir: a filter is (offset, taps, delay, rows)")
+        if any(not 0 <= int(i) <= 0xFFFFFFFF for i in window_filter):
+            raise FlacGpuError(-2, "decode_windows_device_fir: a filter index is not in 0..2^32-1")
+        c_filters = (Fir * max(len(filters), 1))(*[Fir(int(f[0]), int(f[1]), int(f[2]), int(f[3]), 0) for f in filters])
+        c_masks = (ctypes.c_uint8 * len(masks))(*masks) if masks is not None else None
+        how = WindowDelivery(ctypes.sizeof(WindowDelivery), int(sample_format), int(flags),
+                             len(masks) if masks is not None else (w.shape[0] if w is not None else 0),
+                             ctypes.cast(c_masks, ctypes.c_void_p) if c_masks is not None else None,
+                             w.ctypes.data if w is not None else None, int(src_rate), int(dst_rate), None, None)
+        _check(self.lib.flacgpu_decode_windows_device_fir(
+            *self._window_args(d_data, table_first, d_frame_offsets, d_frame_bytes, d_index_results, d_frame_first_sample,
+                               d_stream_samples, windows),
+            ctypes.byref(how), d_taps, int(taps_len), len(filters), c_filters, _u32s([int(i) for i in window_filter]), d_out,
+            _u64s(out_offsets), _u64s(out_caps), d_results, _stream(stream)), "decode_windows_device_fir")
 
     def decode_files_windows(self, flacs: Sequence[bytes], windows: Sequence, guard: int = 0,
                              pcm_caps: Optional[Sequence[int]] = None):
